@@ -18,6 +18,12 @@ The JSON line carries
                  stream, against the dense f16 MFMA peak; "step" inside it: the same for all kernels of a step together
   cpu_baseline : the CPU oracle (port of the reference's aten op sequence) timed on this host's cores on a bounded
                  sample of the same workload (rank 0, N = 1 only)
+
+``--dump-outputs DIR`` writes, after the timed steps of the headline, what its last timed step computed as DIR/<name>.npy
+(float32; rank 0): the sample depths and the render outputs of the step's batch, in train mode also the loss and every
+parameter after the optimiser step with its gradient.  An array above 2^20 elements is written as a fixed seeded sample of
+its rows (whole rays for the per-sample arrays), 64 MB at most in all.  The inputs (weights, rays, times, targets) are
+seeded, so the same arguments give the same inputs on every run and two builds can be compared output for output.
 """
 import argparse
 import json
@@ -28,6 +34,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, '2024-hl-spi3s-sunerf_amd'))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -89,6 +96,34 @@ def cpu_baseline(res, samples, mode, seconds_budget=20.0):
                       + f', best of {reps}'}
 
 
+
+
+DUMP_BYTES = 64 << 20           # --dump-outputs: all arrays together
+DUMP_ARRAY_ELEMS = 1 << 20      # an array above this is written as a seeded sample of its rows
+
+
+def dump_outputs(path, arrays):
+    """Writes ``arrays`` (name -> tensor) as ``path/<name>.npy`` in float32 (float64 stays float64).  Arrays above the
+    per-array cap keep a fixed seeded sample of their rows (the same rows for every array with the same number of rows);
+    the cap halves until everything fits into DUMP_BYTES."""
+    def rows_of(t, cap):
+        if t.numel() <= cap:
+            return t
+        n = t.shape[0]
+        keep = max(1, cap // max(1, t.numel() // n))
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        return t[idx.to(t.device)]
+
+    host = {k: t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32) for k, t in arrays.items()}
+    cap = DUMP_ARRAY_ELEMS
+    while True:
+        out = {k: rows_of(t, cap) for k, t in host.items()}
+        if sum(t.numel() * t.element_size() for t in out.values()) <= DUMP_BYTES or cap == 1:
+            break
+        cap //= 2
+    os.makedirs(path, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(path, name + '.npy'), t.cpu().numpy())
 
 
 def two_pass_rate(dev, world, rays_o, rays_d, times, target, batch, samples, steps=10, warmup=2, density_temperature=False):
@@ -180,11 +215,15 @@ def main():
     ap.add_argument('--no-dt', action='store_true', help='skip BASELINE config 5: density-temperature head, two-pass, 128 + 256 '
                                                          'samples per ray (reported under "dt_two_pass")')
     ap.add_argument('--d-filter', type=int, default=D_FILTER, help='MLP width (headline: 256; 512 = reference default)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 40 if args.mode == 'train' else 8
     if args.warmup is None:
         args.warmup = 4 if args.mode == 'train' else 2
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` started directly: become the launcher.  A child process, started before anything here
         # has touched a GPU (never an exec: see the GPU-box rules), one rank per GPU over RCCL; its output is relayed.
@@ -245,6 +284,8 @@ def main():
     ops.emission_render_fwd = timed_render
     # timing-only ablation builds (tools/experiments): their outputs are wrong by construction
     check_finite = os.environ.get('SUNERF_BENCH_ABLATION', '') in ('', '0')
+    # --dump-outputs: the step with this index (the last timed one) keeps references to what it computed
+    last = {'at': args.warmup + args.steps - 1 if args.dump_outputs else -1}
 
     def timed_loop(step, steps, warmup):
         """``warmup`` untimed steps, then exactly ``steps`` steps between two barrier + synchronize pairs; max over ranks."""
@@ -270,8 +311,10 @@ def main():
 
         def step(i):
             z_vals = ops.sample_z(ops.SAMPLER_STRATIFIED, rays_o, rays_d, t_vals, 1.3, 1.0)
-            return ops.emission_render_fwd(model.packed(), rays_o, rays_d, times, z_vals, reg_radius=1.2,
-                                           want_epilogues=True)['image']
+            out = ops.emission_render_fwd(model.packed(), rays_o, rays_d, times, z_vals, reg_radius=1.2, want_epilogues=True)
+            if i == last['at']:
+                last['arrays'] = dict(out, z_vals=z_vals)
+            return out['image']
         flops_step = flops_fwd(D_FILTER)
     else:
         # this rank's rows of the frame; batches of --batch rays cycle through them
@@ -304,6 +347,8 @@ def main():
                                             asinh_scaling=(1.0, 0.005), finite_check=[out['height_map'], out['absorption_map']])
                 loss.backward()
                 opt.step(skip_if_positive=stats[5:6])
+                if i == last['at']:
+                    last['arrays'] = dict(out, z_vals=z, loss=loss)
                 return loss
             return step
         step = make_step(B)
@@ -345,6 +390,18 @@ def main():
     # W^T of the pipelined backward's data gradient: a single fp16 image while the measured probe allows it (ops._pipe_w_probe)
     pipe_single_w = bool(getattr(model.packed(), 'pipe_hi_only', False)) or ops.pipe_w_mode() == 'hi'
     pipe_w_probe = getattr(model.packed(), 'pipe_w_probe', None)
+
+    if args.dump_outputs:
+        # before the extras below, which go on training the same model
+        arrays = last.pop('arrays')
+        last['at'] = -1
+        if args.mode == 'train':
+            for name, p in model.named_parameters():
+                arrays[f'param.{name}'] = p
+                arrays[f'grad.{name}'] = p.grad
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
+        del arrays
 
     extras = {}
     if args.mode == 'train' and not args.no_small_batch and n_local >= 3072:

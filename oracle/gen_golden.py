@@ -31,6 +31,8 @@ Fixtures:
                     low-precision path.  The oracle's emulation of the opt-in HALF arithmetic (fp16 operands of every
                     product, exact sums: oracle/sunerf_oracle.py mlp_forward_half) applied to the reference weights and inputs
                     of the committed g2 and g5b fixtures, with its deviation from the reference's fp32 outputs recorded.
+  g13_model_helpers the small public classes of model.py beside NeRF -- Sine, PositionalEncoding by itself,
+                    TrainablePositionalEncoding, EmissionModel's parameter names and shapes -- on 50 seeded points
 """
 import os
 import sys
@@ -232,6 +234,7 @@ def main():
     gen_g10(ref)
     gen_g11(ref)
     gen_g12(ref)
+    gen_g13(ref)
     ref_import.release_reference()
 
 
@@ -465,6 +468,20 @@ def gen_g12(_ref=None):
         g5b__image_deviation_from_fp32=dev(p16['image'], g5b['out__coarse_image']))
 
 
+def gen_g13(ref):
+    """The reference's model.py helpers on one seeded input (the drop-in package keeps them)."""
+    import importlib
+    M = importlib.import_module('sunerf.model.model')
+    x = torch.rand(50, 4, generator=torch.Generator().manual_seed(9)) * 4 - 2
+    torch.manual_seed(0)
+    tpe = M.TrainablePositionalEncoding(4, n_freqs=6)
+    em = M.EmissionModel(d_filter=32, n_layers=3)
+    with torch.no_grad():
+        npz('g13_model_helpers', x=x, tpe=tpe(x), tpe_freq=tpe.frequencies, tpe_d_output=tpe.d_output, sine=M.Sine(1.7)(x),
+            pe=M.PositionalEncoding(4, 10)(x), em_keys=np.array(sorted(em.state_dict().keys())),
+            em_shapes=np.array([tuple(v.shape) + (0,) * (2 - v.ndim) for _, v in sorted(em.state_dict().items())]))
+
+
 def compare_with_committed(out_dir):
     """Bit-compares every array of every fixture in ``out_dir`` with the committed file of the same name.
     Returns a list of human-readable differences (empty = the script reproduces the committed fixtures)."""
@@ -497,7 +514,8 @@ def generate(out_dir=None, only=None):
             torch.set_num_threads(1)
             ref = ref_import.import_reference()
             for a in only:
-                {'g7': gen_g7, 'g8': gen_g8, 'g9': gen_g9, 'g10': gen_g10, 'g11': gen_g11, 'g12': gen_g12}[a](ref)
+                {'g7': gen_g7, 'g8': gen_g8, 'g9': gen_g9, 'g10': gen_g10, 'g11': gen_g11, 'g12': gen_g12,
+                 'g13': gen_g13}[a](ref)
             ref_import.release_reference()
         else:
             main()
@@ -511,10 +529,10 @@ if __name__ == '__main__':
     ap.add_argument('--out', default=None, help='write the fixtures here instead of tests/golden')
     ap.add_argument('--check', action='store_true',
                     help='regenerate into a scratch directory and bit-compare with the committed fixtures')
-    ap.add_argument('only', nargs='*', help='regenerate only these (g7 g8 g9 g10 g11 g12)')
+    ap.add_argument('only', nargs='*', help='regenerate only these (g7 ... g13)')
     args = ap.parse_args()
-    if any(a not in ('g7', 'g8', 'g9', 'g10', 'g11', 'g12') for a in args.only):
-        ap.error('only g7 g8 g9 g10 g11 g12 can be regenerated on their own')
+    if any(a not in ('g7', 'g8', 'g9', 'g10', 'g11', 'g12', 'g13') for a in args.only):
+        ap.error('only g7 ... g13 can be regenerated on their own')
     if args.check:
         import tempfile
         with tempfile.TemporaryDirectory() as tmp:

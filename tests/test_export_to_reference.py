@@ -2,7 +2,8 @@
 into the REFERENCE's own classes and the reference's own code renders from it -- what a user does who trains here and then
 runs the reference's evaluation scripts (``evaluation/image_render.py`` / ``video.py`` are not rebuilt).
 
-Container only (needs ``/root/reference``; skipped on the GPU box).  The reference side runs in a child interpreter whose
+The first two tests need the reference checkout (``/root/reference``; skipped elsewhere); the third compares with
+fixture g13, which ``oracle/gen_golden.py`` writes from the reference's own code.  The reference side runs in a child interpreter whose
 ``sunerf`` package is the reference's: the pickle resolves every class by module path, so the child proves that the mirrored
 classes carry exactly the attributes, sub-module names, parameters and buffers the reference's forward reads.  The child
 runs the reference's forward (with the two one-line shims of ``oracle/ref_import.py`` for the HEAD defects D1 / D2) and its
@@ -20,7 +21,7 @@ import torch
 import sunerf_oracle as orc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='needs the reference checkout (container only)')
+needs_reference = pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='needs the reference checkout (container only)')
 
 CHILD = r'''
 import sys, numpy as np, torch
@@ -47,6 +48,7 @@ print('data_config', sorted(state['data_config'].keys()), state['Rs_per_ds'], st
 '''
 
 
+@needs_reference
 def test_state_file_written_here_renders_in_the_reference(tmp_path):
     sys.path.insert(0, os.path.join(ROOT, '2024-hl-spi3s-sunerf_amd'))
     from sunerf.model.sunerf import save_state
@@ -122,6 +124,7 @@ torch.save({'rendering': own, 'data_config': {'type': 'dt'}, 'Rs_per_ds': 1.0, '
 '''
 
 
+@needs_reference
 def test_density_temperature_state_files_travel_in_both_directions(tmp_path):
     """The DT rendering module carries one xitorch interpolator per channel in the reference (density_temperature.py:132-146)
     and a table buffer here.  (1) written here (xitorch importable -> interpolators built through its constructor), the file
@@ -171,37 +174,18 @@ def test_density_temperature_state_files_travel_in_both_directions(tmp_path):
         assert torch.equal(v, sd[k]), k
 
 
-HELPERS_CHILD = r'''
-import sys, numpy as np, torch
-sys.path.insert(0, sys.argv[1])
-import ref_import
-ref_import.import_reference()
-import sunerf.model.model as M
-x = torch.from_numpy(np.load(sys.argv[2])['x'])
-torch.manual_seed(0)
-tpe = M.TrainablePositionalEncoding(4, n_freqs=6)
-em = M.EmissionModel(d_filter=32, n_layers=3)
-np.savez(sys.argv[3], tpe=tpe(x).detach().numpy(), tpe_freq=tpe.frequencies.detach().numpy(), sine=M.Sine(1.7)(x).numpy(),
-         pe=M.PositionalEncoding(4, 10)(x).numpy(), em_keys=np.array(sorted(em.state_dict().keys())),
-         em_shapes=np.array([tuple(v.shape) + (0,) * (2 - v.ndim) for _, v in sorted(em.state_dict().items())]))
-'''
-
-
-def test_model_module_helpers_equal_the_reference(tmp_path):
+def test_model_module_helpers_equal_the_reference():
     """The small public classes of model.py beside ``NeRF`` -- ``Sine``, ``PositionalEncoding`` applied by itself,
-    ``TrainablePositionalEncoding``, ``EmissionModel`` -- against the reference's own, on the same input."""
+    ``TrainablePositionalEncoding``, ``EmissionModel`` -- against the reference's own on the same input (fixture g13, written
+    by the reference's code: oracle/gen_golden.py)."""
     sys.path.insert(0, os.path.join(ROOT, '2024-hl-spi3s-sunerf_amd'))
     from sunerf.model import model as M
-    x = torch.rand(50, 4, generator=torch.Generator().manual_seed(9)) * 4 - 2
-    inp, out = str(tmp_path / 'x.npz'), str(tmp_path / 'o.npz')
-    np.savez(inp, x=x.numpy())
-    env = {k: v for k, v in os.environ.items() if k != 'PYTHONPATH'}
-    res = subprocess.run([sys.executable, '-c', HELPERS_CHILD, os.path.join(ROOT, 'oracle'), inp, out], env=env,
-                         capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
-    assert res.returncode == 0, res.stderr[-3000:]
-    want = np.load(out)
+    with np.load(os.path.join(ROOT, 'tests', 'golden', 'g13_model_helpers.npz'), allow_pickle=False) as f:
+        want = {k: f[k] for k in f.files}
+    x = torch.from_numpy(want['x'])
+    assert torch.equal(x, torch.rand(50, 4, generator=torch.Generator().manual_seed(9)) * 4 - 2)
     tpe = M.TrainablePositionalEncoding(4, n_freqs=6)
-    assert np.array_equal(tpe.frequencies.detach().numpy(), want['tpe_freq']) and tpe.d_output == 48
+    assert np.array_equal(tpe.frequencies.detach().numpy(), want['tpe_freq']) and tpe.d_output == want['tpe_d_output'] == 48
     assert np.abs(tpe(x).detach().numpy() - want['tpe']).max() <= 1e-6 * np.abs(want['tpe']).max()
     assert np.array_equal(M.Sine(1.7)(x).numpy(), want['sine'])
     assert np.array_equal(M.PositionalEncoding(4, 10)(x).numpy(), want['pe'])

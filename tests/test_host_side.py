@@ -66,9 +66,12 @@ def test_argument_errors_without_gpu(lib):
 
 def test_pipelined_backward_entry_points_without_gpu(lib):
     """include/sunerf_hip.h: the pipelined backward is for a 256-CU device -- without one the workspace query says 0 (= use
-    sunerf_mlp_dgrad + sunerf_mlp_wgrad) and bad arguments are refused before anything touches a device."""
+    sunerf_mlp_dgrad + sunerf_mlp_wgrad), with one it sizes the workspace of the 256-wide network only -- and bad arguments
+    are refused before anything touches a device."""
     import ctypes
-    assert lib.sunerf_bwd_pipe_workspace_bytes(100, 128, 256, 9) == 0
+    pipe_device = torch.cuda.is_available() and torch.cuda.get_device_properties(0).multi_processor_count == 256
+    ws = lib.sunerf_bwd_pipe_workspace_bytes(100, 128, 256, 9)
+    assert ws > 0 if pipe_device else ws == 0
     assert lib.sunerf_bwd_pipe_workspace_bytes(100, 128, 512, 9) == 0
     GW, GB = (ctypes.c_void_p * 9)(), (ctypes.c_void_p * 9)()
     assert lib.sunerf_mlp_backward_pipe(256, 9, 2, None, None, None, None, 4, 128, None, 0, None, None, 0, 0, None) == -1
