@@ -57,6 +57,8 @@ struct DtArgs {
   float* g_log_abs;          // (7,) accumulated
   float* g_vol_c;            // (1,) accumulated
   unsigned* g_absmax_bits;
+  const float* g_weights;    // (N,S) or null (EXTRA backward only)
+  const float* g_reg_q;      // (N,S) or null (EXTRA backward only)
 };
 
 __device__ __forceinline__ int channel_of(float wl) {
@@ -219,6 +221,12 @@ __global__ __launch_bounds__(DT_THREADS) void dt_integral_fwd_kernel(DtArgs a) {
 // suffix sums G_k = sum_{j >= k} dL/dA_j chunk by chunk (descending) and from them the gradients of the two raw outputs of
 // every sample, summed over the channels in the lane (no atomics).  log_abs / vol_c gradients: per-ray lane sums ->
 // workgroup sums in LDS -> 8 atomic adds per workgroup.
+// EXTRA: also the gradients arriving at the two other outputs of raw2outputs (density_temperature.py:267-271),
+//   q = relu(inf0):              g_inf0 += g_q [inf0 > 0]
+//   w = q / (sum_s q + 1e-10):   g_inf0 += [inf0 > 0] (g_w - sum_s g_w w) / (sum_s q + 1e-10)
+// with the two per-ray sums taken by the ray's own 32 lanes before the reverse sweep (the sum of q in the forward kernel's
+// order).  EXTRA = false is the kernel of sunerf_dt_integral_bwd as it always was.
+template <bool EXTRA>
 __global__ __launch_bounds__(DT_THREADS) void dt_integral_bwd_kernel(DtArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];    // tables | g_kappa[7] g_vol | [DT_RAYS][S][NCH] exp(-A)
   float* tab = lds;
@@ -260,6 +268,22 @@ __global__ __launch_bounds__(DT_THREADS) void dt_integral_bwd_kernel(DtArgs a) {
     if (j <= S - 3) w += zp1 - z0;
     return 0.5f * w;
   };
+  float inv_denom = 0.f, gw_dot_w = 0.f;
+  if (EXTRA && a.g_weights) {
+    float sum = 0.f;
+    for (int c = 0; c < n_chunks; ++c) {
+      const int i = 32 * c + n;
+      if (i < S) sum += fmaxf(r[2 * i] + a.base_rho, 0.f);
+    }
+    const float denom = sum32(sum) + 1e-10f;
+    float dot = 0.f;
+    for (int c = 0; c < n_chunks; ++c) {
+      const int i = 32 * c + n;
+      if (i < S) dot += a.g_weights[ray * S + i] * (fmaxf(r[2 * i] + a.base_rho, 0.f) / denom);
+    }
+    gw_dot_w = sum32(dot);
+    inv_denom = 1.f / denom;
+  }
   for (int c = n_chunks - 1; c >= 0; --c) {
     const int k = 32 * c + n;
     const bool valid = k < S;
@@ -316,6 +340,10 @@ __global__ __launch_bounds__(DT_THREADS) void dt_integral_bwd_kernel(DtArgs a) {
         const float px = ox + dx * zk, py = oy + dy * zk, pz = oz + dz * zk;
         g0 += gr * fmaxf(sqrtf((px * px + py * py) + pz * pz) - a.reg_radius, 0.f);
       }
+      if (EXTRA && inf0 > 0.f) {
+        if (a.g_reg_q) g0 += a.g_reg_q[ray * S + k];
+        if (a.g_weights) g0 += (a.g_weights[ray * S + k] - gw_dot_w) * inv_denom;
+      }
       const f32x2 gg = {g0, g1};
       *(f32x2*)(a.g_raw + ((size_t)ray * S + k) * 2) = gg;
       local_max = fmaxf(local_max, fmaxf(fabsf(g0), fabsf(g1)));
@@ -368,28 +396,143 @@ struct StarArgs {
   const float* rays_o; const float* rays_d; const float* z_vals;
   int64_t n_rays; int S;
   float rho_0, h0, T0, Rs, t_photosphere;
+  const float* params;       // device (Rs, h0, T0, rho_0) or null: then the four host floats above
   float* raw;
 };
 
-__global__ __launch_bounds__(256) void simple_star_kernel(StarArgs a) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= a.n_rays * a.S) return;
-  const int64_t ray = idx / a.S;
-  const float z = a.z_vals[idx];
-  const float x = a.rays_o[ray * 3 + 0] + a.rays_d[ray * 3 + 0] * z;
-  const float y = a.rays_o[ray * 3 + 1] + a.rays_d[ray * 3 + 1] * z;
-  const float w = a.rays_o[ray * 3 + 2] + a.rays_d[ray * 3 + 2] * z;
+// one sample of the field: the radius, ln rho and log10 T, with the reference's masks (radius <= 1, > 1, <= Rs, > Rs)
+struct StarSample {
+  float radius, temp;
+  float ln_rho, log_t;
+};
+
+__device__ __forceinline__ StarSample star_sample(const float* rays_o, const float* rays_d, int64_t ray, float z, float rho_0,
+                                                  float h0, float T0, float Rs, float t_photosphere) {
+  const float x = rays_o[ray * 3 + 0] + rays_d[ray * 3 + 0] * z;
+  const float y = rays_o[ray * 3 + 1] + rays_d[ray * 3 + 1] * z;
+  const float w = rays_o[ray * 3 + 2] + rays_d[ray * 3 + 2] * z;
   const float radius = sqrtf((x * x + y * y) + w * w);
-  float rho = a.rho_0, temp = a.t_photosphere;
+  float rho = rho_0, temp = t_photosphere;
   if (radius > 1.f) {
-    rho = a.rho_0 * expf((1.f / a.h0) * (1.f / radius - 1.f));
-    temp = radius <= a.Rs ? (radius - 1.f) * ((a.T0 - a.t_photosphere) / (a.Rs - 1.f)) + a.t_photosphere : a.T0;
+    rho = rho_0 * expf((1.f / h0) * (1.f / radius - 1.f));
+    temp = radius <= Rs ? (radius - 1.f) * ((T0 - t_photosphere) / (Rs - 1.f)) + t_photosphere : T0;
   }
   // a NaN radius (missed-sphere rays of SphericalSampler) fails every comparison of the reference's masks and leaves the
   // zero-initialised rho / temp: log(0) = -inf
   if (!(radius == radius)) { rho = 0.f; temp = 0.f; }
-  a.raw[idx * 2 + 0] = logf(rho);
-  a.raw[idx * 2 + 1] = log10f(temp);
+  StarSample s;
+  s.radius = radius; s.temp = temp; s.ln_rho = logf(rho); s.log_t = log10f(temp);
+  return s;
+}
+
+// PARAMS: the four stellar parameters come from a device array (the trainable ones, read after every optimiser step without a
+// host round trip); same fp32 arithmetic either way
+template <bool PARAMS>
+__global__ __launch_bounds__(256) void simple_star_kernel(StarArgs a) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= a.n_rays * a.S) return;
+  float rho_0 = a.rho_0, h0 = a.h0, T0 = a.T0, Rs = a.Rs;
+  if (PARAMS) { Rs = a.params[0]; h0 = a.params[1]; T0 = a.params[2]; rho_0 = a.params[3]; }
+  const StarSample s = star_sample(a.rays_o, a.rays_d, idx / a.S, a.z_vals[idx], rho_0, h0, T0, Rs, a.t_photosphere);
+  a.raw[idx * 2 + 0] = s.ln_rho;
+  a.raw[idx * 2 + 1] = s.log_t;
+}
+
+// Backward of the field w.r.t. the four stellar parameters, given g_raw = dL / d(ln rho, log10 T) at every sample.  The masks
+// carry no gradient (the reference's masked assignments, stellar_model.py:53-102); per sample, with L = log10 T:
+//   every non-NaN radius: d ln rho / d rho_0 = 1 / rho_0
+//   radius > 1:           d ln rho / d h0    = -(1/r - 1) / h0^2
+//   1 < r <= Rs:          dL / dT0 = (r - 1) / ((Rs - 1) T ln 10),  dL / dRs = -(r - 1)(T0 - t_ph) / ((Rs - 1)^2 T ln 10)
+//   r > Rs:               dL / dT0 = 1 / (T0 ln 10)
+// so four sums over the samples carry everything, the parameter factors applied once at the end (rho_0 ~ 3e8: divided after
+// summing):  A = sum g0,  B = sum_{r>1} g0 (1 - 1/r),  C = sum_{ramp} g1 (r - 1) / T,  D = sum_{r>Rs} g1.
+// Pass 1: grid-stride over the samples, fp64 sums per lane -> per workgroup (fixed shuffle / LDS tree) -> partials[block][4].
+// Pass 2: one workgroup adds the partials in a fixed order and writes (or adds) the four gradients.  No float atomics: the
+// result does not depend on scheduling, and the grid depends on N*S only.
+constexpr int STAR_BWD_THREADS = 256;
+constexpr int STAR_BWD_MAX_GRID = 1024;
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(STAR_BWD_THREADS) void simple_star_bwd_partial_kernel(StarArgs a, const float* g_raw,
+                                                                                    double* partials) {
+  const float Rs = a.params[0], h0 = a.params[1], T0 = a.params[2], rho_0 = a.params[3];
+  const int64_t total = a.n_rays * a.S;
+  double acc[4] = {0., 0., 0., 0.};
+  for (int64_t idx = (int64_t)blockIdx.x * STAR_BWD_THREADS + threadIdx.x; idx < total;
+       idx += (int64_t)gridDim.x * STAR_BWD_THREADS) {
+    const StarSample s = star_sample(a.rays_o, a.rays_d, idx / a.S, a.z_vals[idx], rho_0, h0, T0, Rs, a.t_photosphere);
+    if (!(s.radius == s.radius)) continue;              // NaN radius: exactly no contribution
+    const f32x2 g = *(const f32x2*)(g_raw + idx * 2);
+    const double r = s.radius;
+    acc[0] += g[0];
+    if (s.radius > 1.f) {
+      acc[1] += (double)g[0] * (1. - 1. / r);
+      if (s.radius <= Rs) acc[2] += (double)g[1] * (r - 1.) / (double)s.temp;
+      else acc[3] += g[1];
+    }
+  }
+  __shared__ double red[STAR_BWD_THREADS / 64][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double v = wave_sum(acc[k]);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    double v = 0.;
+#pragma unroll
+    for (int w = 0; w < STAR_BWD_THREADS / 64; ++w) v += red[w][threadIdx.x];
+    partials[(size_t)blockIdx.x * 4 + threadIdx.x] = v;
+  }
+}
+
+__global__ __launch_bounds__(STAR_BWD_THREADS) void simple_star_bwd_finish_kernel(StarArgs a, const double* partials,
+                                                                                   int n_partials, float* g_params,
+                                                                                   int accumulate) {
+  double acc[4] = {0., 0., 0., 0.};
+  for (int b = threadIdx.x; b < n_partials; b += STAR_BWD_THREADS) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[k] += partials[(size_t)b * 4 + k];
+  }
+  __shared__ double red[STAR_BWD_THREADS / 64][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double v = wave_sum(acc[k]);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double S[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    S[k] = 0.;
+    for (int w = 0; w < STAR_BWD_THREADS / 64; ++w) S[k] += red[w][k];
+  }
+  const double Rs = a.params[0], h0 = a.params[1], T0 = a.params[2], rho_0 = a.params[3], tph = a.t_photosphere;
+  const double ln10 = 2.302585092994045684;
+  // the ramp sums vanish when no sample lies on it: no 0 / 0 for Rs == 1
+  const double ramp = S[2] != 0. ? S[2] / ((Rs - 1.) * ln10) : 0.;
+  const double g[4] = {S[2] != 0. ? -ramp * (T0 - tph) / (Rs - 1.) : 0.,      // Rs
+                       S[1] / (h0 * h0),                                          // h0
+                       ramp + (S[3] != 0. ? S[3] / (T0 * ln10) : 0.),             // T0
+                       S[0] / rho_0};                                             // rho_0
+#pragma unroll
+  for (int k = 0; k < 4; ++k) g_params[k] = accumulate ? (float)((double)g_params[k] + g[k]) : (float)g[k];
+}
+
+int star_args(StarArgs& a, const float* rays_o, const float* rays_d, const float* z_vals, int64_t n_rays, int n_samples) {
+  if (n_rays < 0 || n_samples < 1) return SUNERF_E_BADARG;
+  a.rays_o = rays_o; a.rays_d = rays_d; a.z_vals = z_vals; a.n_rays = n_rays; a.S = n_samples;
+  if (n_rays == 0) return 0;
+  if (!rays_o || !rays_d || !z_vals) return SUNERF_E_BADARG;
+  return 0;
 }
 
 }  // namespace
@@ -397,15 +540,55 @@ __global__ __launch_bounds__(256) void simple_star_kernel(StarArgs a) {
 extern "C" int sunerf_simple_star_field(const float* rays_o, const float* rays_d, const float* z_vals, int64_t n_rays,
                                         int n_samples, float rho_0, float h0, float T0, float Rs, float t_photosphere,
                                         float* raw, void* stream) {
-  if (n_rays < 0 || n_samples < 1) return SUNERF_E_BADARG;
+  StarArgs a = {};
+  if (int rc = star_args(a, rays_o, rays_d, z_vals, n_rays, n_samples)) return rc;
   if (n_rays == 0) return 0;
-  if (!rays_o || !rays_d || !z_vals || !raw) return SUNERF_E_BADARG;
-  StarArgs a;
-  a.rays_o = rays_o; a.rays_d = rays_d; a.z_vals = z_vals; a.n_rays = n_rays; a.S = n_samples;
+  if (!raw) return SUNERF_E_BADARG;
   a.rho_0 = rho_0; a.h0 = h0; a.T0 = T0; a.Rs = Rs; a.t_photosphere = t_photosphere; a.raw = raw;
   const int64_t total = n_rays * n_samples;
   SUNERF_CLEAR_ERROR();
-  hipLaunchKernelGGL(simple_star_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(simple_star_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  SUNERF_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sunerf_simple_star_field_dev(const float* rays_o, const float* rays_d, const float* z_vals, int64_t n_rays,
+                                            int n_samples, const float* params, float t_photosphere, float* raw,
+                                            void* stream) {
+  StarArgs a = {};
+  if (int rc = star_args(a, rays_o, rays_d, z_vals, n_rays, n_samples)) return rc;
+  if (n_rays == 0) return 0;
+  if (!params || !raw) return SUNERF_E_BADARG;
+  a.params = params; a.t_photosphere = t_photosphere; a.raw = raw;
+  const int64_t total = n_rays * n_samples;
+  SUNERF_CLEAR_ERROR();
+  hipLaunchKernelGGL(simple_star_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  SUNERF_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" size_t sunerf_simple_star_bwd_workspace_bytes(void) {
+  return (size_t)STAR_BWD_MAX_GRID * 4 * sizeof(double);
+}
+
+extern "C" int sunerf_simple_star_bwd(const float* rays_o, const float* rays_d, const float* z_vals, int64_t n_rays,
+                                      int n_samples, const float* params, float t_photosphere, const float* g_raw,
+                                      void* workspace, size_t workspace_bytes, float* g_params, int accumulate, void* stream) {
+  StarArgs a = {};
+  if (int rc = star_args(a, rays_o, rays_d, z_vals, n_rays, n_samples)) return rc;
+  if (!params || !g_params || !workspace || (n_rays > 0 && !g_raw)) return SUNERF_E_BADARG;
+  if (workspace_bytes < sunerf_simple_star_bwd_workspace_bytes()) return SUNERF_E_WORKSPACE;
+  a.params = params; a.t_photosphere = t_photosphere;
+  const int64_t total = n_rays * n_samples;
+  int64_t grid = (total + STAR_BWD_THREADS - 1) / STAR_BWD_THREADS;
+  if (grid > STAR_BWD_MAX_GRID) grid = STAR_BWD_MAX_GRID;
+  hipStream_t st = (hipStream_t)stream;
+  SUNERF_CLEAR_ERROR();
+  if (grid > 0)
+    hipLaunchKernelGGL(simple_star_bwd_partial_kernel, dim3((unsigned)grid), dim3(STAR_BWD_THREADS), 0, st, a, g_raw,
+                       (double*)workspace);
+  hipLaunchKernelGGL(simple_star_bwd_finish_kernel, dim3(1), dim3(STAR_BWD_THREADS), 0, st, a, (const double*)workspace,
+                     (int)grid, g_params, accumulate);
   SUNERF_CHECK_LAUNCH();
   return 0;
 }
@@ -432,6 +615,36 @@ extern "C" int sunerf_dt_integral_fwd(const float* raw, const float* z_vals, con
   return 0;
 }
 
+namespace {
+
+template <bool EXTRA>
+int launch_dt_bwd(const DtArgs& a, void* g_absmax, hipStream_t st) {
+  hipError_t e;
+  if ((char*)a.g_vol_c == (char*)a.g_log_abs + NCH * sizeof(float) && (char*)g_absmax == (char*)a.g_vol_c + sizeof(float)) {
+    // the three small outputs in one buffer (what the Python wrapper passes): one clear instead of three
+    if ((e = hipMemsetAsync(a.g_log_abs, 0, (NCH + 2) * sizeof(float), st)) != hipSuccess) return (int)e;
+  } else {
+    if ((e = hipMemsetAsync(g_absmax, 0, 4, st)) != hipSuccess) return (int)e;
+    if ((e = hipMemsetAsync(a.g_log_abs, 0, NCH * sizeof(float), st)) != hipSuccess) return (int)e;
+    if ((e = hipMemsetAsync(a.g_vol_c, 0, sizeof(float), st)) != hipSuccess) return (int)e;
+  }
+  if (a.n_rays == 0) return 0;
+  const size_t lds = ((size_t)2 * NTAB + 8 + (size_t)DT_RAYS * a.S * NCH) * sizeof(float);
+  if (lds > 160 * 1024) return SUNERF_E_UNSUPPORTED;
+  if (lds > 64 * 1024) {
+    e = hipFuncSetAttribute((const void*)dt_integral_bwd_kernel<EXTRA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  SUNERF_CLEAR_ERROR();
+  int64_t groups = (a.n_rays + DT_RAYS - 1) / DT_RAYS;
+  if (groups > DT_MAX_GRID) groups = DT_MAX_GRID;
+  hipLaunchKernelGGL(dt_integral_bwd_kernel<EXTRA>, dim3((unsigned)groups), dim3(DT_THREADS), lds, st, a);
+  SUNERF_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
 extern "C" int sunerf_dt_integral_bwd(const float* raw, const float* z_vals, const float* rays_o, const float* rays_d,
                                       const float* wavelengths, int n_wavelengths, const float* table_logt,
                                       const float* table_resp, const float* log_abs, const float* vol_c, float base_log_density,
@@ -446,27 +659,23 @@ extern "C" int sunerf_dt_integral_bwd(const float* raw, const float* z_vals, con
   a.g_absmax_bits = (unsigned*)g_absmax;
   if (int rc = check_common(a)) return rc;
   if (!g_image || !g_raw || !g_log_abs || !g_vol_c || !g_absmax) return SUNERF_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  if ((char*)g_vol_c == (char*)g_log_abs + NCH * sizeof(float) && (char*)g_absmax == (char*)g_vol_c + sizeof(float)) {
-    // the three small outputs in one buffer (what the Python wrapper passes): one clear instead of three
-    if ((e = hipMemsetAsync(g_log_abs, 0, (NCH + 2) * sizeof(float), st)) != hipSuccess) return (int)e;
-  } else {
-    if ((e = hipMemsetAsync(g_absmax, 0, 4, st)) != hipSuccess) return (int)e;
-    if ((e = hipMemsetAsync(g_log_abs, 0, NCH * sizeof(float), st)) != hipSuccess) return (int)e;
-    if ((e = hipMemsetAsync(g_vol_c, 0, sizeof(float), st)) != hipSuccess) return (int)e;
-  }
-  if (n_rays == 0) return 0;
-  const size_t lds = ((size_t)2 * NTAB + 8 + (size_t)DT_RAYS * n_samples * NCH) * sizeof(float);
-  if (lds > 160 * 1024) return SUNERF_E_UNSUPPORTED;
-  if (lds > 64 * 1024) {
-    e = hipFuncSetAttribute((const void*)dt_integral_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  SUNERF_CLEAR_ERROR();
-  int64_t groups = (n_rays + DT_RAYS - 1) / DT_RAYS;
-  if (groups > DT_MAX_GRID) groups = DT_MAX_GRID;
-  hipLaunchKernelGGL(dt_integral_bwd_kernel, dim3((unsigned)groups), dim3(DT_THREADS), lds, st, a);
-  SUNERF_CHECK_LAUNCH();
-  return 0;
+  return launch_dt_bwd<false>(a, g_absmax, (hipStream_t)stream);
+}
+
+extern "C" int sunerf_dt_integral_bwd_full(const float* raw, const float* z_vals, const float* rays_o, const float* rays_d,
+                                           const float* wavelengths, int n_wavelengths, const float* table_logt,
+                                           const float* table_resp, const float* log_abs, const float* vol_c,
+                                           float base_log_density, float base_log_temperature, float pixel_intensity_factor,
+                                           float reg_radius, int64_t n_rays, int n_samples, const float* g_image,
+                                           const float* g_reg, const float* g_weights, const float* g_reg_q, float* g_raw,
+                                           float* g_log_abs, float* g_vol_c, void* g_absmax, void* stream) {
+  DtArgs a = {};
+  a.raw = raw; a.z_vals = z_vals; a.rays_o = rays_o; a.rays_d = rays_d; a.wavelengths = wavelengths; a.W = n_wavelengths;
+  a.table_logt = table_logt; a.table_resp = table_resp; a.log_abs = log_abs; a.vol_c = vol_c; a.base_rho = base_log_density;
+  a.base_t = base_log_temperature; a.pixel_factor = pixel_intensity_factor; a.reg_radius = reg_radius; a.n_rays = n_rays;
+  a.S = n_samples; a.g_image = g_image; a.g_reg = g_reg; a.g_raw = g_raw; a.g_log_abs = g_log_abs; a.g_vol_c = g_vol_c;
+  a.g_absmax_bits = (unsigned*)g_absmax; a.g_weights = g_weights; a.g_reg_q = g_reg_q;
+  if (int rc = check_common(a)) return rc;
+  if (!g_image || !g_raw || !g_log_abs || !g_vol_c || !g_absmax) return SUNERF_E_BADARG;
+  return launch_dt_bwd<true>(a, g_absmax, (hipStream_t)stream);
 }

@@ -2,7 +2,8 @@
 that pretends to be a trained ``NeRF_DT`` when synthetic observations are rendered (evaluation/image_render.py:236-268).
 
 Same constructor, parameters and state-dict keys; the field itself is evaluated by ``sunerf_simple_star_field`` on the
-device.  ``astropy`` is optional: quantities are converted when given, plain numbers are taken in the reference's own
+device, and it trains like the reference's module: the stellar parameters, absorption scalars and volumetric constant
+receive gradients (``sunerf_simple_star_bwd`` and the DT integral's backward).  ``astropy`` is optional: quantities are converted when given, plain numbers are taken in the reference's own
 units (h0 [Mm], T0 [K], R_s [solar radii], t_photosphere [K], rho_0 [cm^-3])."""
 import torch
 from torch import nn
@@ -50,15 +51,21 @@ class SimpleStar(nn.Module):
             self._const = tuple(float(sp[k]) for k in ('rho_0', 'h0', 'T0', 'Rs'))
         return self._const
 
-    @torch.no_grad()
     def field_on_rays(self, rays_o, rays_d, z_vals):
-        """(N, S, 2) = (ln rho, log10 T) at o + d z; inference only (the reference never trains a SimpleStar)."""
-        rho_0, h0, T0, Rs = self._constants()
-        return ops.simple_star_field(rays_o, rays_d, z_vals, rho_0, h0, T0, Rs, self.t_photosphere)
+        """(N, S, 2) = (ln rho, log10 T) at o + d z.  Differentiable w.r.t. the four ``stellar_parameters`` when gradients are
+        enabled and one of them is trainable (``sunerf_simple_star_bwd``), as the reference's module is; no gradient w.r.t.
+        the rays or z.  Otherwise (inference) the parameters are read as host floats, once per parameter update."""
+        from sunerf.rendering.functional import star_field, star_parameters
+        if torch.is_grad_enabled() and any(p.requires_grad for p in star_parameters(self)):
+            return star_field(self, rays_o, rays_d, z_vals)
+        with torch.no_grad():
+            rho_0, h0, T0, Rs = self._constants()
+            return ops.simple_star_field(rays_o, rays_d, z_vals, rho_0, h0, T0, Rs, self.t_photosphere)
 
     def forward(self, query_points):
-        """(M, >=3) query points -> {'inferences': (M, 2), 'log_abs', 'vol_c'} (stellar_model.py:53-102)."""
-        pts = query_points.reshape(-1, query_points.shape[-1])
+        """(M, >=3) query points -> {'inferences': (M, 2), 'log_abs', 'vol_c'} (stellar_model.py:53-102).  The inferences are
+        differentiable w.r.t. the stellar parameters like :meth:`field_on_rays`, not w.r.t. the query points."""
+        pts = query_points.reshape(-1, query_points.shape[-1]).detach()
         o = torch.zeros(pts.shape[0], 3, dtype=torch.float32, device=pts.device)
         z = torch.ones(pts.shape[0], 1, dtype=torch.float32, device=pts.device)    # o + d * 1 = the point itself, exactly
         raw = self.field_on_rays(o, pts[:, :3].contiguous(), z)

@@ -251,8 +251,10 @@ def emission_raw2outputs(raw, z_vals, rays_d):
 
 class _DtIntegral(torch.autograd.Function):
     """``DensityTemperatureRadiativeTransfer.raw2outputs`` (density_temperature.py:192-271) on given inferences (base offsets
-    already added, as ``NeRF_DT.forward`` returns them).  Differentiable through ``image`` w.r.t. the inferences, the seven
-    absorption scalars and the volumetric constant (what the loss of sunerf.py:187-195 needs)."""
+    already added, as ``NeRF_DT.forward`` returns them).  Differentiable through all three outputs -- ``image``, ``weights``
+    and ``regularizing_quantity`` -- w.r.t. the inferences, and through ``image`` w.r.t. the seven absorption scalars and the
+    volumetric constant, like the reference's graph (a subclass's loss reaches ``weights`` through ``height_map`` and
+    ``regularizing_quantity`` through its ``regularization``, base_tracing.py:99-110)."""
 
     @staticmethod
     def forward(ctx, tables, pixel_factor, inferences, z_vals, rays_d, wavelengths, vol_c, *la):
@@ -263,22 +265,30 @@ class _DtIntegral(torch.autograd.Function):
         ctx.tables, ctx.pixel_factor = tables, pixel_factor
         ctx.save_for_backward(inferences.detach(), z_vals, rays_d, wavelengths, la_vec, vol_c.detach())
         ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(out['weights'], out['reg_q'])
         return out['image'], out['weights'], out['reg_q']
 
     @staticmethod
     def backward(ctx, g_image, g_weights, g_q):
         inferences, z_vals, rays_d, wavelengths, la_vec, vol_c = ctx.saved_tensors
+        if g_image is None and g_weights is None and g_q is None:
+            return (None,) * (7 + la_vec.shape[0])
         if g_image is None:
-            return (None,) * (8 + la_vec.shape[0])
-        g_raw, g_la, g_vc, _ = ops.dt_integral_bwd(inferences, z_vals, torch.zeros_like(rays_d), rays_d, wavelengths, ctx.tables[0],
-                                                   ctx.tables[1], la_vec, vol_c, 0.0, 0.0, ctx.pixel_factor, 0.0,
-                                                   g_image.contiguous(), None)
+            g_image = torch.zeros(z_vals.shape[0], wavelengths.shape[1], dtype=torch.float32, device=z_vals.device)
+        g_raw, g_la, g_vc, _ = ops.dt_integral_bwd_full(inferences, z_vals, torch.zeros_like(rays_d), rays_d, wavelengths,
+                                                        ctx.tables[0], ctx.tables[1], la_vec, vol_c, 0.0, 0.0, ctx.pixel_factor,
+                                                        0.0, g_image.contiguous(), None,
+                                                        None if g_weights is None else g_weights.contiguous(),
+                                                        None if g_q is None else g_q.contiguous())
         return (None, None, g_raw, None, None, None, g_vc.reshape(())) + tuple(g_la[i] for i in range(g_la.shape[0]))
 
 
 def dt_raw2outputs(tables, pixel_factor, inferences, log_abs, vol_c, z_vals, rays_d, wavelengths):
     la = [log_abs[str(w)] for w in ops.AIA_WAVELENGTHS]
+    if not torch.is_grad_enabled() or not any(t.requires_grad for t in [inferences, vol_c] + la):
+        la_vec = torch.stack([p.detach() for p in la])
+        out = ops.dt_integral_fwd(inferences.detach(), z_vals, torch.zeros_like(rays_d), rays_d, wavelengths, tables[0], tables[1],
+                                  la_vec, vol_c, 0.0, 0.0, pixel_factor, 0.0)
+        return {'image': out['image'], 'weights': out['weights'], 'regularizing_quantity': out['reg_q']}
     image, weights, reg_q = _DtIntegral.apply(tables, pixel_factor, inferences, z_vals, rays_d, wavelengths, vol_c, *la)
     return {'image': image, 'weights': weights, 'regularizing_quantity': reg_q}
 
@@ -355,10 +365,18 @@ class _DtPass(torch.autograd.Function):
 def dt_pass(model, tables, pixel_factor, rays_o, rays_d, times, z_vals, wavelengths, reg_radius, want_epilogues):
     """Dict of one DT pass' outputs (image (N,W), weights, regularizing_quantity[, maps, regularization])."""
     if hasattr(model, 'field_on_rays'):
-        # analytic field (SimpleStar) instead of an MLP: same integral, inference only (stellar_model.py, image_render.py:266)
+        # analytic field (SimpleStar) instead of an MLP: same integral (stellar_model.py, image_render.py:266)
+        keys = ['image', 'weights', 'regularizing_quantity'] + (['height_map', 'absorption_map', 'regularization']
+                                                                if want_epilogues else [])
+        la = [model.log_absortpion[str(w)] for w in ops.AIA_WAVELENGTHS]
+        sp = star_parameters(model) if hasattr(model, 'stellar_parameters') else []
+        if sp and torch.is_grad_enabled() and any(p.requires_grad for p in la + sp + [model.volumetric_constant]):
+            outs = _StarDtPass.apply(model, tables, pixel_factor, rays_o, rays_d, z_vals, wavelengths, reg_radius, want_epilogues,
+                                     model.volumetric_constant, *la, *sp)
+            return dict(zip(keys, outs))
         with torch.no_grad():
             raw = model.field_on_rays(rays_o, rays_d, z_vals)
-            la = torch.stack([model.log_absortpion[str(w)].detach() for w in ops.AIA_WAVELENGTHS])
+            la = torch.stack([p.detach() for p in la])
             out = ops.dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, tables[0], tables[1], la,
                                       model.volumetric_constant, model.base_log_density, model.base_log_temperature,
                                       pixel_factor, reg_radius, want_epilogues=want_epilogues)
@@ -373,3 +391,121 @@ def dt_pass(model, tables, pixel_factor, rays_o, rays_d, times, z_vals, waveleng
     keys = ['image', 'weights', 'regularizing_quantity'] + (['height_map', 'absorption_map', 'regularization']
                                                             if want_epilogues else [])
     return dict(zip(keys, outs))
+
+
+# ---- trainable SimpleStar (stellar_model.py:5-102) ------------------------------------------------------------------------
+STAR_KEYS = ('Rs', 'h0', 'T0', 'rho_0')     # the order of the reference's ``stellar_parameters`` and of the C ABI's params[4]
+
+
+def star_parameters(star):
+    """The four stellar parameters of a ``SimpleStar``, in ``STAR_KEYS`` order."""
+    return [star.stellar_parameters[k] for k in STAR_KEYS]
+
+
+def _star_param_array(sp):
+    """(4,) device array of the stellar parameters for the kernels: the slice of the optimiser's flat parameter buffer the four
+    occupy back to back (``ClipAdam``; no copy, and what its step kernel writes is what the next render reads), else a stack."""
+    tags = [bucket_of(p) for p in sp]
+    if all(t is not None for t in tags):
+        owner, first = tags[0][0], tags[0][1]
+        flat = owner.flat_params[first:first + len(sp)]
+        if all(o is owner and off == first + i and k == 1 and p.data_ptr() == flat[i:i + 1].data_ptr()
+               for i, (p, (o, off, k)) in enumerate(zip(sp, tags))):
+            return flat
+    return torch.stack([p.detach() for p in sp])
+
+
+def _star_grads(needs, rays_o, rays_d, z_vals, params, t_photosphere, g_raw, sp):
+    """Gradients of the four stellar parameters for autograd: accumulated by the kernel straight into their slots of a flat
+    gradient bucket when they have them (then autograd gets None), else returned per parameter."""
+    if not any(needs):
+        return (None,) * 4
+    slot = _scalar_head_slice(sp)
+    if slot is not None:
+        ops.simple_star_bwd(rays_o, rays_d, z_vals, params, t_photosphere, g_raw, out=slot)
+        return (None,) * 4
+    g = ops.simple_star_bwd(rays_o, rays_d, z_vals, params, t_photosphere, g_raw)
+    return tuple(g[i] if needs[i] else None for i in range(4))
+
+
+class _StarField(torch.autograd.Function):
+    """``SimpleStar.forward`` at the samples ``o + d z`` (stellar_model.py:53-102): raw (N, S, 2) = (ln rho, log10 T),
+    differentiable w.r.t. the four stellar parameters (not w.r.t. the rays or z)."""
+
+    @staticmethod
+    def forward(ctx, t_photosphere, rays_o, rays_d, z_vals, *sp):
+        params = _star_param_array(sp)
+        raw = ops.simple_star_field_dev(rays_o, rays_d, z_vals, params, t_photosphere)
+        ctx.t_photosphere, ctx.sp = t_photosphere, sp
+        ctx.save_for_backward(rays_o, rays_d, z_vals, params)
+        return raw
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        rays_o, rays_d, z_vals, params = ctx.saved_tensors
+        return (None,) * 4 + _star_grads(ctx.needs_input_grad[4:], rays_o, rays_d, z_vals, params, ctx.t_photosphere,
+                                         g_raw.contiguous().float(), ctx.sp)
+
+
+def star_field(star, rays_o, rays_d, z_vals):
+    """(N, S, 2) field of ``star`` (a ``SimpleStar``) at the samples of the rays through autograd."""
+    return _StarField.apply(star.t_photosphere, rays_o, rays_d, z_vals, *star_parameters(star))
+
+
+class _StarDtPass(torch.autograd.Function):
+    """One fused density/temperature pass of a ``SimpleStar``: field kernel -> DT integral kernel, the ``_DtPass`` of the
+    analytic model.  Differentiable outputs: ``image`` (N,W) and ``regularization``; gradients for the 7 ``log_absortpion``
+    scalars, ``volumetric_constant`` and the 4 ``stellar_parameters`` of this star (coarse and fine are separate
+    instances), added straight into an optimiser's flat bucket when the parameters have slots there.  No gradient w.r.t.
+    rays or z (the resampled z is detached in the reference, sampling.py:120)."""
+
+    @staticmethod
+    def forward(ctx, star, tables, pixel_factor, rays_o, rays_d, z_vals, wavelengths, reg_radius, want_epilogues, vol_c, *scalars):
+        n_la = len(ops.AIA_WAVELENGTHS)
+        la = torch.stack([p.detach() for p in scalars[:n_la]])
+        sp = scalars[n_la:]
+        ctx.set_materialize_grads(False)
+        params = _star_param_array(sp)
+        raw = ops.simple_star_field_dev(rays_o, rays_d, z_vals, params, star.t_photosphere)
+        out = ops.dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, tables[0], tables[1], la, vol_c,
+                                  star.base_log_density, star.base_log_temperature, pixel_factor, reg_radius,
+                                  want_epilogues=want_epilogues)
+        ctx.tables, ctx.pixel_factor, ctx.reg_radius = tables, pixel_factor, reg_radius
+        ctx.base = (star.base_log_density, star.base_log_temperature)
+        ctx.t_photosphere = star.t_photosphere
+        ctx.la_params, ctx.sp, ctx.vol_c_param = tuple(scalars[:n_la]), sp, vol_c
+        ctx.save_for_backward(rays_o, rays_d, z_vals, wavelengths, raw, la, vol_c.detach(), params)
+        outs = [out['image'], out['weights'], out['reg_q']]
+        non_diff = [out['weights'], out['reg_q']]
+        if want_epilogues:
+            outs += [out['height_map'], out['absorption_map'], out['regularization']]
+            non_diff += [out['height_map'], out['absorption_map']]
+        ctx.mark_non_differentiable(*non_diff)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, g_image, g_weights, g_q, g_hm=None, g_am=None, g_reg=None):
+        rays_o, rays_d, z_vals, wavelengths, raw, la, vol_c, params = ctx.saved_tensors
+        n_la = la.shape[0]
+        if g_image is None and g_reg is None:
+            return (None,) * (10 + n_la + 4)
+        if g_image is None:
+            g_image = torch.zeros(z_vals.shape[0], wavelengths.shape[1], dtype=torch.float32, device=z_vals.device)
+        g_raw, g_la, g_vc, _ = ops.dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, ctx.tables[0], ctx.tables[1], la,
+                                                   vol_c, ctx.base[0], ctx.base[1], ctx.pixel_factor, ctx.reg_radius,
+                                                   g_image.contiguous(), g_reg)
+        needs_vc, needs_la = ctx.needs_input_grad[9], ctx.needs_input_grad[10:10 + n_la]
+        la_slot = _scalar_head_slice(ctx.la_params) if all(needs_la) else None
+        vc_slot = _scalar_head_slice([ctx.vol_c_param]) if needs_vc else None
+        if la_slot is not None:
+            la_slot.add_(g_la)
+            g_la_out = (None,) * n_la
+        else:
+            g_la_out = tuple(g_la[i] if needs_la[i] else None for i in range(n_la))
+        if vc_slot is not None:
+            vc_slot.add_(g_vc)
+            g_vc_out = None
+        else:
+            g_vc_out = g_vc.reshape(()) if needs_vc else None
+        g_sp = _star_grads(ctx.needs_input_grad[10 + n_la:], rays_o, rays_d, z_vals, params, ctx.t_photosphere, g_raw, ctx.sp)
+        return (None,) * 9 + (g_vc_out,) + g_la_out + g_sp

@@ -79,6 +79,15 @@ _SIGNATURES = {
     'sunerf_simple_star_field': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, ctypes.c_float,
                                                  ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_f32p,
                                                  c_void]),
+    'sunerf_simple_star_field_dev': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, c_f32p,
+                                                     ctypes.c_float, c_f32p, c_void]),
+    'sunerf_simple_star_bwd_workspace_bytes': (ctypes.c_size_t, []),
+    'sunerf_simple_star_bwd': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, c_f32p, ctypes.c_float,
+                                               c_f32p, c_void, ctypes.c_size_t, c_f32p, ctypes.c_int, c_void]),
+    'sunerf_dt_integral_bwd_full': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int, c_f32p, c_f32p, c_f32p,
+                                                    c_f32p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                    ctypes.c_int64, ctypes.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                                    c_f32p, c_f32p, c_void, c_void]),
     'sunerf_train_workspace_bytes': (ctypes.c_size_t, []),
     'sunerf_training_loss': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int64, c_f32p, ctypes.c_int64,
                                              ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,

@@ -920,3 +920,62 @@ def dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_
             float(base_log_temperature), float(pixel_intensity_factor), float(reg_radius), n, s, _ptr(g_image),
             _ptr(g_reg), _ptr(g_raw), _ptr(g_la), _ptr(g_vc), _ptr(absmax), _stream(dev))
     return g_raw, g_la, g_vc, absmax
+
+
+def dt_integral_bwd_full(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_resp, log_abs, vol_c, base_log_density,
+                         base_log_temperature, pixel_intensity_factor, reg_radius, g_image, g_reg, g_weights, g_reg_q):
+    """:func:`dt_integral_bwd` for gradients w.r.t. all three outputs of raw2outputs (density_temperature.py:267-271): also
+    ``g_weights`` / ``g_reg_q`` (N,S) (either may be None) -> (g_raw (N,S,2), g_log_abs (7,), g_vol_c (1,), absmax), the two
+    scalar-head gradients adjacent in one buffer as there."""
+    n, s = z_vals.shape
+    dev = z_vals.device
+    w = wavelengths.shape[1]
+    raw = _dev(raw, 'raw', (n, s, 2)); z_vals = _dev(z_vals, 'z_vals', (n, s))
+    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3))
+    wavelengths = _dev(wavelengths.to(torch.float32), 'wavelengths', (n, w))
+    log_abs = _dev(log_abs.detach(), 'log_abs', (7,)); vol_c = _dev(vol_c.detach().reshape(1), 'vol_c', (1,))
+    g_image = _dev(g_image, 'g_image', (n, w))
+    g_reg = None if g_reg is None else _dev(g_reg, 'g_reg', (n, s))
+    g_weights = None if g_weights is None else _dev(g_weights, 'g_weights', (n, s))
+    g_reg_q = None if g_reg_q is None else _dev(g_reg_q, 'g_reg_q', (n, s))
+    f32 = dict(dtype=torch.float32, device=dev)
+    g_raw = torch.empty(n, s, 2, **f32)
+    small = torch.empty(9, **f32)
+    g_la, g_vc, absmax = small[:7], small[7:8], small[8:9].view(torch.int32)
+    _l.call(dev, 'sunerf_dt_integral_bwd_full', _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(wavelengths), w,
+            _ptr(table_logt), _ptr(table_resp), _ptr(log_abs), _ptr(vol_c), float(base_log_density),
+            float(base_log_temperature), float(pixel_intensity_factor), float(reg_radius), n, s, _ptr(g_image),
+            _ptr(g_reg), _ptr(g_weights), _ptr(g_reg_q), _ptr(g_raw), _ptr(g_la), _ptr(g_vc), _ptr(absmax), _stream(dev))
+    return g_raw, g_la, g_vc, absmax
+
+
+def simple_star_field_dev(rays_o, rays_d, z_vals, params, t_photosphere: float):
+    """:func:`simple_star_field` with the stellar parameters read on the device: ``params`` (4,) fp32 = (Rs, h0, T0, rho_0),
+    the order of ``SimpleStar.stellar_parameters`` -> raw (N, S, 2) = (ln rho, log10 T), bit-identical to the host-float form."""
+    n, s = z_vals.shape
+    dev = z_vals.device
+    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3)); z_vals = _dev(z_vals, 'z_vals', (n, s))
+    params = _dev(params.detach(), 'params', (4,))
+    raw = torch.empty(n, s, 2, dtype=torch.float32, device=dev)
+    _l.call(dev, 'sunerf_simple_star_field_dev', _ptr(rays_o), _ptr(rays_d), _ptr(z_vals), n, s, _ptr(params),
+            float(t_photosphere), _ptr(raw), _stream(dev))
+    return raw
+
+
+def simple_star_bwd(rays_o, rays_d, z_vals, params, t_photosphere: float, g_raw, out: Optional[torch.Tensor] = None):
+    """d loss / d (Rs, h0, T0, rho_0) of :func:`simple_star_field_dev` given ``g_raw`` (N, S, 2) -> (4,) fp32.  ``out``: a (4,)
+    contiguous fp32 tensor (e.g. the parameters' slice of a flat gradient buffer) the result is ADDED to; returned."""
+    n, s = z_vals.shape
+    dev = z_vals.device
+    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3)); z_vals = _dev(z_vals, 'z_vals', (n, s))
+    params = _dev(params.detach(), 'params', (4,))
+    g_raw = _dev(g_raw, 'g_raw', (n, s, 2))
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+    elif not out.is_contiguous() or out.shape != (4,) or out.dtype != torch.float32 or out.device != dev:
+        raise ValueError('out must be a contiguous (4,) float32 tensor on the device of the rays')
+    ws = torch.empty(_l.load().sunerf_simple_star_bwd_workspace_bytes(), dtype=torch.uint8, device=dev)
+    _l.call(dev, 'sunerf_simple_star_bwd', _ptr(rays_o), _ptr(rays_d), _ptr(z_vals), n, s, _ptr(params), float(t_photosphere),
+            _ptr(g_raw), _ptr(ws), ws.numel(), _ptr(out), 1 if accumulate else 0, _stream(dev))
+    return out

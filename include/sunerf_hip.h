@@ -266,6 +266,20 @@ int sunerf_dt_integral_bwd(const float* raw, const float* z_vals, const float* r
                            const float* g_image, const float* g_reg, float* g_raw, float* g_log_abs, float* g_vol_c,
                            void* g_absmax, void* stream);
 
+/* sunerf_dt_integral_bwd for gradients w.r.t. all three outputs of raw2outputs (density_temperature.py:267-271), what
+ * the reference's autograd gives a subclass that overrides a hook (its loss reaches `weights` through height_map and
+ * `regularizing_quantity` through its own regularization, base_tracing.py:99-110):
+ *   g_weights (N,S) or NULL : d loss / d weights,  weights = relu(inf0) / (sum_s relu(inf0) + 1e-10)
+ *   g_reg_q (N,S) or NULL   : d loss / d reg_q,    reg_q = relu(inf0)
+ * both added to g_raw[..., 0] where inf0 = raw0 + base_log_density > 0.  Everything else as sunerf_dt_integral_bwd
+ * (which stays the entry point of the fused path: it has no such outputs). */
+int sunerf_dt_integral_bwd_full(const float* raw, const float* z_vals, const float* rays_o, const float* rays_d,
+                                const float* wavelengths, int n_wavelengths, const float* table_logt, const float* table_resp,
+                                const float* log_abs, const float* vol_c, float base_log_density, float base_log_temperature,
+                                float pixel_intensity_factor, float reg_radius, int64_t n_rays, int n_samples,
+                                const float* g_image, const float* g_reg, const float* g_weights, const float* g_reg_q,
+                                float* g_raw, float* g_log_abs, float* g_vol_c, void* g_absmax, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Input side of the path: observer rays on the device.
  * Replaces get_rays, sunerf/data/ray_sampling.py:7-36, and the host-side tiling / H2D copy of the rays and of the
@@ -332,6 +346,26 @@ int sunerf_clip_adam_step(float* params, float* grads, float* exp_avg, float* ex
  * ---------------------------------------------------------------------------------------------------------- */
 int sunerf_simple_star_field(const float* rays_o, const float* rays_d, const float* z_vals, int64_t n_rays, int n_samples,
                              float rho_0, float h0, float T0, float Rs, float t_photosphere, float* raw, void* stream);
+
+/* Trainable SimpleStar: the stellar parameters as the reference's nn.ParameterDict `stellar_parameters` holds them
+ * (stellar_model.py:5-52), in its order, so that the four scalars of an optimiser's flat buffer ARE the array:
+ *   params [4] DEVICE fp32 = (Rs [solar radii], h0 [solar radii], T0 [K], rho_0 [cm^-3])
+ *
+ * sunerf_simple_star_field_dev: sunerf_simple_star_field with the parameters read on the device (no host copy after an
+ *   optimiser step); the same fp32 arithmetic, bit for bit.
+ * sunerf_simple_star_bwd: the gradient of a loss w.r.t. the four parameters, given
+ *   g_raw [N, S, 2] = d loss / d (ln rho, log10 T) at o + d z  ->  g_params [4] in the order of `params`, overwritten
+ *   (accumulate = 0) or added to (accumulate != 0, e.g. the parameters' slots of a flat gradient buffer).
+ *   The reference's masks (radius <= 1, > 1, <= Rs, > Rs) carry no gradient; a NaN radius (missed-sphere rays of
+ *   SphericalSampler) contributes exactly 0.  Deterministic: per-workgroup fp64 partials in `workspace`
+ *   (sunerf_simple_star_bwd_workspace_bytes()), summed in a fixed order by a second launch; no atomics.
+ *   No gradient w.r.t. rays, z or t_photosphere (a plain float in the reference). */
+int sunerf_simple_star_field_dev(const float* rays_o, const float* rays_d, const float* z_vals, int64_t n_rays, int n_samples,
+                                 const float* params, float t_photosphere, float* raw, void* stream);
+size_t sunerf_simple_star_bwd_workspace_bytes(void);
+int sunerf_simple_star_bwd(const float* rays_o, const float* rays_d, const float* z_vals, int64_t n_rays, int n_samples,
+                           const float* params, float t_photosphere, const float* g_raw, void* workspace,
+                           size_t workspace_bytes, float* g_params, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Hierarchical (inverse-CDF) resampling + merge.
