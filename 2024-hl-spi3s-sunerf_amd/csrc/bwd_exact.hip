@@ -100,10 +100,12 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs a) {
 }
 
 // query points -> the 84 encoder features of PositionalEncoding.forward (model.py:123-132): [x, sin(x 2^k / 2) k-major, cos(...)]
+// for samples [first, first + count) of the batch (row i of `enc` is sample first + i)
 __global__ void encode_kernel(const float* rays_o, const float* rays_d, const float* times, const float* z_vals,
-                              const float* points, long n_rays, int S, float* enc /* [n_rays * S][84] */) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_rays * S) return;
+                              const float* points, long first, long count, int S, float* enc /* [count][84] */) {
+  const long local = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (local >= count) return;
+  const long i = first + local;
   float v[4];
   if (points) {
     for (int c = 0; c < 4; ++c) v[c] = points[i * 4 + c];
@@ -114,7 +116,7 @@ __global__ void encode_kernel(const float* rays_o, const float* rays_d, const fl
     for (int c = 0; c < 3; ++c) v[c] = rays_o[ray * 3 + c] + rays_d[ray * 3 + c] * z;
     v[3] = times[ray];
   }
-  float* e = enc + i * SUNERF_ENC_DIM;
+  float* e = enc + local * SUNERF_ENC_DIM;
   for (int c = 0; c < 4; ++c) e[c] = v[c];
   for (int k = 0; k < 10; ++k) {
     const float f = k == 0 ? 0.5f : (float)(1 << (k - 1));      // 2^k / scale_factor, exact
@@ -226,7 +228,7 @@ extern "C" int sunerf_mlp_backward_exact(const float* const* weights_host, const
 
   SUNERF_CLEAR_ERROR();
   hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, rays_o, rays_d, times, z_vals, points,
-                     (long)n_rays, n_samples, enc);
+                     0L, (long)N, n_samples, enc);
   SUNERF_CHECK_LAUNCH();
   // forward, fp32: H_l = sin(X W_l^T + b_l), cos kept for the backward
   for (int l = 0; l < n_act; ++l) {
@@ -266,5 +268,348 @@ extern "C" int sunerf_mlp_backward_exact(const float* const* weights_host, const
     if ((rc = launch_gemm<EPI_MULC>(d, 1, st))) return rc;
     dz = dzb[flip]; dz_cols = D; flip ^= 1;
   }
+  return 0;
+}
+
+// ---- the same backward at ANY batch size: samples in chunks, LDS-tiled fp32 GEMMs, fp64 cross-chunk sums ---------------------------
+// The layer-major kernel above keeps every layer's H and cos for the whole batch (~19 KB per sample at 8 x 256) and gives each wave
+// one 32 x 32 tile read straight from L2.  Here the samples run in chunks of chunk_samples(D): per chunk the encoder features, the
+// fp32 forward (H and cos of that chunk only), and the backward of the chunk -- data gradients chained layer by layer, every weight
+// gradient as split-K partial slabs -- whose partials are added into fp64 accumulators [layer][out][in] / [layer][out] in a fixed
+// order (slices, then row blocks, then chunks: no atomics, two runs are bit-identical).  One last launch casts them to fp32 and
+// writes or adds them to the gradient buffers.  The workspace depends on (d_filter, n_linear) only.
+//
+// GEMM: 128 x 128 output block of 256 threads, 2 x 2 waves of 64 x 64 (4 accumulators of v_mfma_f32_32x32x2_f32 each), K in
+// steps of 16 staged through LDS; the next step's operands are loaded into registers while the current one is multiplied.  The
+// k order of every fp32 chain is the plain 0, 1, 2, ... of the kernel above (zero-filled tails add exact zeros): the forward and
+// data-gradient GEMMs are bit-identical to it; weight gradients differ by the slicing of their long K only.
+namespace {
+
+constexpr int TB_M = 128, TB_N = 128, TB_K = 16;
+constexpr int KC_LD = TB_K + 1;                 // LDS [row][k] of an operand contiguous in k (odd stride: row-parallel reads)
+constexpr int RC_LD = TB_M + 32;                // LDS [k][row] of an operand contiguous in its row index (k + 1 lands 32 banks on)
+constexpr int TILE_FLOATS = TB_K * RC_LD;       // >= TB_M * KC_LD
+constexpr int WGRAD_BLOCKS = 512;               // split-K target of the weight-gradient GEMMs: blocks per launch (2 per CU)
+constexpr int COLSUM_ROWS = 256;                // rows per block of the bias column sums
+
+__host__ __device__ constexpr int chunk_samples(int D) { return D > 256 ? 16384 : 32768; }
+
+struct TiledArgs {
+  const float* A; long lda;     // A_KC: A(m, k) = A[m * lda + k], else A[k * lda + m]
+  const float* B; long ldb;     // B_KC: B(k, n) = B[n * ldb + k], else B[k * ldb + n]
+  int M, N, K;
+  int k_per;                    // EPI_PART: the K range of one slice (blockIdx.z), a multiple of TB_K
+  const float* bias;            // EPI_SINCOS: [N]
+  float* out0; float* out1; long ldo;
+  const float* mul;             // EPI_MULC: [M][ldo]
+};
+
+// one operand's 128 x 16 step: 8 elements per thread, consecutive lanes on the contiguous index
+template <bool KC>
+__device__ __forceinline__ void tile_load(const float* X, long ld, int rows, int row0, int k0, int kend, float* v) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int row = KC ? (t >> 4) + 16 * j : (t & 127);
+    const int k = KC ? (t & 15) : (t >> 7) + 2 * j;
+    const int gr = row0 + row, gk = k0 + k;
+    v[j] = (gr < rows && gk < kend) ? (KC ? X[(long)gr * ld + gk] : X[(long)gk * ld + gr]) : 0.f;
+  }
+}
+
+template <bool KC>
+__device__ __forceinline__ void tile_store(float* s, const float* v) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int row = KC ? (t >> 4) + 16 * j : (t & 127);
+    const int k = KC ? (t & 15) : (t >> 7) + 2 * j;
+    s[KC ? row * KC_LD + k : k * RC_LD + row] = v[j];
+  }
+}
+
+template <bool KC>
+__device__ __forceinline__ float tile_at(const float* s, int row, int k) { return s[KC ? row * KC_LD + k : k * RC_LD + row]; }
+
+// out-of-line: 64 inlined copies of the accurate sinf / cosf keep the epilogue loop from unrolling (accumulators in scratch)
+__device__ __noinline__ float2 sin_cos(float z) { return make_float2(sinf(z), cosf(z)); }
+
+template <bool A_KC, bool B_KC, int EPI>
+__global__ __launch_bounds__(256) void gemm_tiled_kernel(TiledArgs a) {
+  __shared__ float sa[TILE_FLOATS], sb[TILE_FLOATS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+  const int m0 = (int)blockIdx.y * TB_M, n0 = (int)blockIdx.x * TB_N;
+  int k0 = 0, k1 = a.K;
+  if (EPI == EPI_PART) {
+    k0 = (int)blockIdx.z * a.k_per;
+    k1 = k0 + a.k_per < a.K ? k0 + a.k_per : a.K;
+  }
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x16{0};
+  float va[8], vb[8];
+  if (k0 < k1) {
+    tile_load<A_KC>(a.A, a.lda, a.M, m0, k0, k1, va);
+    tile_load<B_KC>(a.B, a.ldb, a.N, n0, k0, k1, vb);
+    tile_store<A_KC>(sa, va);
+    tile_store<B_KC>(sb, vb);
+  }
+  __syncthreads();
+  for (int k = k0; k < k1; k += TB_K) {
+    const bool more = k + TB_K < k1;
+    if (more) {
+      tile_load<A_KC>(a.A, a.lda, a.M, m0, k + TB_K, k1, va);
+      tile_load<B_KC>(a.B, a.ldb, a.N, n0, k + TB_K, k1, vb);
+    }
+#pragma unroll
+    for (int kk = 0; kk < TB_K; kk += 2) {
+      float fa[2], fb[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        fa[i] = tile_at<A_KC>(sa, wm + 32 * i + r, kk + h);
+        fb[i] = tile_at<B_KC>(sb, wn + 32 * i + r, kk + h);
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+    if (more) {
+      tile_store<A_KC>(sa, va);
+      tile_store<B_KC>(sb, vb);
+      __syncthreads();
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int n = n0 + wn + 32 * j + r;
+    if (n >= a.N) continue;
+    const float bn = EPI == EPI_SINCOS ? a.bias[n] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int g = 0; g < 16; ++g) {
+        const int row = m0 + wm + 32 * i + acc_row(g, h);
+        if (row >= a.M) continue;
+        const float v = acc[i][j][g];
+        const long o = (long)row * a.ldo + n;
+        if (EPI == EPI_SINCOS) {
+          const float2 sc = sin_cos(v + bn);
+          a.out0[o] = sc.x;
+          a.out1[o] = sc.y;
+        } else if (EPI == EPI_MULC) {
+          a.out0[o] = v * a.mul[o];
+        } else {
+          a.out0[(long)blockIdx.z * a.M * a.ldo + o] = v;
+        }
+      }
+    }
+  }
+}
+
+// bias gradient, first half: fp64 sums of COLSUM_ROWS rows of dz per block -> part[row block][col]
+__global__ __launch_bounds__(256) void colsum_part_kernel(const float* dz, int rows, int cols, double* part) {
+  __shared__ double s[4][64];
+  const int c = (int)blockIdx.x * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
+  const int r0 = (int)blockIdx.y * COLSUM_ROWS;
+  const int r1 = r0 + COLSUM_ROWS < rows ? r0 + COLSUM_ROWS : rows;
+  double t = 0.0;
+  if (c < cols)
+    for (int i = r0 + q; i < r1; i += 4) t += (double)dz[(long)i * cols + c];
+  s[q][threadIdx.x & 63] = t;
+  __syncthreads();
+  if (q == 0 && c < cols) part[(long)blockIdx.y * cols + c] = (s[0][threadIdx.x] + s[1][threadIdx.x]) + (s[2][threadIdx.x] + s[3][threadIdx.x]);
+}
+
+// one layer of one chunk into the fp64 accumulators: acc_w[i] += sum over slices of wpart[slice][i] (i < count),
+// acc_b[c] += sum over row blocks of bpart[block][c]; both in slice / block order
+__global__ __launch_bounds__(256) void accumulate_layer_kernel(const float* wpart, int slices, long count, double* acc_w,
+                                                               const double* bpart, int blocks, int cols, double* acc_b) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) {
+    double s = 0.0;
+    for (int k = 0; k < slices; ++k) s += (double)wpart[(long)k * count + i];
+    acc_w[i] += s;
+  } else if (i < count + cols) {
+    const int c = (int)(i - count);
+    double s = 0.0;
+    for (int k = 0; k < blocks; ++k) s += bpart[(long)k * cols + c];
+    acc_b[c] += s;
+  }
+}
+
+struct CastArgs {
+  float* gw[SUNERF_MAX_LAYERS]; float* gb[SUNERF_MAX_LAYERS];
+  long w_off[SUNERF_MAX_LAYERS], b_off[SUNERF_MAX_LAYERS];     // offsets into the fp64 accumulators
+  long w_count[SUNERF_MAX_LAYERS]; int b_count[SUNERF_MAX_LAYERS];
+  const double* acc; int accumulate;
+};
+
+// the fp64 sums -> the fp32 gradient buffers (layer = blockIdx.y)
+__global__ __launch_bounds__(256) void cast_grads_kernel(CastArgs a) {
+  const int l = blockIdx.y;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < a.w_count[l]) {
+    const float v = (float)a.acc[a.w_off[l] + i];
+    a.gw[l][i] = a.accumulate ? a.gw[l][i] + v : v;
+  } else if (i < a.w_count[l] + a.b_count[l]) {
+    const long c = i - a.w_count[l];
+    const float v = (float)a.acc[a.b_off[l] + c];
+    a.gb[l][c] = a.accumulate ? a.gb[l][c] + v : v;
+  }
+}
+
+constexpr int CHUNKED_MAX_OUT = 2;      // d_out of the workspace query (NeRF: 1 or 2)
+
+// weight-gradient split of one layer: slices of a multiple of TB_K rows, about WGRAD_BLOCKS blocks in all
+int wgrad_slices(int M, int N, int rows) {
+  const int tiles = ((M + TB_M - 1) / TB_M) * ((N + TB_N - 1) / TB_N);
+  int s = WGRAD_BLOCKS / tiles;
+  const int steps = (rows + TB_K - 1) / TB_K;
+  s = s < 1 ? 1 : (s > steps ? steps : s);
+  return s;
+}
+int wgrad_k_per(int rows, int slices) { return ((rows + slices - 1) / slices + TB_K - 1) / TB_K * TB_K; }
+
+struct ChunkedLayout {
+  size_t enc, act, dz, wpart, bpart, acc, total;     // byte offsets; act: [layer][H | cos][C][D], dz: [2][C][D]
+  size_t per;                                        // floats per [C][D] tensor
+  int C;
+  ChunkedLayout(int D, int n_linear) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    C = chunk_samples(D);
+    per = (size_t)C * D;
+    size_t wp = 0;                                   // largest partial slab of any layer (d_out <= CHUNKED_MAX_OUT)
+    for (int i = 0; i < n_linear; ++i) {
+      const int M = i == n_linear - 1 ? CHUNKED_MAX_OUT : D, N = i == 0 ? SUNERF_ENC_DIM : D;
+      const size_t v = (size_t)wgrad_slices(M, N, C) * M * N;
+      wp = v > wp ? v : wp;
+    }
+    size_t accs = 0;
+    for (int i = 0; i < n_linear; ++i) {
+      const int M = i == n_linear - 1 ? CHUNKED_MAX_OUT : D, N = i == 0 ? SUNERF_ENC_DIM : D;
+      accs += (size_t)M * N + M;
+    }
+    size_t off = 0;
+    enc = off; off += up((size_t)C * SUNERF_ENC_DIM * sizeof(float));
+    act = off; off += up((size_t)(n_linear - 1) * 2 * per * sizeof(float));
+    dz = off; off += up(2 * per * sizeof(float));
+    wpart = off; off += up(wp * sizeof(float));
+    bpart = off; off += up((size_t)((C + COLSUM_ROWS - 1) / COLSUM_ROWS) * D * sizeof(double));
+    acc = off; off += up(accs * sizeof(double));
+    total = off;
+  }
+};
+
+template <bool A_KC, bool B_KC, int EPI>
+int launch_tiled(const TiledArgs& a, int slices, hipStream_t st) {
+  SUNERF_CLEAR_ERROR();
+  hipLaunchKernelGGL((gemm_tiled_kernel<A_KC, B_KC, EPI>), dim3((unsigned)((a.N + TB_N - 1) / TB_N), (unsigned)((a.M + TB_M - 1) / TB_M),
+                     (unsigned)slices), dim3(256), 0, st, a);
+  SUNERF_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" size_t sunerf_mlp_backward_exact_chunked_workspace_bytes(int d_filter, int n_linear) {
+  if (d_filter < 1 || d_filter > 512 || n_linear < 2 || n_linear > SUNERF_MAX_LAYERS) return 0;
+  return ChunkedLayout(d_filter, n_linear).total;
+}
+
+extern "C" int sunerf_mlp_backward_exact_chunked(const float* const* weights_host, const float* const* biases_host, int n_linear,
+                                                 int d_filter, int d_out, const float* rays_o, const float* rays_d,
+                                                 const float* times, const float* z_vals, const float* points, int64_t n_rays,
+                                                 int n_samples, const float* g_raw, void* workspace, size_t workspace_bytes,
+                                                 float* const* grad_weights_host, float* const* grad_biases_host, int accumulate,
+                                                 void* stream) {
+  if (!weights_host || !biases_host || !grad_weights_host || !grad_biases_host || !g_raw || !workspace) return SUNERF_E_BADARG;
+  if (n_rays <= 0 || n_samples < 1 || d_filter < 1 || d_out < 1) return SUNERF_E_BADARG;
+  if (n_linear < 2 || n_linear > SUNERF_MAX_LAYERS || d_filter > 512 || d_out > CHUNKED_MAX_OUT) return SUNERF_E_UNSUPPORTED;
+  if (!points && (!rays_o || !rays_d || !times || !z_vals)) return SUNERF_E_BADARG;
+  for (int i = 0; i < n_linear; ++i)
+    if (!weights_host[i] || !biases_host[i] || !grad_weights_host[i] || !grad_biases_host[i]) return SUNERF_E_BADARG;
+  if (n_rays > ((int64_t)1 << 40) / n_samples) return SUNERF_E_UNSUPPORTED;      // 64-bit sample indices throughout
+  const int64_t N = n_rays * n_samples;
+  const int D = d_filter, n_act = n_linear - 1;
+  const ChunkedLayout L(D, n_linear);
+  if (workspace_bytes < L.total) return SUNERF_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  float* enc = (float*)(ws + L.enc);
+  auto H = [&](int l) { return (float*)(ws + L.act) + (size_t)(2 * l) * L.per; };
+  auto Cs = [&](int l) { return (float*)(ws + L.act) + (size_t)(2 * l + 1) * L.per; };
+  float* dzb[2] = {(float*)(ws + L.dz), (float*)(ws + L.dz) + L.per};
+  float* wpart = (float*)(ws + L.wpart);
+  double* bpart = (double*)(ws + L.bpart);
+  double* acc = (double*)(ws + L.acc);
+  CastArgs ca = {};
+  long off = 0, max_count = 0;
+  for (int i = 0; i < n_linear; ++i) {
+    const int M = i == n_linear - 1 ? d_out : D, K = i == 0 ? SUNERF_ENC_DIM : D;
+    ca.gw[i] = grad_weights_host[i]; ca.gb[i] = grad_biases_host[i];
+    ca.w_off[i] = off; ca.w_count[i] = (long)M * K; off += (long)M * K;
+    ca.b_off[i] = off; ca.b_count[i] = M; off += M;
+    max_count = (long)M * K + M > max_count ? (long)M * K + M : max_count;
+  }
+  ca.acc = acc; ca.accumulate = accumulate;
+  int rc;
+  SUNERF_CLEAR_ERROR();
+  if (hipMemsetAsync(acc, 0, (size_t)off * sizeof(double), st) != hipSuccess) return (int)hipGetLastError();
+
+  for (int64_t c0 = 0; c0 < N; c0 += L.C) {
+    const int Cn = (int)(N - c0 < L.C ? N - c0 : L.C);
+    hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((Cn + 255) / 256)), dim3(256), 0, st, rays_o, rays_d, times, z_vals, points,
+                       (long)c0, (long)Cn, n_samples, enc);
+    SUNERF_CHECK_LAUNCH();
+    // forward, fp32: H_l = sin(X W_l^T + b_l), cos kept for the data gradients
+    for (int l = 0; l < n_act; ++l) {
+      const int K = l == 0 ? SUNERF_ENC_DIM : D;
+      TiledArgs a = {};
+      a.A = l == 0 ? enc : H(l - 1); a.lda = K;
+      a.B = weights_host[l]; a.ldb = K;
+      a.M = Cn; a.N = D; a.K = K; a.bias = biases_host[l];
+      a.out0 = H(l); a.out1 = Cs(l); a.ldo = D;
+      if ((rc = launch_tiled<true, true, EPI_SINCOS>(a, 1, st))) return rc;
+    }
+    const float* dz = g_raw + c0 * d_out;
+    int dz_cols = d_out, flip = 0;
+    for (int i = n_linear - 1; i >= 0; --i) {
+      const int cols = i == 0 ? SUNERF_ENC_DIM : D;         // fan-in of layer i
+      const float* X = i == 0 ? enc : H(i - 1);
+      // dW_i[o][j] partials = sum over a slice of the chunk's samples of dZ_i[s][o] X[s][j]
+      const int slices = wgrad_slices(dz_cols, cols, Cn);
+      TiledArgs w = {};
+      w.A = dz; w.lda = dz_cols;
+      w.B = X; w.ldb = cols;
+      w.M = dz_cols; w.N = cols; w.K = Cn; w.k_per = wgrad_k_per(Cn, slices);
+      w.out0 = wpart; w.ldo = cols;
+      if ((rc = launch_tiled<false, false, EPI_PART>(w, slices, st))) return rc;
+      const int blocks = (Cn + COLSUM_ROWS - 1) / COLSUM_ROWS;
+      hipLaunchKernelGGL(colsum_part_kernel, dim3((unsigned)((dz_cols + 63) / 64), (unsigned)blocks), dim3(256), 0, st, dz, Cn, dz_cols,
+                         bpart);
+      SUNERF_CHECK_LAUNCH();
+      const long count = (long)dz_cols * cols;
+      hipLaunchKernelGGL(accumulate_layer_kernel, dim3((unsigned)((count + dz_cols + 255) / 256)), dim3(256), 0, st, wpart, slices,
+                         count, acc + ca.w_off[i], bpart, blocks, dz_cols, acc + ca.b_off[i]);
+      SUNERF_CHECK_LAUNCH();
+      if (i == 0) break;
+      // dZ_{i-1}[s][j] = (sum_o dZ_i[s][o] W_i[o][j]) cos(Z_{i-1})[s][j]
+      TiledArgs d = {};
+      d.A = dz; d.lda = dz_cols;
+      d.B = weights_host[i]; d.ldb = D;
+      d.M = Cn; d.N = D; d.K = dz_cols;
+      d.out0 = dzb[flip]; d.ldo = D; d.mul = Cs(i - 1);
+      if ((rc = launch_tiled<true, false, EPI_MULC>(d, 1, st))) return rc;
+      dz = dzb[flip]; dz_cols = D; flip ^= 1;
+    }
+  }
+  hipLaunchKernelGGL(cast_grads_kernel, dim3((unsigned)((max_count + 255) / 256), (unsigned)n_linear), dim3(256), 0, st, ca);
+  SUNERF_CHECK_LAUNCH();
   return 0;
 }

@@ -67,6 +67,25 @@ def default_precision(d_filter: int) -> int:
     return names[mode]
 
 
+BACKWARD_PRECISIONS = ('default', 'exact')
+
+
+def backward_precision() -> str:
+    """Arithmetic of the MLP backward: ``SUNERF_BACKWARD_PRECISION`` = ``default`` (unset: the fp16 kernels, the fp32 one for
+    batches of at most ``exact_backward_limit()`` samples) or ``exact`` (every batch with query points in fp32, whatever its size:
+    ``sunerf_mlp_backward_exact_chunked``; the training forwards then write no activation stash).  With
+    ``SUNERF_FORWARD_PRECISION=exact`` this is fp32-class training end to end."""
+    mode = os.environ.get('SUNERF_BACKWARD_PRECISION', 'default').strip().lower() or 'default'
+    if mode not in BACKWARD_PRECISIONS:
+        raise ValueError(f"SUNERF_BACKWARD_PRECISION must be one of {list(BACKWARD_PRECISIONS)}, not {mode!r}")
+    return mode
+
+
+def _stash_wanted(training: bool) -> bool:
+    """A training forward writes the activation stash unless the backward will recompute the activations in fp32."""
+    return training and backward_precision() != 'exact'
+
+
 _workspaces = {}                        # (device, stream) -> scratch of the d_filter = 512 render kernel
 STASH_FP16, STASH_PHASE = 0, 1          # include/sunerf_hip.h: SUNERF_STASH_*
 
@@ -339,7 +358,8 @@ def emission_render_fwd(packed: PackedMLP, rays_o, rays_d, times, z_vals, reg_ra
                         probe_sensitivity: float = 1.0):
     """One fused render pass.  Returns dict(image (N,1), weights (N,S), absorption (N,S)[, raw (N,S,2)]
     [, height_map (N,), absorption_map (N,), regularization (N,S)][, stash]).  ``training=True`` also writes the
-    activation stash needed by :func:`emission_render_bwd` (and implies ``want_raw``)."""
+    activation stash needed by :func:`emission_render_bwd` (and implies ``want_raw``); under
+    ``SUNERF_BACKWARD_PRECISION=exact`` the backward does not read one and ``stash`` is None."""
     lib = _l.load()
     n, s = z_vals.shape
     dev = z_vals.device
@@ -370,7 +390,7 @@ def emission_render_fwd(packed: PackedMLP, rays_o, rays_d, times, z_vals, reg_ra
             ws = _workspaces[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     raw = torch.empty(n, s, 2, **f32) if want_raw else None
     stash, fmt = None, STASH_FP16
-    if training:
+    if _stash_wanted(training):
         fmt = training_stash_format(packed, n, s)
         stash = torch.empty(lib.sunerf_act_stash_bytes(n, s, packed.d_filter, packed.n_linear, fmt), dtype=torch.uint8,
                             device=dev)
@@ -393,7 +413,7 @@ def emission_render_fwd(packed: PackedMLP, rays_o, rays_d, times, z_vals, reg_ra
 def mlp_points_fwd(packed: PackedMLP, points: torch.Tensor, training: bool = False):
     """NeRF.forward on free-standing points (M, 4) -> dict(raw (M, 2)[, stash, n_padded]).  The points are padded to whole
     32-point chunks; ``training=True`` also writes the activation stash :func:`mlp_backward` needs (with ``g_raw`` of shape
-    (n_padded / 32, 32, 2))."""
+    (n_padded / 32, 32, 2)); ``stash`` is None under ``SUNERF_BACKWARD_PRECISION=exact``."""
     lib = _l.load()
     m = points.shape[0]
     dev = points.device
@@ -424,7 +444,7 @@ def mlp_points_fwd(packed: PackedMLP, points: torch.Tensor, training: bool = Fal
             ws = _workspaces[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     raw = torch.empty(m_pad, 2, dtype=torch.float32, device=dev)
     stash, fmt = None, STASH_FP16
-    if training:
+    if _stash_wanted(training):
         fmt = training_stash_format(packed, m_pad // 32, 32)
         stash = torch.empty(lib.sunerf_act_stash_bytes(m_pad // 32, 32, packed.d_filter, packed.n_linear, fmt), dtype=torch.uint8, device=dev)
     _l.call(dev, 'sunerf_mlp_points_fwd', _ptr(weights_image), packed.d_filter, packed.n_linear, precision, _ptr(points),
@@ -488,8 +508,11 @@ def emission_render_bwd(packed: PackedMLP, rays_o, rays_d, z_vals, raw, stash, g
     """Backward of one render pass: fills (or accumulates into) ``grad_weights[i]`` / ``grad_biases[i]`` (nn.Linear
     layouts) from the gradient w.r.t. the 'image' output (N,) or (N,1) and the 'regularization' output
     (``g_reg`` (N,S) tensor or None + the constant ``g_reg_const``).  ``times`` (N,): the forward's time coordinate -- with it
-    the small-batch fp32 backward can recompute the activations (``mlp_backward(query=...)``); without it the fp16 kernels run."""
+    the small-batch fp32 backward can recompute the activations (``mlp_backward(query=...)``); without it the fp16 kernels run.
+    Under ``SUNERF_BACKWARD_PRECISION=exact`` ``times`` is required."""
     lib = _l.load()
+    if times is None and backward_precision() == 'exact':
+        raise _l.SunerfHipError(_NO_QUERY)
     n, s = z_vals.shape
     dev = z_vals.device
     rays_o = _dev(rays_o, 'rays_o', (n, 3))
@@ -732,16 +755,23 @@ def _use_exact_backward(n_samples: int, query) -> bool:
     return n_samples <= exact_backward_limit()
 
 
-_exact_ws = {}          # (device, stream) -> workspace of the fp32 backward
+_exact_ws = {}          # (device, stream) -> workspace of the fp32 backward (either kernel)
+_NO_QUERY = ('SUNERF_BACKWARD_PRECISION=exact: the fp32 backward recomputes the activations from the query points, and this '
+             'backward was given none (pass times= / query=); the fp16 kernels are not run in its place')
 
 
-def _mlp_backward_exact(packed: PackedMLP, g_raw, query, grad_weights, grad_biases, accumulate: bool):
+def _mlp_backward_exact(packed: PackedMLP, g_raw, query, grad_weights, grad_biases, accumulate: bool, chunked: bool = False):
+    """``chunked``: the any-size kernel (sunerf_mlp_backward_exact_chunked, workspace independent of the batch), else the
+    small-batch one."""
     lib = _l.load()
     dev = g_raw.device
     n, s = g_raw.shape[0], g_raw.shape[1]
     ws_, bs_ = packed._keepalive          # fp32 parameters of the kernel shapes (the padded copies for padded models)
     nl = packed.n_linear
-    nbytes = lib.sunerf_mlp_backward_exact_workspace_bytes(n * s, packed.d_filter, nl)
+    if chunked:
+        nbytes = lib.sunerf_mlp_backward_exact_chunked_workspace_bytes(packed.d_filter, nl)
+    else:
+        nbytes = lib.sunerf_mlp_backward_exact_workspace_bytes(n * s, packed.d_filter, nl)
     key = (dev, torch.cuda.current_stream(dev).cuda_stream)
     ws = _exact_ws.get(key)
     if ws is None or ws.numel() < nbytes:
@@ -760,8 +790,8 @@ def _mlp_backward_exact(packed: PackedMLP, g_raw, query, grad_weights, grad_bias
         args = (None, None, None, None, _ptr(pts))
     g = g_raw if g_raw.shape[-1] == packed.d_out else g_raw[..., :packed.d_out]       # (N, S, d_out), densely packed
     g = _dev(g, 'g_raw')
-    _l.call(dev, 'sunerf_mlp_backward_exact', W, B, nl, packed.d_filter, packed.d_out, *args, n, s, _ptr(g),
-            _ptr(ws), nbytes, GW, GB, int(accumulate), _stream(dev))
+    _l.call(dev, 'sunerf_mlp_backward_exact_chunked' if chunked else 'sunerf_mlp_backward_exact', W, B, nl, packed.d_filter,
+            packed.d_out, *args, n, s, _ptr(g), _ptr(ws), nbytes, GW, GB, int(accumulate), _stream(dev))
 
 
 def mlp_backward(packed: PackedMLP, g_raw, absmax, stash, grad_weights: Sequence[torch.Tensor],
@@ -769,13 +799,17 @@ def mlp_backward(packed: PackedMLP, g_raw, absmax, stash, grad_weights: Sequence
     """dgrad + wgrad of the sine MLP from the gradient w.r.t. its raw output (N,S,2): fills / accumulates the nn.Linear
     gradients.  ``absmax``: 4-byte device scalar with the bit pattern of max |g_raw| (written by the integral backward).
     ``query``: what the forward was evaluated on -- ``('rays', rays_o, rays_d, times, z_vals)`` or ``('points', points (N*S, 4))``;
-    given it, batches of at most ``exact_backward_limit()`` samples take the fp32 backward (csrc/bwd_exact.hip)."""
+    given it, batches of at most ``exact_backward_limit()`` samples take the fp32 backward (csrc/bwd_exact.hip), and under
+    ``SUNERF_BACKWARD_PRECISION=exact`` every batch does (the any-size kernel; no stash is read, ``stash`` may be None)."""
     lib = _l.load()
     n, s = g_raw.shape[0], g_raw.shape[1]
     dev = g_raw.device
     D, nl = packed.d_filter, packed.n_linear
     stream = _stream(dev)
-    exact = _use_exact_backward(n * s, query)
+    exact_any = backward_precision() == 'exact'
+    if exact_any and query is None:
+        raise _l.SunerfHipError(_NO_QUERY)
+    exact = exact_any or _use_exact_backward(n * s, query)
     pipe_bytes = 0
     if n > 0 and not exact:
         # the forward chose the stash format for the backward it expected (training_stash_format): phases are read by the
@@ -821,8 +855,13 @@ def mlp_backward(packed: PackedMLP, g_raw, absmax, stash, grad_weights: Sequence
             raise ValueError(f'grad buffer {i} has the wrong shape / layout')
     GW = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in grad_weights])
     GB = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in grad_biases])
-    if exact:
-        _mlp_backward_exact(packed, g_raw, query, grad_weights, grad_biases, kernel_accumulate)
+    if exact_any and n * s == 0:
+        if not kernel_accumulate:
+            for gw, gb in zip(grad_weights, grad_biases):
+                gw.zero_()
+                gb.zero_()
+    elif exact:
+        _mlp_backward_exact(packed, g_raw, query, grad_weights, grad_biases, kernel_accumulate, chunked=exact_any)
     elif pipe_bytes:
         ws = _pipe_workspace(dev, pipe_bytes)
         flags = _pipe_flags()

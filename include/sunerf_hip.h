@@ -237,6 +237,21 @@ int sunerf_mlp_backward_exact(const float* const* weights_host, const float* con
                               size_t workspace_bytes, float* const* grad_weights_host, float* const* grad_biases_host,
                               int accumulate, void* stream);
 
+/* The same gradients, same arithmetic, at ANY batch size (opt-in: SUNERF_BACKWARD_PRECISION=exact, sunerf_hip/ops.py).  Replaces
+ * torch.autograd over sunerf/model/model.py:44-57 + 123-132 for a whole training batch.  The samples run in chunks of 32768
+ * (16384 at d_filter > 256): per chunk the encoder features and the fp32 forward are recomputed and the chunk's weight and bias
+ * gradients are added into fp64 accumulators in a fixed order (no atomics: two runs give bit-identical gradients); the GEMMs are
+ * LDS-tiled fp32-input MFMA.  The workspace depends on (d_filter, n_linear) only.
+ *   arguments                 : as sunerf_mlp_backward_exact; d_out 1 or 2; N*S up to 2^40 samples
+ *   workspace                 : sunerf_mlp_backward_exact_chunked_workspace_bytes(d_filter, n_linear) bytes */
+size_t sunerf_mlp_backward_exact_chunked_workspace_bytes(int d_filter, int n_linear);
+int sunerf_mlp_backward_exact_chunked(const float* const* weights_host, const float* const* biases_host, int n_linear,
+                                      int d_filter, int d_out, const float* rays_o, const float* rays_d, const float* times,
+                                      const float* z_vals, const float* points, int64_t n_rays, int n_samples,
+                                      const float* g_raw, void* workspace, size_t workspace_bytes,
+                                      float* const* grad_weights_host, float* const* grad_biases_host, int accumulate,
+                                      void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Density / temperature head (run_density_temperature.py path).
  * Replaces DensityTemperatureRadiativeTransfer.raw2outputs / regularization, density_temperature.py:192-274, the base
