@@ -29,6 +29,7 @@ constexpr int DT_RAYS = DT_THREADS / 32;      // rays per workgroup (and per ste
 constexpr int DT_MAX_GRID = 1024;             // backward: workgroups of the grid
 constexpr int NCH = 7;
 constexpr int NTAB = NCH * 101;
+constexpr int DT_BWD_LDS_HEAD = 2 * NTAB + 8 + DT_THREADS / 64;   // backward LDS floats before the exp(-A) slabs
 
 struct DtArgs {
   const float* raw;          // (N,S,2) MLP output
@@ -228,9 +229,12 @@ __global__ __launch_bounds__(DT_THREADS) void dt_integral_fwd_kernel(DtArgs a) {
 // order).  EXTRA = false is the kernel of sunerf_dt_integral_bwd as it always was.
 template <bool EXTRA>
 __global__ __launch_bounds__(DT_THREADS) void dt_integral_bwd_kernel(DtArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];    // tables | g_kappa[7] g_vol | [DT_RAYS][S][NCH] exp(-A)
+  // tables | g_kappa[7] g_vol | wave maxima | [DT_RAYS][S][NCH] exp(-A).  All of it dynamic (no static __shared__): the
+  // launcher's 160 KiB check then sees the whole allocation.
+  extern __shared__ __attribute__((aligned(16))) float lds[];
   float* tab = lds;
   float* acc8 = lds + 2 * NTAB;
+  float* wave_max = acc8 + 8;
   const int tid = threadIdx.x, n = tid & 31, sub = tid >> 5;
   for (int i = tid; i < NTAB; i += DT_THREADS) { tab[i] = a.table_logt[i]; tab[NTAB + i] = a.table_resp[i]; }
   if (tid < 8) acc8[tid] = 0.f;
@@ -244,7 +248,7 @@ __global__ __launch_bounds__(DT_THREADS) void dt_integral_bwd_kernel(DtArgs a) {
   const bool ray_ok = ray_raw < a.n_rays;
   const int64_t ray = ray_ok ? ray_raw : a.n_rays - 1;
   const int S = a.S, n_chunks = (S + 31) >> 5;
-  float* ea = lds + 2 * NTAB + 8 + (size_t)sub * S * NCH;
+  float* ea = lds + DT_BWD_LDS_HEAD + (size_t)sub * S * NCH;
   const float* z = a.z_vals + ray * S;
   const float* r = a.raw + ray * S * 2;
   Channels C;
@@ -363,7 +367,6 @@ __global__ __launch_bounds__(DT_THREADS) void dt_integral_bwd_kernel(DtArgs a) {
   }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) local_max = fmaxf(local_max, __shfl_xor(local_max, d));
-  __shared__ float wave_max[DT_THREADS / 64];
   if ((tid & 63) == 0) wave_max[tid >> 6] = local_max;
   __syncthreads();
   if (tid < NCH && acc8[tid] != 0.f) atomicAdd(a.g_log_abs + tid, acc8[tid]);
@@ -619,6 +622,10 @@ namespace {
 
 template <bool EXTRA>
 int launch_dt_bwd(const DtArgs& a, void* g_absmax, hipStream_t st) {
+  // dynamic LDS is the whole allocation (the kernel declares no static __shared__): S <= 705 fits the 160 KiB of a CU.
+  // Refused before anything is queued, the outputs untouched.
+  const size_t lds = ((size_t)DT_BWD_LDS_HEAD + (size_t)DT_RAYS * a.S * NCH) * sizeof(float);
+  if (a.n_rays > 0 && lds > 160 * 1024) return SUNERF_E_UNSUPPORTED;
   hipError_t e;
   if ((char*)a.g_vol_c == (char*)a.g_log_abs + NCH * sizeof(float) && (char*)g_absmax == (char*)a.g_vol_c + sizeof(float)) {
     // the three small outputs in one buffer (what the Python wrapper passes): one clear instead of three
@@ -629,8 +636,6 @@ int launch_dt_bwd(const DtArgs& a, void* g_absmax, hipStream_t st) {
     if ((e = hipMemsetAsync(a.g_vol_c, 0, sizeof(float), st)) != hipSuccess) return (int)e;
   }
   if (a.n_rays == 0) return 0;
-  const size_t lds = ((size_t)2 * NTAB + 8 + (size_t)DT_RAYS * a.S * NCH) * sizeof(float);
-  if (lds > 160 * 1024) return SUNERF_E_UNSUPPORTED;
   if (lds > 64 * 1024) {
     e = hipFuncSetAttribute((const void*)dt_integral_bwd_kernel<EXTRA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
@@ -658,7 +663,8 @@ extern "C" int sunerf_dt_integral_bwd(const float* raw, const float* z_vals, con
   a.S = n_samples; a.g_image = g_image; a.g_reg = g_reg; a.g_raw = g_raw; a.g_log_abs = g_log_abs; a.g_vol_c = g_vol_c;
   a.g_absmax_bits = (unsigned*)g_absmax;
   if (int rc = check_common(a)) return rc;
-  if (!g_image || !g_raw || !g_log_abs || !g_vol_c || !g_absmax) return SUNERF_E_BADARG;
+  // an empty batch has null (N,...) tensors; its call only clears the scalar outputs
+  if (!g_log_abs || !g_vol_c || !g_absmax || (n_rays > 0 && (!g_image || !g_raw))) return SUNERF_E_BADARG;
   return launch_dt_bwd<false>(a, g_absmax, (hipStream_t)stream);
 }
 
@@ -676,6 +682,7 @@ extern "C" int sunerf_dt_integral_bwd_full(const float* raw, const float* z_vals
   a.S = n_samples; a.g_image = g_image; a.g_reg = g_reg; a.g_raw = g_raw; a.g_log_abs = g_log_abs; a.g_vol_c = g_vol_c;
   a.g_absmax_bits = (unsigned*)g_absmax; a.g_weights = g_weights; a.g_reg_q = g_reg_q;
   if (int rc = check_common(a)) return rc;
-  if (!g_image || !g_raw || !g_log_abs || !g_vol_c || !g_absmax) return SUNERF_E_BADARG;
+  // an empty batch has null (N,...) tensors; its call only clears the scalar outputs
+  if (!g_log_abs || !g_vol_c || !g_absmax || (n_rays > 0 && (!g_image || !g_raw))) return SUNERF_E_BADARG;
   return launch_dt_bwd<true>(a, g_absmax, (hipStream_t)stream);
 }

@@ -667,6 +667,8 @@ extern "C" int sunerf_emission_integral_bwd(const float* raw, const float* z_val
                                             int64_t n_rays, int n_samples, float* g_raw, void* g_absmax, void* stream) {
   if (n_rays < 0 || n_samples < 2 || !g_absmax) return SUNERF_E_BADARG;
   if (n_rays > 0 && (!raw || !z_vals || !rays_o || !rays_d || !g_image || !g_raw)) return SUNERF_E_BADARG;
+  // + 16 B of static LDS (wave_max): `lds` is a multiple of 3072 B, so the largest accepted value is 162 816 B and the total
+  // stays within the CU's 160 KiB
   const size_t lds = (size_t)IB_RAYS * 3 * (size_t)((n_samples + 31) / 32 * 32) * sizeof(float);
   if (lds > 160 * 1024) return SUNERF_E_UNSUPPORTED;
   hipError_t e = hipMemsetAsync(g_absmax, 0, 4, (hipStream_t)stream);

@@ -1281,7 +1281,7 @@ __global__ __launch_bounds__(THREADS, 1) void render_fwd_kernel(RenderArgs a) {
 template <int D, int STASH, bool FP8C, bool HALF = false>
 int launch_render_t(const RenderArgs& a, hipStream_t stream) {
   const PackedLayout L(D, a.n_linear);
-  const size_t lds = (size_t)Ring<D>::RING + L.n_bias() * 4;
+  const size_t lds = (size_t)Ring<D>::RING + L.n_bias() * 4;      // the whole allocation: the kernel has no static __shared__
   if (lds > 160 * 1024) return SUNERF_E_UNSUPPORTED;
   hipError_t e = hipFuncSetAttribute((const void*)render_fwd_kernel<D, STASH, FP8C, HALF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;

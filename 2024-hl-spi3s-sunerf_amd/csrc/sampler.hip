@@ -195,6 +195,7 @@ extern "C" int sunerf_hier_resample(const float* z_vals, const float* weights, c
   if (n_rays < 0 || n_coarse < 3 || n_fine < 1) return SUNERF_E_BADARG;
   if (n_rays == 0) return 0;
   if (!z_vals || !weights || !u || !new_z || !z_comb) return SUNERF_E_BADARG;
+  // hier_resample_kernel declares no static __shared__: `lds` is the whole allocation, checked against the CU's 160 KiB
   const size_t lds = ((size_t)2 * (n_coarse - 1) + n_fine + n_coarse) * RS_RAYS * sizeof(float);
   if (lds > 160 * 1024) return SUNERF_E_UNSUPPORTED;
   if (n_rays == 0) return 0;

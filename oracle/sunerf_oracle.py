@@ -430,7 +430,7 @@ def dt_integral(inferences: torch.Tensor, log_abs: Dict[str, torch.Tensor], vol_
     log_temperature = torch.nn.functional.relu(inferences[..., 1])
     log_temperature = log_temperature[:, :, None].expand(-1, -1, wl.shape[2])
     temperature_response = torch.zeros_like(log_temperature)
-    absorption_coefficients = torch.zeros_like(wl).float()
+    absorption_coefficients = torch.zeros_like(log_temperature)      # the working dtype: fp64 when the caller evaluates in fp64
     for c, w in enumerate(AIA_WAVELENGTHS):
         sel = wl == float(w)
         if sel.any():
