@@ -125,7 +125,7 @@ def positional_encoding(x: torch.Tensor, n_freqs: int = 10, scale_factor: float 
     """PositionalEncoding.forward, model.py:123-132 (freq bands :113-114): (M, 4) -> (M, 84).
 
     Layout: 4 raw, 40 sin (frequency-major, coordinate-minor), 40 cos."""
-    freq_bands = 2. ** torch.linspace(0., n_freqs - 1, n_freqs)
+    freq_bands = 2. ** torch.linspace(0., n_freqs - 1, n_freqs, device=x.device)     # (integers: the same values on any device)
     f = freq_bands[None, :, None]
     arg = x[:, None, :] * f / scale_factor
     return torch.concat([x, torch.sin(arg).reshape(x.shape[0], -1), torch.cos(arg).reshape(x.shape[0], -1)],
@@ -228,6 +228,30 @@ def render_pass(params: Params, rays_o, rays_d, times, z_vals, half: bool = Fals
     out = emission_integral(raw, z_vals, rays_d)
     out['raw'] = raw
     out['points'] = pts
+    return out
+
+
+def render_pass_f64(params: Params, rays_o, rays_d, times, z_vals, reg_radius: float = 1.2) -> Dict[str, torch.Tensor]:
+    """:func:`render_pass` evaluated in float64 on the reference's own fp32 inputs: a high-precision yardstick for kernels that
+    are held to fp32-class accuracy (the fp32 oracle carries ~2^-24 of rounding noise per operation itself).
+
+    The sample points are formed in fp32 exactly as :func:`render_pass` forms them -- they ARE the network's input in the
+    reference -- then the query, the parameters, ``z_vals`` and ``rays_d`` are promoted and the MLP and the emission integral
+    run in float64.  Returns the dict of :func:`render_pass` (float64; ``points`` the fp32 points promoted) plus
+    ``regularization`` (N, S) = relu(|p| - reg_radius) (1 - absorption) (base_tracing.py:43-44, D2 resolved) and
+    ``height_map`` / ``absorption_map`` of the single pass.  Plain torch on whatever device the inputs are on; gradients flow
+    to float64 leaves passed in ``params``."""
+    pts = points_on_rays(rays_o, rays_d, z_vals)
+    query = torch.cat([pts, times[:, None].repeat(1, pts.shape[1], 1)], -1).double()
+    p64 = [(W.double(), b.double()) for W, b in params]
+    raw = mlp_forward(p64, query.view(-1, 4)).reshape(*query.shape[:-1], -1)
+    out = emission_integral(raw, z_vals.double(), rays_d.double())
+    out['raw'] = raw
+    out['points'] = pts.double()
+    dist_pts = out['points'].pow(2).sum(-1).pow(0.5)
+    out['height_map'] = (out['weights'] * dist_pts).sum(-1)
+    out['absorption_map'] = (1 - out['regularizing_quantity']).sum(-1)
+    out['regularization'] = torch.relu(dist_pts - reg_radius) * (1 - out['regularizing_quantity'])
     return out
 
 

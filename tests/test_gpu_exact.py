@@ -52,6 +52,14 @@ def _oracle(params, o, d, t, z, g_image, g_reg_const):
     return [(W.grad, b.grad) for W, b in leaves], out['raw'].grad
 
 
+def _oracle64(params, o, d, t, z, g_image, g_reg_const):
+    """The same gradients in float64 (orc.render_pass_f64): the yardstick both fp32 evaluations are measured against."""
+    leaves = [(W.double().requires_grad_(True), b.double().requires_grad_(True)) for W, b in params]
+    out = orc.render_pass_f64(leaves, o, d, t, z, 1.2)
+    ((out['image'][:, 0] * g_image.double()).sum() + g_reg_const * out['regularization'].sum()).backward()
+    return [(W.grad, b.grad) for W, b in leaves]
+
+
 def _hip(ops, params, o, d, t, z, g_image, g_reg_const, times=True, accumulate_twice=False):
     dev = torch.device('cuda')
     Ws, bs = [W.to(dev) for W, _ in params], [b.to(dev) for _, b in params]
@@ -67,28 +75,37 @@ def _hip(ops, params, o, d, t, z, g_image, g_reg_const, times=True, accumulate_t
 
 
 def _worst(got, ref):
-    return max(max(((W - rW).norm() / rW.norm()).item(), ((b - rb).norm() / rb.norm()).item()) for (W, b), (rW, rb) in zip(got, ref))
+    return max(max(((W.double() - rW).norm() / rW.norm()).item(), ((b.double() - rb).norm() / rb.norm()).item())
+               for (W, b), (rW, rb) in zip(got, ref))
 
 
 @pytest.mark.parametrize('d_filter,n_layers,n_rays,S', [(256, 8, 17, 128), (256, 8, 17, 2), (64, 3, 33, 33), (128, 7, 17, 2), (64, 4, 33, 3),
                                                         (512, 3, 5, 65), (64, 1, 1, 2), (256, 2, 100, 31), (128, 8, 3, 200)])
 def test_fp32_backward_matches_the_oracle_autograd(ops, d_filter, n_layers, n_rays, S):
     """Every tensor of every shape -- the three shapes the randomised sweep of round 3 found outside the gate included (d 64 / 128,
-    34 ... 1100 samples) -- within 1e-4 of torch.autograd on the fp32 oracle (measured 4e-7 ... 5e-5: printed); the fp16 kernels on the same
-    inputs, for comparison, against the bound their arithmetic allows (conftest.fp16_chain_bias_bounds)."""
+    34 ... 1100 samples) -- within 1e-4 of torch.autograd on the fp32 oracle (measured 4e-7 ... 5e-5: printed) and within 1e-4 of
+    float64 autograd (orc.render_pass_f64); the fp16 kernels on the same inputs, for comparison, against the bound their arithmetic
+    allows (conftest.fp16_chain_bias_bounds).  The kernel-vs-fp32-oracle difference is the sum of two fp32 evaluations' rounding
+    errors; the float64 reference splits it (printed side by side) and puts it on the KERNEL's side: the fp32 oracle is <= 1.8e-6
+    from float64 in every case, the kernel up to 4.5e-5 (2 x 256, 100 rays x 31: the 4.7e-5 seen against the fp32 oracle).  The
+    kernel is not the more accurate side, so the bound stays 1e-4 against both."""
     params, o, d, t, z = _case(d_filter, n_layers, n_rays, S, seed=S)
     assert n_rays * S <= ops.exact_backward_limit()
     g_image = torch.randn(n_rays) * 1e-3
     ref, ref_graw = _oracle(params, o, d, t, z, g_image, 2e-5)
     got = _hip(ops, params, o, d, t, z, g_image, 2e-5)
     worst = _worst(got, ref)
+    ref64 = _oracle64(params, o, d, t, z, g_image, 2e-5)
+    worst64, oracle64 = _worst(got, ref64), _worst(ref, ref64)
     fp16 = _hip(ops, params, o, d, t, z, g_image, 2e-5, times=False)          # no query -> the fp16 kernels, as before
     model = fp16_chain_bias_bounds(params, o, d, t, z, ref_graw)
     eb16 = [((b - rb).norm() / rb.norm()).item() for (_, b), (_, rb) in zip(fp16, ref)]
     ew16 = max(((W - rW).norm() / rW.norm()).item() for (W, _), (rW, _) in zip(fp16, ref))
-    print(f'{n_layers} x {d_filter}, {n_rays} rays x {S}: fp32 backward worst tensor {worst:.1e}; fp16 kernels: weights {ew16:.1e}, biases '
+    print(f'{n_layers} x {d_filter}, {n_rays} rays x {S}: fp32 backward worst tensor {worst:.1e} vs the fp32 oracle; vs float64: kernel '
+          f'{worst64:.1e}, fp32 oracle {oracle64:.1e}; fp16 kernels: weights {ew16:.1e}, biases '
           + ' '.join(f'{e:.1e} (kappa {k:.1f}, bound {bd:.1e})' for e, (k, bd) in zip(eb16, model)))
     assert worst < 1e-4
+    assert worst64 < 1e-4
     for l, (e, (_, bound)) in enumerate(zip(eb16, model)):
         assert e <= bound, (l, e, bound)
 
