@@ -92,6 +92,26 @@ def _scalar_head_slice(scalars):
     return owner.flat_grads[first:first + len(tags)]
 
 
+def _scalar_head_grads(needs_vc, needs_la, vol_c_param, la_params, g_vc, g_la):
+    """Autograd's share of the DT integral's scalar-head gradients (``g_vc`` (1,), ``g_la`` (7,)) for the passes of an analytic
+    field (``_StarDtPass``, ``_FieldDtPass``): added straight into the parameters' slots of a flat gradient bucket when they
+    have them (autograd then gets None), else returned per parameter.  Returns ``(g_vol_c, (g_la per channel))``."""
+    n_la = len(la_params)
+    la_slot = _scalar_head_slice(la_params) if all(needs_la) else None
+    vc_slot = _scalar_head_slice([vol_c_param]) if needs_vc else None
+    if la_slot is not None:
+        la_slot.add_(g_la)
+        g_la_out = (None,) * n_la
+    else:
+        g_la_out = tuple(g_la[i] if needs_la[i] else None for i in range(n_la))
+    if vc_slot is not None:
+        vc_slot.add_(g_vc)
+        g_vc_out = None
+    else:
+        g_vc_out = g_vc.reshape(()) if needs_vc else None
+    return g_vc_out, g_la_out
+
+
 def _announce(params):
     """The gradients of ``params`` are final in their flat bucket: let its owner start the all-reduce of that slice while the
     other model's backward still runs (``ClipAdam(overlap=True)``)."""
@@ -365,7 +385,8 @@ class _DtPass(torch.autograd.Function):
 def dt_pass(model, tables, pixel_factor, rays_o, rays_d, times, z_vals, wavelengths, reg_radius, want_epilogues):
     """Dict of one DT pass' outputs (image (N,W), weights, regularizing_quantity[, maps, regularization])."""
     if hasattr(model, 'field_on_rays'):
-        # analytic field (SimpleStar) instead of an MLP: same integral (stellar_model.py, image_render.py:266)
+        # analytic field (SimpleStar) or simulation cube (MHDModel) instead of an MLP: same integral (stellar_model.py,
+        # mhd_model.py, image_render.py:244-269).  A time-dependent field is handed the rays' times.
         keys = ['image', 'weights', 'regularizing_quantity'] + (['height_map', 'absorption_map', 'regularization']
                                                                 if want_epilogues else [])
         la = [model.log_absortpion[str(w)] for w in ops.AIA_WAVELENGTHS]
@@ -374,8 +395,15 @@ def dt_pass(model, tables, pixel_factor, rays_o, rays_d, times, z_vals, waveleng
             outs = _StarDtPass.apply(model, tables, pixel_factor, rays_o, rays_d, z_vals, wavelengths, reg_radius, want_epilogues,
                                      model.volumetric_constant, *la, *sp)
             return dict(zip(keys, outs))
+        time_dependent = getattr(model, 'time_dependent', False)
+        if (not sp and time_dependent and torch.is_grad_enabled()
+                and any(p.requires_grad for p in la + [model.volumetric_constant])):
+            outs = _FieldDtPass.apply(model, tables, pixel_factor, rays_o, rays_d, times, z_vals, wavelengths, reg_radius,
+                                      want_epilogues, model.volumetric_constant, *la)
+            return dict(zip(keys, outs))
         with torch.no_grad():
-            raw = model.field_on_rays(rays_o, rays_d, z_vals)
+            raw = (model.field_on_rays(rays_o, rays_d, z_vals, times) if time_dependent
+                   else model.field_on_rays(rays_o, rays_d, z_vals))
             la = torch.stack([p.detach() for p in la])
             out = ops.dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, tables[0], tables[1], la,
                                       model.volumetric_constant, model.base_log_density, model.base_log_temperature,
@@ -494,18 +522,50 @@ class _StarDtPass(torch.autograd.Function):
         g_raw, g_la, g_vc, _ = ops.dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, ctx.tables[0], ctx.tables[1], la,
                                                    vol_c, ctx.base[0], ctx.base[1], ctx.pixel_factor, ctx.reg_radius,
                                                    g_image.contiguous(), g_reg)
-        needs_vc, needs_la = ctx.needs_input_grad[9], ctx.needs_input_grad[10:10 + n_la]
-        la_slot = _scalar_head_slice(ctx.la_params) if all(needs_la) else None
-        vc_slot = _scalar_head_slice([ctx.vol_c_param]) if needs_vc else None
-        if la_slot is not None:
-            la_slot.add_(g_la)
-            g_la_out = (None,) * n_la
-        else:
-            g_la_out = tuple(g_la[i] if needs_la[i] else None for i in range(n_la))
-        if vc_slot is not None:
-            vc_slot.add_(g_vc)
-            g_vc_out = None
-        else:
-            g_vc_out = g_vc.reshape(()) if needs_vc else None
+        g_vc_out, g_la_out = _scalar_head_grads(ctx.needs_input_grad[9], ctx.needs_input_grad[10:10 + n_la], ctx.vol_c_param,
+                                                ctx.la_params, g_vc, g_la)
         g_sp = _star_grads(ctx.needs_input_grad[10 + n_la:], rays_o, rays_d, z_vals, params, ctx.t_photosphere, g_raw, ctx.sp)
         return (None,) * 9 + (g_vc_out,) + g_la_out + g_sp
+
+
+class _FieldDtPass(torch.autograd.Function):
+    """One fused density/temperature pass of a time-dependent field without parameters of its own (``MHDModel``): field
+    kernel -> DT integral kernel.  Differentiable outputs: ``image`` (N,W) and ``regularization``; gradients for the 7
+    ``log_absortpion`` scalars and ``volumetric_constant`` (added straight into an optimiser's flat bucket when they have slots
+    there, as in ``_StarDtPass``).  No gradient w.r.t. the field's data, the rays or z."""
+
+    @staticmethod
+    def forward(ctx, field, tables, pixel_factor, rays_o, rays_d, times, z_vals, wavelengths, reg_radius, want_epilogues, vol_c,
+                *la_params):
+        la = torch.stack([p.detach() for p in la_params])
+        ctx.set_materialize_grads(False)
+        raw = field.field_on_rays(rays_o, rays_d, z_vals, times)
+        out = ops.dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, tables[0], tables[1], la, vol_c,
+                                  field.base_log_density, field.base_log_temperature, pixel_factor, reg_radius,
+                                  want_epilogues=want_epilogues)
+        ctx.tables, ctx.pixel_factor, ctx.reg_radius = tables, pixel_factor, reg_radius
+        ctx.base = (field.base_log_density, field.base_log_temperature)
+        ctx.la_params, ctx.vol_c_param = la_params, vol_c
+        ctx.save_for_backward(rays_o, rays_d, z_vals, wavelengths, raw, la, vol_c.detach())
+        outs = [out['image'], out['weights'], out['reg_q']]
+        non_diff = [out['weights'], out['reg_q']]
+        if want_epilogues:
+            outs += [out['height_map'], out['absorption_map'], out['regularization']]
+            non_diff += [out['height_map'], out['absorption_map']]
+        ctx.mark_non_differentiable(*non_diff)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, g_image, g_weights, g_q, g_hm=None, g_am=None, g_reg=None):
+        rays_o, rays_d, z_vals, wavelengths, raw, la, vol_c = ctx.saved_tensors
+        n_la = la.shape[0]
+        if g_image is None and g_reg is None:
+            return (None,) * (11 + n_la)
+        if g_image is None:
+            g_image = torch.zeros(z_vals.shape[0], wavelengths.shape[1], dtype=torch.float32, device=z_vals.device)
+        _, g_la, g_vc, _ = ops.dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, ctx.tables[0], ctx.tables[1], la,
+                                               vol_c, ctx.base[0], ctx.base[1], ctx.pixel_factor, ctx.reg_radius,
+                                               g_image.contiguous(), g_reg)
+        g_vc_out, g_la_out = _scalar_head_grads(ctx.needs_input_grad[10], ctx.needs_input_grad[11:11 + n_la], ctx.vol_c_param,
+                                                ctx.la_params, g_vc, g_la)
+        return (None,) * 10 + (g_vc_out,) + g_la_out

@@ -1018,3 +1018,104 @@ def simple_star_bwd(rays_o, rays_d, z_vals, params, t_photosphere: float, g_raw,
     _l.call(dev, 'sunerf_simple_star_bwd', _ptr(rays_o), _ptr(rays_d), _ptr(z_vals), n, s, _ptr(params), float(t_photosphere),
             _ptr(g_raw), _ptr(ws), ws.numel(), _ptr(out), 1 if accumulate else 0, _stream(dev))
     return out
+
+
+# ---- MHD simulation cube (csrc/mhd.hip) -----------------------------------------------------------------------------------
+class MhdFrame(ctypes.Structure):
+    """``SunerfMhdFrame`` of include/sunerf_hip.h: where one resident frame's nodes, axes and bucket tables live."""
+    _fields_ = [('data', ctypes.c_void_p), ('axis', ctypes.c_void_p * 3), ('bucket', ctypes.c_void_p * 3),
+                ('n', ctypes.c_int * 3), ('nb', ctypes.c_int * 3), ('lo', ctypes.c_float * 3), ('hi', ctypes.c_float * 3),
+                ('inv_width', ctypes.c_float * 3), ('reserved', ctypes.c_int)]
+
+
+MHD_MAX_BUCKETS = 1 << 16
+
+
+def mhd_bucket_table(axis: torch.Tensor) -> Tuple[torch.Tensor, float]:
+    """Uniform bucket table of one strictly increasing fp32 axis for the kernel's cell search: ``(table int32 [nb], nb /
+    (hi - lo))``, ``table[b]`` = the cell ``searchsorted(axis, edge_b, 'right') - 1`` (clipped to [0, n - 2]) holding the lower
+    edge of bucket b.  ``nb`` = span / smallest spacing (at most ``MHD_MAX_BUCKETS``): a handful of nodes per bucket even on
+    PSI's clustered r grid, so the kernel's walk from ``table[b]`` to the point's cell stays short."""
+    g = axis.detach().cpu().double()
+    n = g.numel()
+    span = float(g[-1] - g[0])
+    nb = int(min(MHD_MAX_BUCKETS, max(1, -(-span // float((g[1:] - g[:-1]).min())))))
+    edges = g[0] + torch.arange(nb, dtype=torch.float64) * (span / nb)
+    table = (torch.searchsorted(g, edges, right=True) - 1).clamp_(0, n - 2).to(torch.int32)
+    return table, float(torch.tensor(nb / span, dtype=torch.float32))
+
+
+def mhd_frame(data: torch.Tensor, axes: Sequence[torch.Tensor]) -> Tuple[MhdFrame, Tuple[torch.Tensor, ...]]:
+    """Descriptor of one resident frame: ``data`` (n_phi, n_theta, n_r, 2) fp32 (rho, T) and its three fp32 axes
+    (phi, theta, r), all on the device.  Returns the descriptor and the tensors it points into (the bucket tables are made
+    here and must be kept alive with the data)."""
+    dev = data.device
+    if data.dtype != torch.float32 or not data.is_contiguous() or data.dim() != 4 or data.shape[3] != 2:
+        raise ValueError('data must be a contiguous (n_phi, n_theta, n_r, 2) float32 tensor')
+    desc = MhdFrame()
+    keep = [data]
+    desc.data = data.data_ptr()
+    for k, ax in enumerate(axes):
+        ax = _dev(ax, 'axis', (data.shape[k],))
+        if ax.numel() < 2 or not bool((ax[1:] > ax[:-1]).all()):
+            raise ValueError('every MHD grid axis needs at least two strictly increasing nodes')
+        table, inv_width = mhd_bucket_table(ax)
+        table = table.to(dev)
+        keep += [ax, table]
+        desc.axis[k], desc.bucket[k] = ax.data_ptr(), table.data_ptr()
+        desc.n[k], desc.nb[k] = ax.numel(), table.numel()
+        desc.lo[k], desc.hi[k], desc.inv_width[k] = float(ax[0]), float(ax[-1]), inv_width
+    return desc, tuple(keep)
+
+
+def _mhd_tables(frames, slot, ffirst: int, flast: int, dev):
+    if ctypes.sizeof(MhdFrame) != _l.load().sunerf_mhd_frame_bytes():
+        raise _l.SunerfHipError('SunerfMhdFrame layout differs between the library and sunerf_hip.ops.MhdFrame')
+    if (not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.device != dev
+            or frames.numel() % ctypes.sizeof(MhdFrame) or not frames.is_contiguous()):
+        raise ValueError('frames must be a contiguous uint8 device tensor of SunerfMhdFrame records on the device of the inputs')
+    if (not isinstance(slot, torch.Tensor) or slot.dtype != torch.int32 or slot.device != dev
+            or tuple(slot.shape) != (flast - ffirst + 1,) or not slot.is_contiguous()):
+        raise ValueError(f'slot must be a contiguous int32 ({flast - ffirst + 1},) tensor on the device of the inputs')
+
+
+def _mhd_status(status):
+    if int(status.item()) != 0:
+        raise _l.SunerfHipError('sunerf_mhd_field: a point needed a frame that is not resident (its output is NaN)')
+
+
+def mhd_field(rays_o, rays_d, z_vals, times, frames, slot, ffirst: int, flast: int):
+    """MHDModel.forward (mhd_model.py:76-142) at the samples o + d z of every ray at its time ``times`` (N, 1) -> raw
+    (N, S, 2) = (ln rho, log10 T).  ``frames`` / ``slot``: the resident-frame table (uint8 records of ``MhdFrame``) and the
+    int32 slot of every frame ffirst..flast (-1: not resident).  Raises when a point needed a frame that is not resident."""
+    n, s = z_vals.shape
+    dev = z_vals.device
+    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3)); z_vals = _dev(z_vals, 'z_vals', (n, s))
+    times = _dev(times, 'times').reshape(-1)
+    if times.shape != (n,):
+        raise ValueError(f'times has {times.numel()} entries, expected one per ray ({n})')
+    _mhd_tables(frames, slot, ffirst, flast, dev)
+    raw = torch.empty(n, s, 2, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _l.call(dev, 'sunerf_mhd_field', _ptr(rays_o), _ptr(rays_d), _ptr(z_vals), _ptr(times), n, s, _ptr(frames), _ptr(slot),
+            int(ffirst), int(flast), _ptr(raw), _ptr(status), _stream(dev))
+    _mhd_status(status)
+    return raw
+
+
+def mhd_field_points(points, frames, slot, ffirst: int, flast: int):
+    """:func:`mhd_field` at free-standing points (M, 4) = (x, y, z, t) -> (M, 2)."""
+    dev = points.device
+    points = _dev(points, 'points')
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise ValueError(f'points has shape {tuple(points.shape)}, expected (M, 4)')
+    if points.data_ptr() % 16:                  # the kernel reads a point as one 16-byte load
+        points = points.clone()
+    _mhd_tables(frames, slot, ffirst, flast, dev)
+    m = points.shape[0]
+    raw = torch.empty(m, 2, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _l.call(dev, 'sunerf_mhd_field_points', _ptr(points), m, _ptr(frames), _ptr(slot), int(ffirst), int(flast), _ptr(raw),
+            _ptr(status), _stream(dev))
+    _mhd_status(status)
+    return raw

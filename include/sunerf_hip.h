@@ -383,6 +383,43 @@ int sunerf_simple_star_bwd(const float* rays_o, const float* rays_d, const float
                            size_t workspace_bytes, float* g_params, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * MHD simulation cube (PSI rho / t frames): replaces MHDModel.forward, sunerf/model/mhd_model.py:76-142, as a field
+ * behind sunerf_dt_integral_fwd (DensityTemperatureRadiativeTransfer(model=MHDModel), evaluation/image_render.py:244-269).
+ *
+ * Per point (x, y, z, t), fp32 (:100-103, :121-124):
+ *   r = sqrt(x^2 + y^2 + z^2), theta = acos(z / r), phi = atan2(y, x) (+ 2 pi where < 0)
+ *   f = t (flast - ffirst) + ffirst, w = f - trunc(f), f1 = floor(f), f2 = ceil(f)
+ *   v_k = trilinear interpolation of frame f_k on ITS (phi, theta, r) grid, (1e-10, 1e-10) outside it (bounds inclusive),
+ *         NaN for a NaN coordinate (RegularGridInterpolator(method='linear', bounds_error=False, fill_value=1e-10), :45-75)
+ *   raw = (ln((1 - w) rho_1 + w rho_2), log10(1e6 ((1 - w) T_1 + w T_2)))                                  (:137-138)
+ *
+ * Residency: frames[] holds one SunerfMhdFrame per resident slot, slot[f - ffirst] (f = ffirst..flast) the slot of
+ * frame f or -1.  A point whose frame is not resident gets NaN and sets *status = 1 (status is only ever written 1;
+ * the caller zeroes it).  No host synchronisation.
+ *   sunerf_mhd_field:        rays_o [N,3], rays_d [N,3], z_vals [N,S], times [N] -> raw [N,S,2]  (points o + d z in the kernel)
+ *   sunerf_mhd_field_points: points [M,4] = (x, y, z, t) -> raw [M,2]
+ *   sunerf_mhd_frame_bytes:  sizeof(SunerfMhdFrame), for bindings that lay the table out themselves.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct SunerfMhdFrame {
+  const float* data;        /* [n_phi][n_theta][n_r] nodes, each (rho, T) interleaved: 8 bytes per node */
+  const float* axis[3];     /* phi, theta, r nodes, strictly increasing */
+  const int* bucket[3];     /* per axis nb[k] entries: the cell (lower node) holding the lower edge of each uniform bucket */
+  int n[3];                 /* nodes per axis, >= 2 */
+  int nb[3];                /* buckets per axis, >= 1 */
+  float lo[3];              /* axis[k][0] */
+  float hi[3];              /* axis[k][n[k] - 1] */
+  float inv_width[3];       /* nb[k] / (hi[k] - lo[k]) */
+  int reserved;
+} SunerfMhdFrame;
+
+size_t sunerf_mhd_frame_bytes(void);
+int sunerf_mhd_field(const float* rays_o, const float* rays_d, const float* z_vals, const float* times, int64_t n_rays,
+                     int n_samples, const SunerfMhdFrame* frames, const int* slot, int ffirst, int flast, float* raw,
+                     int* status, void* stream);
+int sunerf_mhd_field_points(const float* points, int64_t n_points, const SunerfMhdFrame* frames, const int* slot, int ffirst,
+                            int flast, float* raw, int* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Hierarchical (inverse-CDF) resampling + merge.
  * Replaces HierarchicalSampler.forward / sample_pdf, sampling.py:111-169 (perturb=False: u = linspace(0,1,S_f),
  * passed in as the tensor `u` [S_f] so that torch.linspace's own fp32 values are used; or a per-ray u [N,S_f]
