@@ -569,3 +569,114 @@ class _FieldDtPass(torch.autograd.Function):
         g_vc_out, g_la_out = _scalar_head_grads(ctx.needs_input_grad[10], ctx.needs_input_grad[11:11 + n_la], ctx.vol_c_param,
                                                 ctx.la_params, g_vc, g_la)
         return (None,) * 10 + (g_vc_out,) + g_la_out
+
+
+# ---- white-light Thomson scattering (thompson.py:17-109) -----------------------------------------------------------------
+LN10 = 2.302585092994046        # a NeRF's channel 0 is log10 rho (thompson.py:39: rho = 10 ** raw[..., 0])
+THOMSON_KEYS = ('pixel_B', 'pixel_density', 'distance_from_sun', 'distance_from_obs', 'weights')
+
+
+def _thomson_dict(outs):
+    out = dict(zip(THOMSON_KEYS, outs))
+    out['image'] = out['pixel_B']
+    out['regularizing_quantity'] = torch.ones_like(out['weights'])     # optically thin: no absorption, no regularization
+    return out
+
+
+class _ThomsonIntegral(torch.autograd.Function):
+    """``ThompsonScattering.raw2outputs`` (thompson.py:17-109, defects resolved) on a given raw tensor (N, S, C): differentiable
+    w.r.t. ``raw`` through all five outputs (sunerf_thomson_integral_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, raw, z_vals, rays_o, rays_d, constants, kappa):
+        out = ops.thomson_integral_fwd(raw.detach(), z_vals, rays_o, rays_d, constants, kappa)
+        ctx.constants, ctx.kappa = constants, kappa
+        ctx.save_for_backward(raw.detach(), z_vals, rays_o, rays_d)
+        ctx.set_materialize_grads(False)
+        return tuple(out[k] for k in THOMSON_KEYS)
+
+    @staticmethod
+    def backward(ctx, g_b, g_den, g_sun, g_obs, g_w):
+        raw, z_vals, rays_o, rays_d = ctx.saved_tensors
+        if all(g is None for g in (g_b, g_den, g_sun, g_obs, g_w)):
+            return (None,) * 6
+        cont = lambda g: None if g is None else g.contiguous()      # noqa: E731
+        g_raw, _ = ops.thomson_integral_bwd(raw, z_vals, rays_o, rays_d, ctx.constants, ctx.kappa, cont(g_b), cont(g_den),
+                                            cont(g_sun), cont(g_obs), cont(g_w))
+        return (g_raw,) + (None,) * 5
+
+
+def thomson_raw2outputs(raw, z_vals, rays_o, rays_d, constants, kappa):
+    """``{pixel_B (N,2), pixel_density, distance_from_sun, distance_from_obs (N,), weights (N,S), image (= pixel_B),
+    regularizing_quantity (ones)}`` for the log density ``raw[..., 0]``, rho = exp(kappa raw0).  ``constants``: the module's
+    (solar_radius, limb_darkening_coeff, C_0) buffers.  Through autograd when ``raw`` requires a gradient."""
+    constants = tuple(constants)
+    if torch.is_grad_enabled() and raw.requires_grad:
+        return _thomson_dict(_ThomsonIntegral.apply(raw, z_vals, rays_o, rays_d, constants, kappa))
+    out = ops.thomson_integral_fwd(raw.detach(), z_vals, rays_o, rays_d, constants, kappa)
+    return _thomson_dict([out[k] for k in THOMSON_KEYS])
+
+
+class _ThomsonPass(torch.autograd.Function):
+    """One fused white-light pass of a NeRF: render kernel (MLP) -> Thomson integral kernel.  Differentiable outputs:
+    ``pixel_B``, ``pixel_density`` and the two distances; gradients for the MLP parameters (``weights`` is marked
+    non-differentiable, as in the fused emission / DT passes)."""
+
+    @staticmethod
+    def forward(ctx, model, constants, rays_o, rays_d, times, z_vals, *params):
+        training = any(ctx.needs_input_grad[6:])
+        ctx.set_materialize_grads(False)
+        packed = model.packed()
+        # (the image goes with rho = 10^raw_0: ln 10 times the emission image's sensitivity to the raw output)
+        mlp = ops.emission_render_fwd(packed, rays_o, rays_d, times, z_vals, 0.0, want_raw=True, training=training,
+                                      probe_sensitivity=LN10)
+        out = ops.thomson_integral_fwd(mlp['raw'], z_vals, rays_o, rays_d, constants, LN10)
+        if training:
+            ctx.packed, ctx.constants = packed, constants
+            ctx.params = params
+            ctx.param_meta = [(p.shape, p.device) for p in params]
+            ctx.save_for_backward(rays_o, rays_d, z_vals, mlp['raw'], mlp['stash'], times)
+        ctx.mark_non_differentiable(out['weights'])
+        return tuple(out[k] for k in THOMSON_KEYS)
+
+    @staticmethod
+    def backward(ctx, g_b, g_den, g_sun, g_obs, g_w=None):
+        if all(g is None for g in (g_b, g_den, g_sun, g_obs)):
+            return (None,) * (6 + len(ctx.params))
+        rays_o, rays_d, z_vals, raw, stash, times = ctx.saved_tensors
+        query = ('rays', rays_o, rays_d, times, z_vals)
+        cont = lambda g: None if g is None else g.contiguous()      # noqa: E731
+        g_raw, absmax = ops.thomson_integral_bwd(raw, z_vals, rays_o, rays_d, ctx.constants, LN10, cont(g_b), cont(g_den),
+                                                 cont(g_sun), cont(g_obs))
+        direct = _grad_targets(ctx.params)
+        if direct is not None:
+            ops.mlp_backward(ctx.packed, g_raw, absmax, stash, direct[0], direct[1], accumulate=True, query=query)
+            _announce(ctx.params)
+            return (None,) * (6 + len(ctx.params))
+        gW = [torch.empty(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_meta[0::2]]
+        gb = [torch.empty(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_meta[1::2]]
+        ops.mlp_backward(ctx.packed, g_raw, absmax, stash, gW, gb, query=query)
+        grads = []
+        for w, b in zip(gW, gb):
+            grads += [w, b]
+        return (None,) * 6 + tuple(grads)
+
+
+def thomson_pass(model, constants, rays_o, rays_d, times, z_vals):
+    """Dict of one white-light pass' outputs (the keys of :func:`thomson_raw2outputs`).  A ``NeRF`` runs fused (log10 rho);
+    a field module with ``field_on_rays`` (SimpleStar, MHDModel: ln rho) is evaluated by its own kernel and then integrated,
+    differentiable w.r.t. whatever parameters its ``field_on_rays`` carries gradients for."""
+    constants = tuple(constants)
+    if hasattr(model, 'field_on_rays'):
+        raw = (model.field_on_rays(rays_o, rays_d, z_vals, times) if getattr(model, 'time_dependent', False)
+               else model.field_on_rays(rays_o, rays_d, z_vals))
+        return thomson_raw2outputs(raw, z_vals, rays_o, rays_d, constants, 1.0)
+    params = []
+    for lin in model.linears():
+        params += [lin.weight, lin.bias]
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        return _thomson_dict(_ThomsonPass.apply(model, constants, rays_o, rays_d, times, z_vals, *params))
+    raw = ops.emission_render_fwd(model.packed(), rays_o, rays_d, times, z_vals, 0.0, want_raw=True,
+                                  probe_sensitivity=LN10)['raw']
+    out = ops.thomson_integral_fwd(raw, z_vals, rays_o, rays_d, constants, LN10)
+    return _thomson_dict([out[k] for k in THOMSON_KEYS])

@@ -99,6 +99,12 @@ _SIGNATURES = {
                                          ctypes.c_int, c_f32p, c_void, c_void]),
     'sunerf_mhd_field_points': (ctypes.c_int, [c_f32p, ctypes.c_int64, c_void, c_void, ctypes.c_int, ctypes.c_int, c_f32p, c_void,
                                                 c_void]),
+    'sunerf_thomson_integral_fwd': (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                                    c_f32p, ctypes.c_int64, ctypes.c_int, c_f32p, c_f32p, c_f32p, c_f32p,
+                                                    c_f32p, c_void]),
+    'sunerf_thomson_integral_bwd': (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                                    c_f32p, ctypes.c_int64, ctypes.c_int, c_f32p, c_f32p, c_f32p, c_f32p,
+                                                    c_f32p, c_f32p, c_void, c_void]),
     'sunerf_train_workspace_bytes': (ctypes.c_size_t, []),
     'sunerf_training_loss': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int64, c_f32p, ctypes.c_int64,
                                              ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,

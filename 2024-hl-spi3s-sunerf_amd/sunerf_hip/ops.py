@@ -1119,3 +1119,53 @@ def mhd_field_points(points, frames, slot, ffirst: int, flast: int):
             _ptr(status), _stream(dev))
     _mhd_status(status)
     return raw
+
+
+# ---- white-light Thomson scattering (thompson.py:17-109) ------------------------------------------------------------------
+def _thomson_inputs(raw, z_vals, rays_o, rays_d, constants):
+    n, s = z_vals.shape
+    if raw.dim() != 3 or raw.shape[:2] != (n, s) or raw.shape[2] not in (1, 2):
+        raise ValueError(f'raw has shape {tuple(raw.shape)}, expected ({n}, {s}, 1 or 2)')
+    raw = _dev(raw.detach(), 'raw'); z_vals = _dev(z_vals, 'z_vals', (n, s))
+    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3))
+    names = ('solar_radius', 'limb_darkening_coeff', 'C_0')
+    constants = [_dev(c.detach().reshape(1), name, (1,)) for c, name in zip(constants, names)]
+    return raw, z_vals, rays_o, rays_d, constants
+
+
+def thomson_integral_fwd(raw, z_vals, rays_o, rays_d, constants, kappa: float):
+    """Thomson-scattering integral on the log density ``raw[..., 0]`` (N, S, C in {1, 2}), rho = exp(kappa raw0).
+    ``constants``: the module's (solar_radius, limb_darkening_coeff, C_0) buffers, read on the device.  Returns dict(pixel_B
+    (N,2), pixel_density, distance_from_sun, distance_from_obs (N,), weights (N,S))."""
+    n, s = z_vals.shape
+    dev = z_vals.device
+    raw, z_vals, rays_o, rays_d, (rs, ld, c0) = _thomson_inputs(raw, z_vals, rays_o, rays_d, constants)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {'pixel_B': torch.empty(n, 2, **f32), 'pixel_density': torch.empty(n, **f32),
+           'distance_from_sun': torch.empty(n, **f32), 'distance_from_obs': torch.empty(n, **f32),
+           'weights': torch.empty(n, s, **f32)}
+    _l.call(dev, 'sunerf_thomson_integral_fwd', _ptr(raw), raw.shape[2], float(kappa), _ptr(z_vals), _ptr(rays_o),
+            _ptr(rays_d), _ptr(rs), _ptr(ld), _ptr(c0), n, s, _ptr(out['pixel_B']), _ptr(out['pixel_density']),
+            _ptr(out['distance_from_sun']), _ptr(out['distance_from_obs']), _ptr(out['weights']), _stream(dev))
+    return out
+
+
+def thomson_integral_bwd(raw, z_vals, rays_o, rays_d, constants, kappa: float, g_pixel_b=None, g_pixel_density=None,
+                         g_distance_from_sun=None, g_distance_from_obs=None, g_weights=None):
+    """d / d raw of :func:`thomson_integral_fwd` for the gradients of any subset of its five outputs (None = absent) ->
+    (g_raw (N,S,C), absmax): channel 1 of g_raw is 0; ``absmax`` is the int32 bit pattern of max |g_raw| that
+    :func:`mlp_backward` takes."""
+    n, s = z_vals.shape
+    dev = z_vals.device
+    raw, z_vals, rays_o, rays_d, (rs, ld, c0) = _thomson_inputs(raw, z_vals, rays_o, rays_d, constants)
+    g_pixel_b = None if g_pixel_b is None else _dev(g_pixel_b, 'g_pixel_B', (n, 2))
+    g_pixel_density = None if g_pixel_density is None else _dev(g_pixel_density, 'g_pixel_density', (n,))
+    g_distance_from_sun = None if g_distance_from_sun is None else _dev(g_distance_from_sun, 'g_distance_from_sun', (n,))
+    g_distance_from_obs = None if g_distance_from_obs is None else _dev(g_distance_from_obs, 'g_distance_from_obs', (n,))
+    g_weights = None if g_weights is None else _dev(g_weights, 'g_weights', (n, s))
+    g_raw = torch.empty(n, s, raw.shape[2], dtype=torch.float32, device=dev)
+    absmax = torch.empty(1, dtype=torch.int32, device=dev)
+    _l.call(dev, 'sunerf_thomson_integral_bwd', _ptr(raw), raw.shape[2], float(kappa), _ptr(z_vals), _ptr(rays_o),
+            _ptr(rays_d), _ptr(rs), _ptr(ld), _ptr(c0), n, s, _ptr(g_pixel_b), _ptr(g_pixel_density),
+            _ptr(g_distance_from_sun), _ptr(g_distance_from_obs), _ptr(g_weights), _ptr(g_raw), _ptr(absmax), _stream(dev))
+    return g_raw, absmax

@@ -296,6 +296,36 @@ int sunerf_dt_integral_bwd_full(const float* raw, const float* z_vals, const flo
                                 float* g_raw, float* g_log_abs, float* g_vol_c, void* g_absmax, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * White-light Thomson scattering (total / polarised brightness, Howard & Tappin 2009).
+ * Replaces ThompsonScattering.raw2outputs, sunerf/rendering/thompson.py:17-109, with the reference's defects resolved
+ * (DESIGN.md 8b): the radius runs over (x, y, z) only (:43, :53 take the time coordinate in), the geometry is fp64 (the
+ * fp32 expressions of :59-66 lose 8 % at 215 solar radii), and the outputs are those of the table below.
+ *
+ *   raw (N,S,C), C in {1, 2}: channel 0 is the log density, rho = exp(kappa raw0) (kappa = ln 10 for a NeRF, :39,
+ *   1 for a field answering ln rho); z_vals (N,S); rays_o / rays_d (N,3);
+ *   solar_radius, limb_darkening_coeff, c0: (1) device scalars, the module's buffers (:11-15), read in the kernel
+ *   pixel_b (N,2) = C_0 (sum rho |I_tot| ds, sum rho |I_P| ds)      (:82-90, eqs. 23, 24, 29)
+ *   pixel_density (N) = sum rho ds;  distance_from_sun / _obs (N) = sum rho r / (M + 1e-10), sum rho z |d| / (M + 1e-10);
+ *   weights (N,S) = rho / (M + 1e-10), M = sum rho                   (:94-101)
+ *   ds_j = (z_j - z_{j-1}) |d|, ds_0 = ds_1 (:25-31); for S = 1 there is no ds and pixel_b = pixel_density = 0.
+ *   backward: any subset of g_pixel_b (N,2), g_pixel_density, g_distance_from_sun, g_distance_from_obs (N),
+ *   g_weights (N,S) (NULL = absent) -> g_raw (N,S,C) (channel 1 written 0); g_absmax (4 bytes, may be NULL) receives
+ *   the bit pattern of max |g_raw|, as in sunerf_emission_integral_bwd (the scale sunerf_mlp_dgrad takes).
+ *   n_samples >= 1; no float atomics: reruns are bit-identical.
+ * ---------------------------------------------------------------------------------------------------------- */
+int sunerf_thomson_integral_fwd(const float* raw, int n_channels, float kappa, const float* z_vals, const float* rays_o,
+                                const float* rays_d, const float* solar_radius, const float* limb_darkening_coeff,
+                                const float* c0, int64_t n_rays, int n_samples, float* pixel_b, float* pixel_density,
+                                float* distance_from_sun, float* distance_from_obs, float* weights, void* stream);
+
+int sunerf_thomson_integral_bwd(const float* raw, int n_channels, float kappa, const float* z_vals, const float* rays_o,
+                                const float* rays_d, const float* solar_radius, const float* limb_darkening_coeff,
+                                const float* c0, int64_t n_rays, int n_samples, const float* g_pixel_b,
+                                const float* g_pixel_density, const float* g_distance_from_sun,
+                                const float* g_distance_from_obs, const float* g_weights, float* g_raw, void* g_absmax,
+                                void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Input side of the path: observer rays on the device.
  * Replaces get_rays, sunerf/data/ray_sampling.py:7-36, and the host-side tiling / H2D copy of the rays and of the
  * time column in SuNeRFLoader.render_observer_image, sunerf/evaluation/loader.py:73-92 and :186-214.
