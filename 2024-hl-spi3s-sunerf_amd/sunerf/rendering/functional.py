@@ -5,6 +5,15 @@ from sunerf_hip import ops
 from sunerf_hip.train import bucket_of
 
 
+def _mlp_params(model):
+    """``[W0, b0, W1, b1, ...]`` of a NeRF's ``nn.Linear`` layers: the order every MLP node takes its parameters in."""
+    return [t for lin in model.linears() for t in (lin.weight, lin.bias)]
+
+
+def _differentiable(params):
+    return torch.is_grad_enabled() and any(p.requires_grad for p in params)
+
+
 class _MlpOnPoints(torch.autograd.Function):
     """``NeRF.forward`` on free-standing query points (model.py:44-57) as an autograd node: the fused render kernel fed with the
     points themselves (32 per chunk, no ray, its integral unused), differentiable w.r.t. the model's parameters."""
@@ -16,7 +25,6 @@ class _MlpOnPoints(torch.autograd.Function):
         out = ops.mlp_points_fwd(packed, points, training=training)
         if training:
             ctx.packed, ctx.params, ctx.n_padded = packed, params, out['n_padded']
-            ctx.param_meta = [(p.shape, p.device) for p in params]
             ctx.save_for_backward(out['stash'], points)
         return out['raw'][:, :packed.d_out] if packed.d_out < 2 else out['raw']
 
@@ -30,18 +38,8 @@ class _MlpOnPoints(torch.autograd.Function):
         g[:g_raw.shape[0], :g_raw.shape[1]] = g_raw
         g = g.view(ctx.n_padded // 32, 32, 2)
         absmax = g.abs().max().reshape(1).view(torch.int32)      # bit pattern of max |g_raw| (sunerf_common.h: gradient scale)
-        direct = _grad_targets(ctx.params)
-        if direct is not None:
-            ops.mlp_backward(ctx.packed, g, absmax, stash, direct[0], direct[1], accumulate=True, query=query)
-            _announce(ctx.params)
-            return (None,) * (2 + len(ctx.params))
-        gW = [torch.empty(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_meta[0::2]]
-        gb = [torch.empty(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_meta[1::2]]
-        ops.mlp_backward(ctx.packed, g, absmax, stash, gW, gb, query=query)
-        grads = []
-        for w, b in zip(gW, gb):
-            grads += [w, b]
-        return (None,) * 2 + tuple(grads)
+        return (None,) * 2 + _mlp_param_grads(ctx.params, lambda gW, gb, accumulate: ops.mlp_backward(
+            ctx.packed, g, absmax, stash, gW, gb, accumulate=accumulate, query=query))
 
 
 def mlp_points(model, x: torch.Tensor) -> torch.Tensor:
@@ -49,30 +47,31 @@ def mlp_points(model, x: torch.Tensor) -> torch.Tensor:
     mode (``sunerf_mlp_points_fwd``), every lane of it a query point.  Differentiable w.r.t. the model's parameters like the
     reference's module call (a loss on free-standing points trains)."""
     flat = x.reshape(-1, 4)
-    params = []
-    for lin in model.linears():
-        params += [lin.weight, lin.bias]
-    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+    params = _mlp_params(model)
+    if _differentiable(params):
         return _MlpOnPoints.apply(model, flat, *params)
     packed = model.packed()
     raw = ops.mlp_points_fwd(packed, flat)['raw']
     return raw[:, :packed.d_out] if packed.d_out < 2 else raw
 
 
-def _grad_targets(params):
-    """(grad_weights, grad_biases) views to accumulate into directly, or None.
+def _mlp_param_grads(params, launch):
+    """Autograd's gradients for the MLP parameters ``params`` (W0, b0, W1, b1, ...) of a node.  ``launch(grad_weights,
+    grad_biases, accumulate)`` runs the weight-gradient kernels (``ops.mlp_backward`` / ``ops.emission_render_bwd``).
 
     When every parameter already owns a contiguous fp32 ``.grad`` on its device (``ClipAdam`` / ``GradBucket`` keep them as
-    views of one flat buffer), the weight-gradient kernel adds its result straight into it and the autograd node reports "no
-    gradient" for the parameters -- instead of returning 18 fresh tensors per model that autograd would then add to
-    ``.grad`` with 18 tiny kernels (a third of the step at the reference's default batch of 1024 rays)."""
-    grads = []
-    for p in params:
-        g = p.grad
-        if g is None or g.dtype != torch.float32 or g.device != p.device or not g.is_contiguous() or g.shape != p.shape:
-            return None
-        grads.append(g)
-    return grads[0::2], grads[1::2]
+    views of one flat buffer), the kernels add their result straight into it and the node reports "no gradient" for the
+    parameters -- instead of returning 18 fresh tensors per model that autograd would then add to ``.grad`` with 18 tiny
+    kernels (a third of the step at the reference's default batch of 1024 rays).  Else fresh fp32 tensors are returned."""
+    grads = [p.grad for p in params]
+    if all(g is not None and g.dtype == torch.float32 and g.device == p.device and g.is_contiguous() and g.shape == p.shape
+           for p, g in zip(params, grads)):
+        launch(grads[0::2], grads[1::2], True)
+        _announce(params)
+        return (None,) * len(params)
+    grads = [torch.empty(p.shape, dtype=torch.float32, device=p.device) for p in params]
+    launch(grads[0::2], grads[1::2], False)
+    return tuple(grads)
 
 
 def _scalar_head_slice(scalars):
@@ -93,9 +92,9 @@ def _scalar_head_slice(scalars):
 
 
 def _scalar_head_grads(needs_vc, needs_la, vol_c_param, la_params, g_vc, g_la):
-    """Autograd's share of the DT integral's scalar-head gradients (``g_vc`` (1,), ``g_la`` (7,)) for the passes of an analytic
-    field (``_StarDtPass``, ``_FieldDtPass``): added straight into the parameters' slots of a flat gradient bucket when they
-    have them (autograd then gets None), else returned per parameter.  Returns ``(g_vol_c, (g_la per channel))``."""
+    """Autograd's share of the DT integral's scalar-head gradients (``g_vc`` (1,), ``g_la`` (7,)) for the DT passes
+    (``_DtPass``, ``_FieldDtPass``): added straight into the parameters' slots of a flat gradient bucket when they have them
+    (autograd then gets None), else returned per parameter.  Returns ``(g_vol_c, (g_la per channel))``."""
     n_la = len(la_params)
     la_slot = _scalar_head_slice(la_params) if all(needs_la) else None
     vc_slot = _scalar_head_slice([vol_c_param]) if needs_vc else None
@@ -120,6 +119,22 @@ def _announce(params):
         owner[0].segment_ready(params)
 
 
+_EPILOGUES = ('height_map', 'absorption_map', 'regularization')
+
+
+def _pass_outputs(ctx, out, third, want_epilogues):
+    """The outputs of a fused emission / DT pass node: ``(image, weights, out[third][, height_map, absorption_map,
+    regularization])``, all but ``image`` and ``regularization`` marked non-differentiable."""
+    outs = tuple(out[k] for k in ('image', 'weights', third) + (_EPILOGUES if want_epilogues else ()))
+    ctx.mark_non_differentiable(*outs[1:5])
+    return outs
+
+
+def _pass_dict(outs, third):
+    """:func:`_pass_outputs`' tuple as the pass's dict, its third output named ``third``."""
+    return dict(zip(('image', 'weights', third) + _EPILOGUES, outs))
+
+
 class _EmissionPass(torch.autograd.Function):
     """One fused render pass (coarse or fine) as an autograd node.
 
@@ -134,58 +149,30 @@ class _EmissionPass(torch.autograd.Function):
         packed = model.packed()
         out = ops.emission_render_fwd(packed, rays_o, rays_d, times, z_vals, reg_radius,
                                       want_epilogues=want_epilogues, training=training)
-        ctx.training = training
         if training:
-            ctx.packed = packed
-            ctx.reg_radius = reg_radius
-            ctx.n_params = len(params)
-            ctx.params = params
-            ctx.param_meta = [(p.shape, p.device) for p in params]
+            ctx.packed, ctx.reg_radius, ctx.params = packed, reg_radius, params
             ctx.save_for_backward(rays_o, rays_d, z_vals, out['raw'], out['stash'], times)
-        outs = [out['image'], out['weights'], out['absorption']]
-        non_diff = [out['weights'], out['absorption']]
-        if want_epilogues:
-            outs += [out['height_map'], out['absorption_map'], out['regularization']]
-            non_diff += [out['height_map'], out['absorption_map']]
-        ctx.mark_non_differentiable(*non_diff)
-        ctx.want_epilogues = want_epilogues
-        return tuple(outs)
+        return _pass_outputs(ctx, out, 'absorption', want_epilogues)
 
     @staticmethod
     def backward(ctx, g_image, g_weights, g_absorption, g_hm=None, g_am=None, g_reg=None):
         rays_o, rays_d, z_vals, raw, stash, times = ctx.saved_tensors
         n, s = z_vals.shape
         if g_image is None and g_reg is None:
-            return (None,) * (7 + ctx.n_params)
+            return (None,) * (7 + len(ctx.params))
         if g_image is None:
             g_image = torch.zeros(n, dtype=torch.float32, device=z_vals.device)
-        # parameters arrive as (W0, b0, W1, b1, ...)
-        direct = _grad_targets(ctx.params)
-        if direct is not None:
-            ops.emission_render_bwd(ctx.packed, rays_o, rays_d, z_vals, raw, stash, g_image, g_reg, 0.0, ctx.reg_radius,
-                                    direct[0], direct[1], accumulate=True, times=times)
-            _announce(ctx.params)
-            return (None,) * (7 + ctx.n_params)
-        gW = [torch.empty(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_meta[0::2]]
-        gb = [torch.empty(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_meta[1::2]]
-        ops.emission_render_bwd(ctx.packed, rays_o, rays_d, z_vals, raw, stash, g_image, g_reg, 0.0, ctx.reg_radius,
-                                gW, gb, times=times)
-        grads = []
-        for w, b in zip(gW, gb):
-            grads += [w, b]
-        return (None,) * 7 + tuple(grads)
+        return (None,) * 7 + _mlp_param_grads(ctx.params, lambda gW, gb, accumulate: ops.emission_render_bwd(
+            ctx.packed, rays_o, rays_d, z_vals, raw, stash, g_image, g_reg, 0.0, ctx.reg_radius, gW, gb,
+            accumulate=accumulate, times=times))
 
 
 def emission_pass(model, rays_o, rays_d, times, z_vals, reg_radius, want_epilogues):
     """Dict of one pass' outputs; goes through autograd when gradients are enabled and the model is trainable."""
-    params = []
-    for lin in model.linears():
-        params += [lin.weight, lin.bias]
-    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+    params = _mlp_params(model)
+    if _differentiable(params):
         outs = _EmissionPass.apply(model, rays_o, rays_d, times, z_vals, reg_radius, want_epilogues, *params)
-        keys = ['image', 'weights', 'absorption'] + (['height_map', 'absorption_map', 'regularization']
-                                                     if want_epilogues else [])
-        return dict(zip(keys, outs))
+        return _pass_dict(outs, 'absorption')
     return ops.emission_render_fwd(model.packed(), rays_o, rays_d, times, z_vals, reg_radius,
                                    want_epilogues=want_epilogues)
 
@@ -202,12 +189,9 @@ class _MlpOnRays(torch.autograd.Function):
         training = any(ctx.needs_input_grad[5:])
         packed = model.packed()
         out = ops.emission_render_fwd(packed, rays_o, rays_d, times, z_vals, 0.0, want_raw=True, training=training)
-        ctx.training = training
         if training:
             ctx.packed, ctx.params = packed, params
-            ctx.param_meta = [(p.shape, p.device) for p in params]
             ctx.save_for_backward(out['stash'], rays_o, rays_d, times, z_vals)
-        ctx.d_out = packed.d_out
         return out['raw'][..., :packed.d_out] if packed.d_out < 2 else out['raw']
 
     @staticmethod
@@ -219,27 +203,15 @@ class _MlpOnRays(torch.autograd.Function):
         g_raw = g_raw.contiguous().float()
         # bit pattern of max |g_raw|: the scale the fp16 backward arithmetic is normalised with (sunerf_common.h)
         absmax = g_raw.abs().max().reshape(1).view(torch.int32)
-        direct = _grad_targets(ctx.params)
-        if direct is not None:
-            ops.mlp_backward(ctx.packed, g_raw, absmax, stash, direct[0], direct[1], accumulate=True, query=query)
-            _announce(ctx.params)
-            return (None,) * (5 + len(ctx.params))
-        gW = [torch.empty(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_meta[0::2]]
-        gb = [torch.empty(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_meta[1::2]]
-        ops.mlp_backward(ctx.packed, g_raw, absmax, stash, gW, gb, query=query)
-        grads = []
-        for w, b in zip(gW, gb):
-            grads += [w, b]
-        return (None,) * 5 + tuple(grads)
+        return (None,) * 5 + _mlp_param_grads(ctx.params, lambda gW, gb, accumulate: ops.mlp_backward(
+            ctx.packed, g_raw, absmax, stash, gW, gb, accumulate=accumulate, query=query))
 
 
 def mlp_on_rays(model, rays_o, rays_d, times, z_vals) -> torch.Tensor:
     """(N, S, d_output) raw output of ``model`` (a ``NeRF``) at the samples of the rays; goes through autograd when the
     model is trainable and gradients are enabled."""
-    params = []
-    for lin in model.linears():
-        params += [lin.weight, lin.bias]
-    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+    params = _mlp_params(model)
+    if _differentiable(params):
         return _MlpOnRays.apply(model, rays_o, rays_d, times, z_vals, *params)
     raw = ops.emission_render_fwd(model.packed(), rays_o, rays_d, times, z_vals, 0.0, want_raw=True)['raw']
     return raw[..., :model.packed().d_out] if model.packed().d_out < 2 else raw
@@ -313,6 +285,26 @@ def dt_raw2outputs(tables, pixel_factor, inferences, log_abs, vol_c, z_vals, ray
     return {'image': image, 'weights': weights, 'regularizing_quantity': reg_q}
 
 
+def _dt_forward(model, tables, pixel_factor, raw, rays_o, rays_d, z_vals, wavelengths, reg_radius, want_epilogues, la, vol_c):
+    """The DT integral of ``raw`` (N, S, 2), ``model``'s raw output or field, with its base offsets: the forward of every DT
+    pass, with or without autograd.  ``la``: the (7,) stacked absorption scalars."""
+    return ops.dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, tables[0], tables[1], la, vol_c,
+                               model.base_log_density, model.base_log_temperature, pixel_factor, reg_radius,
+                               want_epilogues=want_epilogues)
+
+
+def _dt_backward(ctx, saved, g_image, g_reg):
+    """``ops.dt_integral_bwd`` of a DT pass node whose forward set ``ctx.dt = (tables, pixel_factor, reg_radius,
+    base_log_density, base_log_temperature)`` and saved ``saved = (rays_o, rays_d, z_vals, wavelengths, raw, la, vol_c)``
+    -> (g_raw, g_la, g_vc, absmax)."""
+    rays_o, rays_d, z_vals, wavelengths, raw, la, vol_c = saved
+    tables, pixel_factor, reg_radius, base_d, base_t = ctx.dt
+    if g_image is None:
+        g_image = torch.zeros(z_vals.shape[0], wavelengths.shape[1], dtype=torch.float32, device=z_vals.device)
+    return ops.dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, tables[0], tables[1], la, vol_c, base_d, base_t,
+                               pixel_factor, reg_radius, g_image.contiguous(), g_reg)
+
+
 class _DtPass(torch.autograd.Function):
     """One fused density/temperature pass: render kernel (MLP) -> DT integral kernel.  Differentiable outputs: ``image``
     (N,W) and ``regularization``; gradients for the MLP parameters, the 7 ``log_absortpion`` scalars and
@@ -329,96 +321,57 @@ class _DtPass(torch.autograd.Function):
         # (the DT image goes with rho^2 = exp(2 raw_0): twice the emission image's sensitivity to the raw output)
         mlp = ops.emission_render_fwd(packed, rays_o, rays_d, times, z_vals, 0.0, want_raw=True, training=training,
                                       probe_sensitivity=2.0)
-        out = ops.dt_integral_fwd(mlp['raw'], z_vals, rays_o, rays_d, wavelengths, tables[0], tables[1], la, vol_c,
-                                  model.base_log_density, model.base_log_temperature, pixel_factor, reg_radius,
-                                  want_epilogues=want_epilogues)
+        out = _dt_forward(model, tables, pixel_factor, mlp['raw'], rays_o, rays_d, z_vals, wavelengths, reg_radius,
+                          want_epilogues, la, vol_c)
         if training:
-            ctx.packed, ctx.tables, ctx.pixel_factor, ctx.reg_radius = packed, tables, pixel_factor, reg_radius
-            ctx.base = (model.base_log_density, model.base_log_temperature)
-            ctx.param_meta = [(p.shape, p.device) for p in params[n_la:]]
-            ctx.mlp_params = params[n_la:]
-            ctx.scalar_params = tuple(params[:n_la]) + (vol_c,)
-            ctx.save_for_backward(rays_o, rays_d, z_vals, wavelengths, mlp['raw'], mlp['stash'], la, vol_c.detach(), times)
-        outs = [out['image'], out['weights'], out['reg_q']]
-        non_diff = [out['weights'], out['reg_q']]
-        if want_epilogues:
-            outs += [out['height_map'], out['absorption_map'], out['regularization']]
-            non_diff += [out['height_map'], out['absorption_map']]
-        ctx.mark_non_differentiable(*non_diff)
-        return tuple(outs)
+            ctx.packed, ctx.la_params, ctx.vol_c_param, ctx.mlp_params = packed, params[:n_la], vol_c, params[n_la:]
+            ctx.dt = (tables, pixel_factor, reg_radius, model.base_log_density, model.base_log_temperature)
+            ctx.save_for_backward(rays_o, rays_d, z_vals, wavelengths, mlp['raw'], la, vol_c.detach(), mlp['stash'], times)
+        return _pass_outputs(ctx, out, 'reg_q', want_epilogues)
 
     @staticmethod
     def backward(ctx, g_image, g_weights, g_q, g_hm=None, g_am=None, g_reg=None):
-        rays_o, rays_d, z_vals, wavelengths, raw, stash, la, vol_c, times = ctx.saved_tensors
+        *saved, stash, times = ctx.saved_tensors
+        rays_o, rays_d, z_vals = saved[:3]
         query = ('rays', rays_o, rays_d, times, z_vals)
-        if g_image is None:
-            g_image = torch.zeros(z_vals.shape[0], wavelengths.shape[1], dtype=torch.float32, device=z_vals.device)
-        g_raw, g_la, g_vc, absmax = ops.dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, ctx.tables[0], ctx.tables[1],
-                                                        la, vol_c, ctx.base[0], ctx.base[1], ctx.pixel_factor, ctx.reg_radius,
-                                                        g_image.contiguous(), g_reg)
-        la_slice = _scalar_head_slice(ctx.scalar_params[:-1])
-        vol_c_param = ctx.scalar_params[-1]
-        vc_tag = bucket_of(vol_c_param)
-        if (la_slice is not None and vc_tag is not None and vol_c_param.requires_grad and vol_c_param.grad is not None
-                and vol_c_param.grad.data_ptr() == vc_tag[0].flat_grads[vc_tag[1]:vc_tag[1] + 1].data_ptr()):
-            # the seven absorption scalars sit back to back in the optimiser's flat gradient buffer (the volumetric constant, a
-            # direct parameter of the module, elsewhere in it): two adds instead of eight AccumulateGrad launches
-            la_slice.add_(g_la)
-            vol_c_param.grad.add_(g_vc.reshape(vol_c_param.grad.shape))
-            head = (None,) * (11 + g_la.shape[0])
-        else:
-            head = (None,) * 10 + (g_vc.reshape(()),) + tuple(g_la[i] for i in range(g_la.shape[0]))
-        direct = _grad_targets(ctx.mlp_params)
-        if direct is not None:
-            ops.mlp_backward(ctx.packed, g_raw, absmax, stash, direct[0], direct[1], accumulate=True, query=query)
-            _announce(ctx.mlp_params)
-            return head + (None,) * len(ctx.mlp_params)
-        gW = [torch.empty(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_meta[0::2]]
-        gb = [torch.empty(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_meta[1::2]]
-        ops.mlp_backward(ctx.packed, g_raw, absmax, stash, gW, gb, query=query)
-        grads = []
-        for w, b in zip(gW, gb):
-            grads += [w, b]
-        return head + tuple(grads)
+        g_raw, g_la, g_vc, absmax = _dt_backward(ctx, saved, g_image, g_reg)
+        n_la = len(ctx.la_params)
+        g_vc_out, g_la_out = _scalar_head_grads(ctx.needs_input_grad[10], ctx.needs_input_grad[11:11 + n_la], ctx.vol_c_param,
+                                                ctx.la_params, g_vc, g_la)
+        g_mlp = _mlp_param_grads(ctx.mlp_params, lambda gW, gb, accumulate: ops.mlp_backward(
+            ctx.packed, g_raw, absmax, stash, gW, gb, accumulate=accumulate, query=query))
+        return (None,) * 10 + (g_vc_out,) + g_la_out + g_mlp
+
+
+def _field_raw(model, rays_o, rays_d, z_vals, times):
+    """``model.field_on_rays`` at the samples of the rays; a time-dependent field (``MHDModel``) is handed the rays' times."""
+    if getattr(model, 'time_dependent', False):
+        return model.field_on_rays(rays_o, rays_d, z_vals, times)
+    return model.field_on_rays(rays_o, rays_d, z_vals)
 
 
 def dt_pass(model, tables, pixel_factor, rays_o, rays_d, times, z_vals, wavelengths, reg_radius, want_epilogues):
     """Dict of one DT pass' outputs (image (N,W), weights, regularizing_quantity[, maps, regularization])."""
+    la = [model.log_absortpion[str(w)] for w in ops.AIA_WAVELENGTHS]
     if hasattr(model, 'field_on_rays'):
         # analytic field (SimpleStar) or simulation cube (MHDModel) instead of an MLP: same integral (stellar_model.py,
-        # mhd_model.py, image_render.py:244-269).  A time-dependent field is handed the rays' times.
-        keys = ['image', 'weights', 'regularizing_quantity'] + (['height_map', 'absorption_map', 'regularization']
-                                                                if want_epilogues else [])
-        la = [model.log_absortpion[str(w)] for w in ops.AIA_WAVELENGTHS]
+        # mhd_model.py, image_render.py:244-269)
         sp = star_parameters(model) if hasattr(model, 'stellar_parameters') else []
-        if sp and torch.is_grad_enabled() and any(p.requires_grad for p in la + sp + [model.volumetric_constant]):
-            outs = _StarDtPass.apply(model, tables, pixel_factor, rays_o, rays_d, z_vals, wavelengths, reg_radius, want_epilogues,
-                                     model.volumetric_constant, *la, *sp)
-            return dict(zip(keys, outs))
-        time_dependent = getattr(model, 'time_dependent', False)
-        if (not sp and time_dependent and torch.is_grad_enabled()
-                and any(p.requires_grad for p in la + [model.volumetric_constant])):
-            outs = _FieldDtPass.apply(model, tables, pixel_factor, rays_o, rays_d, times, z_vals, wavelengths, reg_radius,
+        if _differentiable(la + sp + [model.volumetric_constant]):
+            # a star's field through its own node, on the device-side parameters even when they are frozen
+            raw = star_field(model, rays_o, rays_d, z_vals) if sp else _field_raw(model, rays_o, rays_d, z_vals, times)
+            outs = _FieldDtPass.apply(model, tables, pixel_factor, raw, rays_o, rays_d, z_vals, wavelengths, reg_radius,
                                       want_epilogues, model.volumetric_constant, *la)
-            return dict(zip(keys, outs))
+            return _pass_dict(outs, 'regularizing_quantity')
         with torch.no_grad():
-            raw = (model.field_on_rays(rays_o, rays_d, z_vals, times) if time_dependent
-                   else model.field_on_rays(rays_o, rays_d, z_vals))
-            la = torch.stack([p.detach() for p in la])
-            out = ops.dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, tables[0], tables[1], la,
-                                      model.volumetric_constant, model.base_log_density, model.base_log_temperature,
-                                      pixel_factor, reg_radius, want_epilogues=want_epilogues)
+            raw = _field_raw(model, rays_o, rays_d, z_vals, times)
+            out = _dt_forward(model, tables, pixel_factor, raw, rays_o, rays_d, z_vals, wavelengths, reg_radius,
+                              want_epilogues, torch.stack([p.detach() for p in la]), model.volumetric_constant)
         out['regularizing_quantity'] = out.pop('reg_q')
         return out
-    la = [model.log_absortpion[str(w)] for w in ops.AIA_WAVELENGTHS]
-    mlp_params = []
-    for lin in model.linears():
-        mlp_params += [lin.weight, lin.bias]
     outs = _DtPass.apply(model, tables, pixel_factor, rays_o, rays_d, times, z_vals, wavelengths, reg_radius, want_epilogues,
-                         model.volumetric_constant, *la, *mlp_params)
-    keys = ['image', 'weights', 'regularizing_quantity'] + (['height_map', 'absorption_map', 'regularization']
-                                                            if want_epilogues else [])
-    return dict(zip(keys, outs))
+                         model.volumetric_constant, *la, *_mlp_params(model))
+    return _pass_dict(outs, 'regularizing_quantity')
 
 
 # ---- trainable SimpleStar (stellar_model.py:5-102) ------------------------------------------------------------------------
@@ -443,22 +396,11 @@ def _star_param_array(sp):
     return torch.stack([p.detach() for p in sp])
 
 
-def _star_grads(needs, rays_o, rays_d, z_vals, params, t_photosphere, g_raw, sp):
-    """Gradients of the four stellar parameters for autograd: accumulated by the kernel straight into their slots of a flat
-    gradient bucket when they have them (then autograd gets None), else returned per parameter."""
-    if not any(needs):
-        return (None,) * 4
-    slot = _scalar_head_slice(sp)
-    if slot is not None:
-        ops.simple_star_bwd(rays_o, rays_d, z_vals, params, t_photosphere, g_raw, out=slot)
-        return (None,) * 4
-    g = ops.simple_star_bwd(rays_o, rays_d, z_vals, params, t_photosphere, g_raw)
-    return tuple(g[i] if needs[i] else None for i in range(4))
-
-
 class _StarField(torch.autograd.Function):
     """``SimpleStar.forward`` at the samples ``o + d z`` (stellar_model.py:53-102): raw (N, S, 2) = (ln rho, log10 T),
-    differentiable w.r.t. the four stellar parameters (not w.r.t. the rays or z)."""
+    differentiable w.r.t. the four stellar parameters (not w.r.t. the rays or z).  Their gradients are accumulated by the
+    kernel straight into their slots of a flat gradient bucket when they have them (then autograd gets None), else returned
+    per parameter."""
 
     @staticmethod
     def forward(ctx, t_photosphere, rays_o, rays_d, z_vals, *sp):
@@ -466,13 +408,22 @@ class _StarField(torch.autograd.Function):
         raw = ops.simple_star_field_dev(rays_o, rays_d, z_vals, params, t_photosphere)
         ctx.t_photosphere, ctx.sp = t_photosphere, sp
         ctx.save_for_backward(rays_o, rays_d, z_vals, params)
+        ctx.set_materialize_grads(False)
         return raw
 
     @staticmethod
     def backward(ctx, g_raw):
+        needs = ctx.needs_input_grad[4:]
+        if g_raw is None or not any(needs):       # (None: a DT pass without an image / regularization gradient)
+            return (None,) * 8
         rays_o, rays_d, z_vals, params = ctx.saved_tensors
-        return (None,) * 4 + _star_grads(ctx.needs_input_grad[4:], rays_o, rays_d, z_vals, params, ctx.t_photosphere,
-                                         g_raw.contiguous().float(), ctx.sp)
+        g_raw = g_raw.contiguous().float()
+        slot = _scalar_head_slice(ctx.sp)
+        if slot is not None:
+            ops.simple_star_bwd(rays_o, rays_d, z_vals, params, ctx.t_photosphere, g_raw, out=slot)
+            return (None,) * 8
+        g = ops.simple_star_bwd(rays_o, rays_d, z_vals, params, ctx.t_photosphere, g_raw)
+        return (None,) * 4 + tuple(g[i] if needs[i] else None for i in range(4))
 
 
 def star_field(star, rays_o, rays_d, z_vals):
@@ -480,95 +431,35 @@ def star_field(star, rays_o, rays_d, z_vals):
     return _StarField.apply(star.t_photosphere, rays_o, rays_d, z_vals, *star_parameters(star))
 
 
-class _StarDtPass(torch.autograd.Function):
-    """One fused density/temperature pass of a ``SimpleStar``: field kernel -> DT integral kernel, the ``_DtPass`` of the
-    analytic model.  Differentiable outputs: ``image`` (N,W) and ``regularization``; gradients for the 7 ``log_absortpion``
-    scalars, ``volumetric_constant`` and the 4 ``stellar_parameters`` of this star (coarse and fine are separate
-    instances), added straight into an optimiser's flat bucket when the parameters have slots there.  No gradient w.r.t.
-    rays or z (the resampled z is detached in the reference, sampling.py:120)."""
-
-    @staticmethod
-    def forward(ctx, star, tables, pixel_factor, rays_o, rays_d, z_vals, wavelengths, reg_radius, want_epilogues, vol_c, *scalars):
-        n_la = len(ops.AIA_WAVELENGTHS)
-        la = torch.stack([p.detach() for p in scalars[:n_la]])
-        sp = scalars[n_la:]
-        ctx.set_materialize_grads(False)
-        params = _star_param_array(sp)
-        raw = ops.simple_star_field_dev(rays_o, rays_d, z_vals, params, star.t_photosphere)
-        out = ops.dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, tables[0], tables[1], la, vol_c,
-                                  star.base_log_density, star.base_log_temperature, pixel_factor, reg_radius,
-                                  want_epilogues=want_epilogues)
-        ctx.tables, ctx.pixel_factor, ctx.reg_radius = tables, pixel_factor, reg_radius
-        ctx.base = (star.base_log_density, star.base_log_temperature)
-        ctx.t_photosphere = star.t_photosphere
-        ctx.la_params, ctx.sp, ctx.vol_c_param = tuple(scalars[:n_la]), sp, vol_c
-        ctx.save_for_backward(rays_o, rays_d, z_vals, wavelengths, raw, la, vol_c.detach(), params)
-        outs = [out['image'], out['weights'], out['reg_q']]
-        non_diff = [out['weights'], out['reg_q']]
-        if want_epilogues:
-            outs += [out['height_map'], out['absorption_map'], out['regularization']]
-            non_diff += [out['height_map'], out['absorption_map']]
-        ctx.mark_non_differentiable(*non_diff)
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, g_image, g_weights, g_q, g_hm=None, g_am=None, g_reg=None):
-        rays_o, rays_d, z_vals, wavelengths, raw, la, vol_c, params = ctx.saved_tensors
-        n_la = la.shape[0]
-        if g_image is None and g_reg is None:
-            return (None,) * (10 + n_la + 4)
-        if g_image is None:
-            g_image = torch.zeros(z_vals.shape[0], wavelengths.shape[1], dtype=torch.float32, device=z_vals.device)
-        g_raw, g_la, g_vc, _ = ops.dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, ctx.tables[0], ctx.tables[1], la,
-                                                   vol_c, ctx.base[0], ctx.base[1], ctx.pixel_factor, ctx.reg_radius,
-                                                   g_image.contiguous(), g_reg)
-        g_vc_out, g_la_out = _scalar_head_grads(ctx.needs_input_grad[9], ctx.needs_input_grad[10:10 + n_la], ctx.vol_c_param,
-                                                ctx.la_params, g_vc, g_la)
-        g_sp = _star_grads(ctx.needs_input_grad[10 + n_la:], rays_o, rays_d, z_vals, params, ctx.t_photosphere, g_raw, ctx.sp)
-        return (None,) * 9 + (g_vc_out,) + g_la_out + g_sp
-
-
 class _FieldDtPass(torch.autograd.Function):
-    """One fused density/temperature pass of a time-dependent field without parameters of its own (``MHDModel``): field
-    kernel -> DT integral kernel.  Differentiable outputs: ``image`` (N,W) and ``regularization``; gradients for the 7
-    ``log_absortpion`` scalars and ``volumetric_constant`` (added straight into an optimiser's flat bucket when they have slots
-    there, as in ``_StarDtPass``).  No gradient w.r.t. the field's data, the rays or z."""
+    """The DT integral of a field module's ``raw`` (``SimpleStar``, ``MHDModel``: no MLP) as the node of a pass.
+    Differentiable outputs: ``image`` (N,W) and ``regularization``; gradients for ``raw`` (a ``SimpleStar``'s comes from
+    :func:`star_field`, whose node turns it into the stellar parameters' gradients), the 7 ``log_absortpion`` scalars and
+    ``volumetric_constant`` (added straight into an optimiser's flat bucket when they have slots there).  No gradient w.r.t.
+    the rays or z (the resampled z is detached in the reference, sampling.py:120)."""
 
     @staticmethod
-    def forward(ctx, field, tables, pixel_factor, rays_o, rays_d, times, z_vals, wavelengths, reg_radius, want_epilogues, vol_c,
+    def forward(ctx, field, tables, pixel_factor, raw, rays_o, rays_d, z_vals, wavelengths, reg_radius, want_epilogues, vol_c,
                 *la_params):
         la = torch.stack([p.detach() for p in la_params])
         ctx.set_materialize_grads(False)
-        raw = field.field_on_rays(rays_o, rays_d, z_vals, times)
-        out = ops.dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, tables[0], tables[1], la, vol_c,
-                                  field.base_log_density, field.base_log_temperature, pixel_factor, reg_radius,
-                                  want_epilogues=want_epilogues)
-        ctx.tables, ctx.pixel_factor, ctx.reg_radius = tables, pixel_factor, reg_radius
-        ctx.base = (field.base_log_density, field.base_log_temperature)
+        out = _dt_forward(field, tables, pixel_factor, raw, rays_o, rays_d, z_vals, wavelengths, reg_radius,
+                          want_epilogues, la, vol_c)
         ctx.la_params, ctx.vol_c_param = la_params, vol_c
+        ctx.dt = (tables, pixel_factor, reg_radius, field.base_log_density, field.base_log_temperature)
         ctx.save_for_backward(rays_o, rays_d, z_vals, wavelengths, raw, la, vol_c.detach())
-        outs = [out['image'], out['weights'], out['reg_q']]
-        non_diff = [out['weights'], out['reg_q']]
-        if want_epilogues:
-            outs += [out['height_map'], out['absorption_map'], out['regularization']]
-            non_diff += [out['height_map'], out['absorption_map']]
-        ctx.mark_non_differentiable(*non_diff)
-        return tuple(outs)
+        return _pass_outputs(ctx, out, 'reg_q', want_epilogues)
 
     @staticmethod
     def backward(ctx, g_image, g_weights, g_q, g_hm=None, g_am=None, g_reg=None):
-        rays_o, rays_d, z_vals, wavelengths, raw, la, vol_c = ctx.saved_tensors
-        n_la = la.shape[0]
+        n_la = len(ctx.la_params)
         if g_image is None and g_reg is None:
             return (None,) * (11 + n_la)
-        if g_image is None:
-            g_image = torch.zeros(z_vals.shape[0], wavelengths.shape[1], dtype=torch.float32, device=z_vals.device)
-        _, g_la, g_vc, _ = ops.dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, ctx.tables[0], ctx.tables[1], la,
-                                               vol_c, ctx.base[0], ctx.base[1], ctx.pixel_factor, ctx.reg_radius,
-                                               g_image.contiguous(), g_reg)
+        g_raw, g_la, g_vc, _ = _dt_backward(ctx, ctx.saved_tensors, g_image, g_reg)
         g_vc_out, g_la_out = _scalar_head_grads(ctx.needs_input_grad[10], ctx.needs_input_grad[11:11 + n_la], ctx.vol_c_param,
                                                 ctx.la_params, g_vc, g_la)
-        return (None,) * 10 + (g_vc_out,) + g_la_out
+        return (None,) * 3 + (g_raw if ctx.needs_input_grad[3] else None,) + (None,) * 6 + (g_vc_out,) + g_la_out
+
 
 
 # ---- white-light Thomson scattering (thompson.py:17-109) -----------------------------------------------------------------
@@ -600,9 +491,7 @@ class _ThomsonIntegral(torch.autograd.Function):
         raw, z_vals, rays_o, rays_d = ctx.saved_tensors
         if all(g is None for g in (g_b, g_den, g_sun, g_obs, g_w)):
             return (None,) * 6
-        cont = lambda g: None if g is None else g.contiguous()      # noqa: E731
-        g_raw, _ = ops.thomson_integral_bwd(raw, z_vals, rays_o, rays_d, ctx.constants, ctx.kappa, cont(g_b), cont(g_den),
-                                            cont(g_sun), cont(g_obs), cont(g_w))
+        g_raw, _ = ops.thomson_integral_bwd(raw, z_vals, rays_o, rays_d, ctx.constants, ctx.kappa, g_b, g_den, g_sun, g_obs, g_w)
         return (g_raw,) + (None,) * 5
 
 
@@ -632,9 +521,7 @@ class _ThomsonPass(torch.autograd.Function):
                                       probe_sensitivity=LN10)
         out = ops.thomson_integral_fwd(mlp['raw'], z_vals, rays_o, rays_d, constants, LN10)
         if training:
-            ctx.packed, ctx.constants = packed, constants
-            ctx.params = params
-            ctx.param_meta = [(p.shape, p.device) for p in params]
+            ctx.packed, ctx.constants, ctx.params = packed, constants, params
             ctx.save_for_backward(rays_o, rays_d, z_vals, mlp['raw'], mlp['stash'], times)
         ctx.mark_non_differentiable(out['weights'])
         return tuple(out[k] for k in THOMSON_KEYS)
@@ -645,21 +532,9 @@ class _ThomsonPass(torch.autograd.Function):
             return (None,) * (6 + len(ctx.params))
         rays_o, rays_d, z_vals, raw, stash, times = ctx.saved_tensors
         query = ('rays', rays_o, rays_d, times, z_vals)
-        cont = lambda g: None if g is None else g.contiguous()      # noqa: E731
-        g_raw, absmax = ops.thomson_integral_bwd(raw, z_vals, rays_o, rays_d, ctx.constants, LN10, cont(g_b), cont(g_den),
-                                                 cont(g_sun), cont(g_obs))
-        direct = _grad_targets(ctx.params)
-        if direct is not None:
-            ops.mlp_backward(ctx.packed, g_raw, absmax, stash, direct[0], direct[1], accumulate=True, query=query)
-            _announce(ctx.params)
-            return (None,) * (6 + len(ctx.params))
-        gW = [torch.empty(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_meta[0::2]]
-        gb = [torch.empty(shape, dtype=torch.float32, device=dev) for shape, dev in ctx.param_meta[1::2]]
-        ops.mlp_backward(ctx.packed, g_raw, absmax, stash, gW, gb, query=query)
-        grads = []
-        for w, b in zip(gW, gb):
-            grads += [w, b]
-        return (None,) * 6 + tuple(grads)
+        g_raw, absmax = ops.thomson_integral_bwd(raw, z_vals, rays_o, rays_d, ctx.constants, LN10, g_b, g_den, g_sun, g_obs)
+        return (None,) * 6 + _mlp_param_grads(ctx.params, lambda gW, gb, accumulate: ops.mlp_backward(
+            ctx.packed, g_raw, absmax, stash, gW, gb, accumulate=accumulate, query=query))
 
 
 def thomson_pass(model, constants, rays_o, rays_d, times, z_vals):
@@ -668,13 +543,10 @@ def thomson_pass(model, constants, rays_o, rays_d, times, z_vals):
     differentiable w.r.t. whatever parameters its ``field_on_rays`` carries gradients for."""
     constants = tuple(constants)
     if hasattr(model, 'field_on_rays'):
-        raw = (model.field_on_rays(rays_o, rays_d, z_vals, times) if getattr(model, 'time_dependent', False)
-               else model.field_on_rays(rays_o, rays_d, z_vals))
+        raw = _field_raw(model, rays_o, rays_d, z_vals, times)
         return thomson_raw2outputs(raw, z_vals, rays_o, rays_d, constants, 1.0)
-    params = []
-    for lin in model.linears():
-        params += [lin.weight, lin.bias]
-    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+    params = _mlp_params(model)
+    if _differentiable(params):
         return _thomson_dict(_ThomsonPass.apply(model, constants, rays_o, rays_d, times, z_vals, *params))
     raw = ops.emission_render_fwd(model.packed(), rays_o, rays_d, times, z_vals, 0.0, want_raw=True,
                                   probe_sensitivity=LN10)['raw']

@@ -143,6 +143,15 @@ def _stream(device) -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _workspace(cache, dev, nbytes: int) -> torch.Tensor:
+    """The byte workspace ``cache`` keeps for the current stream of ``dev``, grown to at least ``nbytes``."""
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = cache.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return ws
+
+
 class PackedMLP:
     """fp16 hi/lo A-fragment image of one NeRF MLP (see csrc/sunerf_common.h).  Re-pack after every
     parameter update (``repack``)."""
@@ -382,12 +391,7 @@ def emission_render_fwd(packed: PackedMLP, rays_o, rays_d, times, z_vals, reg_ra
         raise NotImplementedError(f'training with d_filter={packed.d_filter} is not implemented (inference only); '
                                   f'trainable widths: {TRAINABLE_D_FILTER}')
     ws_bytes = lib.sunerf_render_workspace_bytes(packed.d_filter)
-    ws = None
-    if ws_bytes:
-        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-        ws = _workspaces.get(key)
-        if ws is None or ws.numel() < ws_bytes:
-            ws = _workspaces[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(_workspaces, dev, ws_bytes) if ws_bytes else None
     raw = torch.empty(n, s, 2, **f32) if want_raw else None
     stash, fmt = None, STASH_FP16
     if _stash_wanted(training):
@@ -436,12 +440,7 @@ def mlp_points_fwd(packed: PackedMLP, points: torch.Tensor, training: bool = Fal
     if training and packed.d_filter not in TRAINABLE_D_FILTER:
         raise NotImplementedError(f'training with d_filter={packed.d_filter} is not implemented (inference only)')
     ws_bytes = lib.sunerf_render_workspace_bytes(packed.d_filter)
-    ws = None
-    if ws_bytes:
-        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-        ws = _workspaces.get(key)
-        if ws is None or ws.numel() < ws_bytes:
-            ws = _workspaces[key] = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(_workspaces, dev, ws_bytes) if ws_bytes else None
     raw = torch.empty(m_pad, 2, dtype=torch.float32, device=dev)
     stash, fmt = None, STASH_FP16
     if _stash_wanted(training):
@@ -772,10 +771,7 @@ def _mlp_backward_exact(packed: PackedMLP, g_raw, query, grad_weights, grad_bias
         nbytes = lib.sunerf_mlp_backward_exact_chunked_workspace_bytes(packed.d_filter, nl)
     else:
         nbytes = lib.sunerf_mlp_backward_exact_workspace_bytes(n * s, packed.d_filter, nl)
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _exact_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _exact_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(_exact_ws, dev, nbytes)
     W = (ctypes.c_void_p * nl)(*[w.data_ptr() for w in ws_])
     B = (ctypes.c_void_p * nl)(*[b.data_ptr() for b in bs_])
     GW = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in grad_weights])
@@ -935,11 +931,10 @@ def simple_star_field(rays_o, rays_d, z_vals, rho_0: float, h0: float, T0: float
     return raw
 
 
-def dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_resp, log_abs, vol_c, base_log_density,
-                    base_log_temperature, pixel_intensity_factor, reg_radius, g_image, g_reg):
-    """-> (g_raw (N,S,2), g_log_abs (7,), g_vol_c (1,), absmax).  The two scalar-head gradients are adjacent views of one buffer
-    (``g_log_abs.storage`` holds [7 channels, vol_c, absmax]): one clear in the entry point, one add into a flat gradient bucket."""
-    lib = _l.load()
+def _dt_integral_bwd(entry, raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_resp, log_abs, vol_c,
+                     base_log_density, base_log_temperature, pixel_intensity_factor, reg_radius, g_image, per_sample):
+    """Launches DT integral backward ``entry`` with the (N,S) output gradients ``per_sample`` ((name, tensor or None) pairs,
+    in the entry point's order) -> (g_raw, g_log_abs, g_vol_c, absmax)."""
     n, s = z_vals.shape
     dev = z_vals.device
     w = wavelengths.shape[1]
@@ -948,17 +943,25 @@ def dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_
     wavelengths = _dev(wavelengths.to(torch.float32), 'wavelengths', (n, w))
     log_abs = _dev(log_abs.detach(), 'log_abs', (7,)); vol_c = _dev(vol_c.detach().reshape(1), 'vol_c', (1,))
     g_image = _dev(g_image, 'g_image', (n, w))
-    if g_reg is not None:
-        g_reg = _dev(g_reg, 'g_reg', (n, s))
+    per_sample = [None if g is None else _dev(g, name, (n, s)) for name, g in per_sample]
     f32 = dict(dtype=torch.float32, device=dev)
     g_raw = torch.empty(n, s, 2, **f32)
     small = torch.empty(9, **f32)
     g_la, g_vc, absmax = small[:7], small[7:8], small[8:9].view(torch.int32)
-    _l.call(dev, 'sunerf_dt_integral_bwd', _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(wavelengths), w,
+    _l.call(dev, entry, _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(wavelengths), w,
             _ptr(table_logt), _ptr(table_resp), _ptr(log_abs), _ptr(vol_c), float(base_log_density),
             float(base_log_temperature), float(pixel_intensity_factor), float(reg_radius), n, s, _ptr(g_image),
-            _ptr(g_reg), _ptr(g_raw), _ptr(g_la), _ptr(g_vc), _ptr(absmax), _stream(dev))
+            *[_ptr(g) for g in per_sample], _ptr(g_raw), _ptr(g_la), _ptr(g_vc), _ptr(absmax), _stream(dev))
     return g_raw, g_la, g_vc, absmax
+
+
+def dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_resp, log_abs, vol_c, base_log_density,
+                    base_log_temperature, pixel_intensity_factor, reg_radius, g_image, g_reg):
+    """-> (g_raw (N,S,2), g_log_abs (7,), g_vol_c (1,), absmax).  The two scalar-head gradients are adjacent views of one buffer
+    (``g_log_abs.storage`` holds [7 channels, vol_c, absmax]): one clear in the entry point, one add into a flat gradient bucket."""
+    return _dt_integral_bwd('sunerf_dt_integral_bwd', raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_resp, log_abs,
+                            vol_c, base_log_density, base_log_temperature, pixel_intensity_factor, reg_radius, g_image,
+                            [('g_reg', g_reg)])
 
 
 def dt_integral_bwd_full(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_resp, log_abs, vol_c, base_log_density,
@@ -966,26 +969,9 @@ def dt_integral_bwd_full(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, t
     """:func:`dt_integral_bwd` for gradients w.r.t. all three outputs of raw2outputs (density_temperature.py:267-271): also
     ``g_weights`` / ``g_reg_q`` (N,S) (either may be None) -> (g_raw (N,S,2), g_log_abs (7,), g_vol_c (1,), absmax), the two
     scalar-head gradients adjacent in one buffer as there."""
-    n, s = z_vals.shape
-    dev = z_vals.device
-    w = wavelengths.shape[1]
-    raw = _dev(raw, 'raw', (n, s, 2)); z_vals = _dev(z_vals, 'z_vals', (n, s))
-    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3))
-    wavelengths = _dev(wavelengths.to(torch.float32), 'wavelengths', (n, w))
-    log_abs = _dev(log_abs.detach(), 'log_abs', (7,)); vol_c = _dev(vol_c.detach().reshape(1), 'vol_c', (1,))
-    g_image = _dev(g_image, 'g_image', (n, w))
-    g_reg = None if g_reg is None else _dev(g_reg, 'g_reg', (n, s))
-    g_weights = None if g_weights is None else _dev(g_weights, 'g_weights', (n, s))
-    g_reg_q = None if g_reg_q is None else _dev(g_reg_q, 'g_reg_q', (n, s))
-    f32 = dict(dtype=torch.float32, device=dev)
-    g_raw = torch.empty(n, s, 2, **f32)
-    small = torch.empty(9, **f32)
-    g_la, g_vc, absmax = small[:7], small[7:8], small[8:9].view(torch.int32)
-    _l.call(dev, 'sunerf_dt_integral_bwd_full', _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(wavelengths), w,
-            _ptr(table_logt), _ptr(table_resp), _ptr(log_abs), _ptr(vol_c), float(base_log_density),
-            float(base_log_temperature), float(pixel_intensity_factor), float(reg_radius), n, s, _ptr(g_image),
-            _ptr(g_reg), _ptr(g_weights), _ptr(g_reg_q), _ptr(g_raw), _ptr(g_la), _ptr(g_vc), _ptr(absmax), _stream(dev))
-    return g_raw, g_la, g_vc, absmax
+    return _dt_integral_bwd('sunerf_dt_integral_bwd_full', raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_resp,
+                            log_abs, vol_c, base_log_density, base_log_temperature, pixel_intensity_factor, reg_radius, g_image,
+                            [('g_reg', g_reg), ('g_weights', g_weights), ('g_reg_q', g_reg_q)])
 
 
 def simple_star_field_dev(rays_o, rays_d, z_vals, params, t_photosphere: float):

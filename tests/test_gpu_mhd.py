@@ -189,7 +189,10 @@ def test_two_pass_render_matches_oracle(tmp_path):
     assert (got['regularization'].cpu() - reg).abs().max().item() / reg.abs().max().item() < 2e-4
 
 
-def test_absorption_and_volumetric_gradients_match_oracle_autograd(tmp_path):
+@pytest.mark.parametrize('flat_bucket', [False, True])
+def test_absorption_and_volumetric_gradients_match_oracle_autograd(tmp_path, flat_bucket):
+    """``flat_bucket``: with a ``ClipAdam`` over the module's parameters (gradients are views of one flat buffer) the DT
+    backward adds the seven absorption scalars' and the volumetric constant's gradients straight into that buffer."""
     root, reader, frames = _simulation(tmp_path)
     mod, logte, resp, pixel_factor = _renderer(root, reader, 24, 24)
     with torch.no_grad():
@@ -208,11 +211,20 @@ def test_absorption_and_volumetric_gradients_match_oracle_autograd(tmp_path):
     mse = torch.nn.functional.mse_loss
     ref_loss = mse(want['coarse_image'], target) + mse(want['fine_image'], target) + want['regularization'].mean()
     ref_loss.backward()
+    if flat_bucket:
+        from sunerf_hip.train import ClipAdam, bucket_of
+        optimizer = ClipAdam(mod.parameters())       # (held: a parameter's bucket tag refers to its optimiser weakly)
+        optimizer.zero_grad()
+        assert all(bucket_of(p) is not None for p in mod.parameters())
     got = mod(o.cuda(), d.cuda(), t.cuda(), wl.cuda())
     tc = target.cuda()
     loss = mse(got['coarse_image'], tc) + mse(got['fine_image'], tc) + got['regularization'].mean()
     assert abs(loss.item() - ref_loss.item()) < 2e-4 * abs(ref_loss.item()), (loss.item(), ref_loss.item())
     loss.backward()
+    if flat_bucket:        # every .grad is still its slot of the bucket: nothing replaced a view
+        for name, p in mod.named_parameters():
+            owner, off, k = bucket_of(p)
+            assert p.grad.data_ptr() == owner.flat_grads[off:off + k].data_ptr(), name
     for name, p in mod.named_parameters():
         ref_g = leaves[name].grad
         assert p.grad is not None and ref_g is not None, name
