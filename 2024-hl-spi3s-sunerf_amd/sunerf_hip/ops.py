@@ -544,20 +544,33 @@ def emission_integral_fwd(raw, z_vals, rays_d):
     return image, weights, absorption
 
 
-def emission_integral_bwd(raw, z_vals, rays_d, g_image=None, g_weights=None, g_absorption=None):
-    """d / d raw of :func:`emission_integral_fwd` for gradients w.r.t. any of its three outputs -> g_raw (N,S,2)."""
+def emission_integral_bwd(raw, z_vals, rays_d, g_image=None, g_weights=None, g_absorption=None, *, rays_o=None, g_reg=None,
+                          g_reg_const: float = 0.0, reg_radius: float = 0.0, return_absmax: bool = False):
+    """d / d raw of :func:`emission_integral_fwd` for gradients w.r.t. any of its three outputs -> g_raw (N,S,2).
+
+    The keyword-only arguments reach the rest of ``sunerf_emission_integral_bwd``: the gradient w.r.t. the 'regularization'
+    epilogue relu(|o + d z| - reg_radius) (1 - absorption), as the (N,S) tensor ``g_reg`` or, when that is None, the constant
+    ``g_reg_const`` (both need ``rays_o``).  ``return_absmax=True`` returns (g_raw, absmax): the 4-byte word with the bit pattern
+    of max |g_raw| (int32, view it as float32) that selects the fp16 gradient scale of the backward kernels after it."""
     n, s = z_vals.shape
     dev = z_vals.device
     raw = _dev(raw, 'raw', (n, s, 2)); z_vals = _dev(z_vals, 'z_vals', (n, s)); rays_d = _dev(rays_d, 'rays_d', (n, 3))
     g_image = torch.zeros(n, dtype=torch.float32, device=dev) if g_image is None else _dev(g_image.reshape(-1), 'g_image', (n,))
     g_weights = None if g_weights is None else _dev(g_weights, 'g_weights', (n, s))
     g_absorption = None if g_absorption is None else _dev(g_absorption, 'g_absorption', (n, s))
+    g_reg = None if g_reg is None else _dev(g_reg, 'g_reg', (n, s))
+    if rays_o is None:
+        if g_reg is not None or g_reg_const != 0.0:
+            raise ValueError('a gradient w.r.t. the regularization output needs rays_o')
+        rays_o = rays_d           # (rays_o only enters through the regularization term: not read when g_reg = 0)
+    else:
+        rays_o = _dev(rays_o, 'rays_o', (n, 3))
     g_raw = torch.empty(n, s, 2, dtype=torch.float32, device=dev)
     absmax = torch.empty(1, dtype=torch.int32, device=dev)
-    # (rays_o only enters through the regularization term, which is not an output of raw2outputs: g_reg = 0)
-    _l.call(dev, 'sunerf_emission_integral_bwd', _ptr(raw), _ptr(z_vals), _ptr(rays_d), _ptr(rays_d), _ptr(g_image), None,
-            _ptr(g_weights), _ptr(g_absorption), 0.0, 0.0, n, s, _ptr(g_raw), _ptr(absmax), _stream(dev))
-    return g_raw
+    _l.call(dev, 'sunerf_emission_integral_bwd', _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(g_image), _ptr(g_reg),
+            _ptr(g_weights), _ptr(g_absorption), float(g_reg_const), float(reg_radius), n, s, _ptr(g_raw), _ptr(absmax),
+            _stream(dev))
+    return (g_raw, absmax) if return_absmax else g_raw
 
 
 # ---- which backward runs (DESIGN.md section 5.4) -------------------------------------------------------------------------

@@ -245,9 +245,21 @@ def render_pass_f64(params: Params, rays_o, rays_d, times, z_vals, reg_radius: f
     query = torch.cat([pts, times[:, None].repeat(1, pts.shape[1], 1)], -1).double()
     p64 = [(W.double(), b.double()) for W, b in params]
     raw = mlp_forward(p64, query.view(-1, 4)).reshape(*query.shape[:-1], -1)
-    out = emission_integral(raw, z_vals.double(), rays_d.double())
+    out = emission_outputs(raw, z_vals, rays_o, rays_d, reg_radius)
     out['raw'] = raw
-    out['points'] = pts.double()
+    return out
+
+
+def emission_outputs(raw, z_vals, rays_o, rays_d, reg_radius: float) -> Dict[str, torch.Tensor]:
+    """raw (N, S, 2) -> the emission integral (:func:`emission_integral`) and the single-pass epilogues of base_tracing.py:99-110,
+    computed in the dtype of ``raw`` (float32: the fp32 oracle's own expressions; float64: the yardstick of
+    :func:`render_pass_f64`).  The sample points are formed in fp32 as :func:`render_pass` forms them, then promoted.
+    Returns the dict of :func:`emission_integral` plus ``points`` (N, S, 3), ``height_map`` (N,), ``absorption_map`` (N,) and
+    ``regularization`` (N, S) = relu(|p| - reg_radius) (1 - absorption) (D2 resolved); differentiable w.r.t. ``raw``."""
+    dt = raw.dtype
+    pts = points_on_rays(rays_o.float(), rays_d.float(), z_vals.float())
+    out = emission_integral(raw, z_vals.to(dt), rays_d.to(dt))
+    out['points'] = pts.to(dt)
     dist_pts = out['points'].pow(2).sum(-1).pow(0.5)
     out['height_map'] = (out['weights'] * dist_pts).sum(-1)
     out['absorption_map'] = (1 - out['regularizing_quantity']).sum(-1)
