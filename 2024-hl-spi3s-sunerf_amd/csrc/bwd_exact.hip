@@ -23,6 +23,7 @@ namespace {
 constexpr int EPI_SINCOS = 0;   // out0 = sin(acc + bias), out1 = cos(acc + bias)           (forward layer)
 constexpr int EPI_MULC = 1;     // out0 = acc * mul                                           (data gradient: dZ = dH * cos)
 constexpr int EPI_PART = 2;     // out0[slice][m][n] = acc over this block's slice of K       (weight gradient partial sums)
+constexpr int EPI_STORE = 3;    // out0 = acc                                                 (encoder-feature gradient, tiled GEMM only)
 
 struct GemmArgs {
   const float* A; long a_sm, a_sk;     // A(m, k) = A[m * a_sm + k * a_sk]
@@ -404,6 +405,8 @@ __global__ __launch_bounds__(256) void gemm_tiled_kernel(TiledArgs a) {
           a.out1[o] = sc.y;
         } else if (EPI == EPI_MULC) {
           a.out0[o] = v * a.mul[o];
+        } else if (EPI == EPI_STORE) {
+          a.out0[o] = v;
         } else {
           a.out0[(long)blockIdx.z * a.M * a.ldo + o] = v;
         }
@@ -517,30 +520,108 @@ int launch_tiled(const TiledArgs& a, int slices, hipStream_t st) {
 
 }  // namespace
 
-extern "C" size_t sunerf_mlp_backward_exact_chunked_workspace_bytes(int d_filter, int n_linear) {
-  if (d_filter < 1 || d_filter > 512 || n_linear < 2 || n_linear > SUNERF_MAX_LAYERS) return 0;
-  return ChunkedLayout(d_filter, n_linear).total;
+// ---- input gradients: the last link from dZ_0 to the query points, rays and times ------------------------------------------------
+// After the chunk loop's data-gradient chain has reached dZ_0 (the fp32 gradient of the first layer's pre-activation):
+//   g_enc[s][j] = sum_o dZ_0[s][o] W_0[o][j]                 (84 encoder columns; the tiled GEMM, fp32-input MFMA)
+//   g_x[s][c]   = g_enc[s][c] + sum_k f_k (g_enc[s][4+4k+c] cos(x_c f_k) - g_enc[s][44+4k+c] sin(x_c f_k)),  f_k = 2^k / 2
+// (the derivative of PositionalEncoding, model.py:123-132, from the sin / cos already in `enc`; a model without encoding or of a
+// padded width has zeros in the padded columns of W_0, so the same formula is exact for it), then in ray mode (x = o + d z, t)
+//   g_o[r] = sum_s g_xyz,  g_d[r] = sum_s z_s g_xyz,  g_z[r][s] = d_r . g_xyz,  g_t[r] = sum_s g_t
+// in fp64, each ray's samples in sample order; a ray that straddles a chunk seam carries its partial sums into the next chunk
+// (two carry slots, alternating by chunk parity: the first ray of a chunk reads one while its last ray writes the other).
+namespace {
+
+struct InputGrads {
+  float* points;                           // points mode: (N*S, 4)
+  float* rays_o; float* rays_d;            // ray mode: (N, 3) each, or NULL
+  float* times; float* z;                  // ray mode: (N) and (N, S), or NULL
+};
+
+constexpr int RAY_CARRY = 8;               // doubles per carry slot: o 3, d 3, t 1 (+1 pad)
+
+struct InputGradLayout {
+  ChunkedLayout base;
+  size_t genc, gx, carry, total;           // byte offsets: genc [C][84] floats, gx [C][4] doubles, carry [2][RAY_CARRY] doubles
+  InputGradLayout(int D, int n_linear) : base(D, n_linear) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    size_t off = base.total;
+    genc = off; off += up((size_t)base.C * SUNERF_ENC_DIM * sizeof(float));
+    gx = off; off += up((size_t)base.C * 4 * sizeof(double));
+    carry = off; off += up(2 * RAY_CARRY * sizeof(double));
+    total = off;
+  }
+};
+
+// g_enc + enc -> g_x of samples [first, first + count): written to grad_points (points mode) or, in ray mode, kept in fp64 in `gx`
+// for the per-ray sums, with g_z = d . g_xyz written at once
+__global__ void encoding_grad_kernel(const float* genc, const float* enc, long first, long count, int S, const float* rays_d,
+                                     float* grad_points, double* gx, float* grad_z) {
+  const long local = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (local >= count) return;
+  const long i = first + local;
+  const float* g = genc + local * SUNERF_ENC_DIM;
+  const float* e = enc + local * SUNERF_ENC_DIM;
+  double v[4];
+  for (int c = 0; c < 4; ++c) {
+    double s = (double)g[c];
+    for (int k = 0; k < 10; ++k) {
+      const double f = k == 0 ? 0.5 : (double)(1 << (k - 1));
+      s += f * ((double)g[4 + 4 * k + c] * (double)e[44 + 4 * k + c] - (double)g[44 + 4 * k + c] * (double)e[4 + 4 * k + c]);
+    }
+    v[c] = s;
+  }
+  if (grad_points) {
+    for (int c = 0; c < 4; ++c) grad_points[i * 4 + c] = (float)v[c];
+    return;
+  }
+  for (int c = 0; c < 4; ++c) gx[local * 4 + c] = v[c];
+  if (grad_z) {
+    const float* d = rays_d + (i / S) * 3;
+    grad_z[i] = (float)((double)d[0] * v[0] + (double)d[1] * v[1] + (double)d[2] * v[2]);
+  }
 }
 
-extern "C" int sunerf_mlp_backward_exact_chunked(const float* const* weights_host, const float* const* biases_host, int n_linear,
-                                                 int d_filter, int d_out, const float* rays_o, const float* rays_d,
-                                                 const float* times, const float* z_vals, const float* points, int64_t n_rays,
-                                                 int n_samples, const float* g_raw, void* workspace, size_t workspace_bytes,
-                                                 float* const* grad_weights_host, float* const* grad_biases_host, int accumulate,
-                                                 void* stream) {
-  if (!weights_host || !biases_host || !grad_weights_host || !grad_biases_host || !g_raw || !workspace) return SUNERF_E_BADARG;
-  if (n_rays <= 0 || n_samples < 1 || d_filter < 1 || d_out < 1) return SUNERF_E_BADARG;
-  if (n_linear < 2 || n_linear > SUNERF_MAX_LAYERS || d_filter > 512 || d_out > CHUNKED_MAX_OUT) return SUNERF_E_UNSUPPORTED;
-  if (!points && (!rays_o || !rays_d || !times || !z_vals)) return SUNERF_E_BADARG;
-  for (int i = 0; i < n_linear; ++i)
-    if (!weights_host[i] || !biases_host[i] || !grad_weights_host[i] || !grad_biases_host[i]) return SUNERF_E_BADARG;
-  if (n_rays > ((int64_t)1 << 40) / n_samples) return SUNERF_E_UNSUPPORTED;      // 64-bit sample indices throughout
-  const int64_t N = n_rays * n_samples;
-  const int D = d_filter, n_act = n_linear - 1;
-  const ChunkedLayout L(D, n_linear);
-  if (workspace_bytes < L.total) return SUNERF_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
+// one thread per ray touching samples [first, first + count): its sums over the chunk's share of its samples, in sample order,
+// started from the carry of the previous chunk if the ray began there, handed to the next chunk if it goes on past this one
+__global__ void ray_sums_kernel(const double* gx, long first, long count, int S, const float* z_vals, float* grad_o, float* grad_d,
+                                float* grad_t, const double* carry_in, double* carry_out) {
+  const long r = first / S + (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long last = first + count;
+  if (r > (last - 1) / S) return;
+  const long s0 = r * S > first ? r * S : first, s1 = (r + 1) * S < last ? (r + 1) * S : last;
+  double o[3] = {0.0, 0.0, 0.0}, d[3] = {0.0, 0.0, 0.0}, t = 0.0;
+  if (r * S < first) {
+    for (int c = 0; c < 3; ++c) { o[c] = carry_in[c]; d[c] = carry_in[3 + c]; }
+    t = carry_in[6];
+  }
+  for (long i = s0; i < s1; ++i) {
+    const double* g = gx + (i - first) * 4;
+    const double z = (double)z_vals[i];
+    for (int c = 0; c < 3; ++c) { o[c] += g[c]; d[c] += z * g[c]; }
+    t += g[3];
+  }
+  if ((r + 1) * S > last) {
+    for (int c = 0; c < 3; ++c) { carry_out[c] = o[c]; carry_out[3 + c] = d[c]; }
+    carry_out[6] = t;
+    return;
+  }
+  for (int c = 0; c < 3; ++c) {
+    if (grad_o) grad_o[r * 3 + c] = (float)o[c];
+    if (grad_d) grad_d[r * 3 + c] = (float)d[c];
+  }
+  if (grad_t) grad_t[r] = (float)t;
+}
+
+// The chunk loop of both entry points below.  Parameter gradients when grad_weights_host != NULL (the fp64 accumulators and the
+// final cast), input gradients when `in` != NULL; the launches of the parameter-gradient part are the same either way, so its
+// results are bit-identical with and without input gradients.
+int chunked_backward(const float* const* weights_host, const float* const* biases_host, int n_linear, int D, int d_out,
+                     const float* rays_o, const float* rays_d, const float* times, const float* z_vals, const float* points,
+                     int64_t N, int n_samples, const float* g_raw, char* ws, const ChunkedLayout& L,
+                     float* const* grad_weights_host, float* const* grad_biases_host, int accumulate, const InputGrads* in,
+                     const InputGradLayout* IL, hipStream_t st) {
+  const int n_act = n_linear - 1;
+  const bool params = grad_weights_host != nullptr;
   float* enc = (float*)(ws + L.enc);
   auto H = [&](int l) { return (float*)(ws + L.act) + (size_t)(2 * l) * L.per; };
   auto Cs = [&](int l) { return (float*)(ws + L.act) + (size_t)(2 * l + 1) * L.per; };
@@ -552,7 +633,7 @@ extern "C" int sunerf_mlp_backward_exact_chunked(const float* const* weights_hos
   long off = 0, max_count = 0;
   for (int i = 0; i < n_linear; ++i) {
     const int M = i == n_linear - 1 ? d_out : D, K = i == 0 ? SUNERF_ENC_DIM : D;
-    ca.gw[i] = grad_weights_host[i]; ca.gb[i] = grad_biases_host[i];
+    ca.gw[i] = params ? grad_weights_host[i] : nullptr; ca.gb[i] = params ? grad_biases_host[i] : nullptr;
     ca.w_off[i] = off; ca.w_count[i] = (long)M * K; off += (long)M * K;
     ca.b_off[i] = off; ca.b_count[i] = M; off += M;
     max_count = (long)M * K + M > max_count ? (long)M * K + M : max_count;
@@ -560,9 +641,10 @@ extern "C" int sunerf_mlp_backward_exact_chunked(const float* const* weights_hos
   ca.acc = acc; ca.accumulate = accumulate;
   int rc;
   SUNERF_CLEAR_ERROR();
-  if (hipMemsetAsync(acc, 0, (size_t)off * sizeof(double), st) != hipSuccess) return (int)hipGetLastError();
+  if (params && hipMemsetAsync(acc, 0, (size_t)off * sizeof(double), st) != hipSuccess) return (int)hipGetLastError();
 
-  for (int64_t c0 = 0; c0 < N; c0 += L.C) {
+  int64_t chunk = 0;
+  for (int64_t c0 = 0; c0 < N; c0 += L.C, ++chunk) {
     const int Cn = (int)(N - c0 < L.C ? N - c0 : L.C);
     hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((Cn + 255) / 256)), dim3(256), 0, st, rays_o, rays_d, times, z_vals, points,
                        (long)c0, (long)Cn, n_samples, enc);
@@ -580,24 +662,26 @@ extern "C" int sunerf_mlp_backward_exact_chunked(const float* const* weights_hos
     const float* dz = g_raw + c0 * d_out;
     int dz_cols = d_out, flip = 0;
     for (int i = n_linear - 1; i >= 0; --i) {
-      const int cols = i == 0 ? SUNERF_ENC_DIM : D;         // fan-in of layer i
-      const float* X = i == 0 ? enc : H(i - 1);
-      // dW_i[o][j] partials = sum over a slice of the chunk's samples of dZ_i[s][o] X[s][j]
-      const int slices = wgrad_slices(dz_cols, cols, Cn);
-      TiledArgs w = {};
-      w.A = dz; w.lda = dz_cols;
-      w.B = X; w.ldb = cols;
-      w.M = dz_cols; w.N = cols; w.K = Cn; w.k_per = wgrad_k_per(Cn, slices);
-      w.out0 = wpart; w.ldo = cols;
-      if ((rc = launch_tiled<false, false, EPI_PART>(w, slices, st))) return rc;
-      const int blocks = (Cn + COLSUM_ROWS - 1) / COLSUM_ROWS;
-      hipLaunchKernelGGL(colsum_part_kernel, dim3((unsigned)((dz_cols + 63) / 64), (unsigned)blocks), dim3(256), 0, st, dz, Cn, dz_cols,
-                         bpart);
-      SUNERF_CHECK_LAUNCH();
-      const long count = (long)dz_cols * cols;
-      hipLaunchKernelGGL(accumulate_layer_kernel, dim3((unsigned)((count + dz_cols + 255) / 256)), dim3(256), 0, st, wpart, slices,
-                         count, acc + ca.w_off[i], bpart, blocks, dz_cols, acc + ca.b_off[i]);
-      SUNERF_CHECK_LAUNCH();
+      if (params) {
+        const int cols = i == 0 ? SUNERF_ENC_DIM : D;         // fan-in of layer i
+        const float* X = i == 0 ? enc : H(i - 1);
+        // dW_i[o][j] partials = sum over a slice of the chunk's samples of dZ_i[s][o] X[s][j]
+        const int slices = wgrad_slices(dz_cols, cols, Cn);
+        TiledArgs w = {};
+        w.A = dz; w.lda = dz_cols;
+        w.B = X; w.ldb = cols;
+        w.M = dz_cols; w.N = cols; w.K = Cn; w.k_per = wgrad_k_per(Cn, slices);
+        w.out0 = wpart; w.ldo = cols;
+        if ((rc = launch_tiled<false, false, EPI_PART>(w, slices, st))) return rc;
+        const int blocks = (Cn + COLSUM_ROWS - 1) / COLSUM_ROWS;
+        hipLaunchKernelGGL(colsum_part_kernel, dim3((unsigned)((dz_cols + 63) / 64), (unsigned)blocks), dim3(256), 0, st, dz, Cn,
+                           dz_cols, bpart);
+        SUNERF_CHECK_LAUNCH();
+        const long count = (long)dz_cols * cols;
+        hipLaunchKernelGGL(accumulate_layer_kernel, dim3((unsigned)((count + dz_cols + 255) / 256)), dim3(256), 0, st, wpart, slices,
+                           count, acc + ca.w_off[i], bpart, blocks, dz_cols, acc + ca.b_off[i]);
+        SUNERF_CHECK_LAUNCH();
+      }
       if (i == 0) break;
       // dZ_{i-1}[s][j] = (sum_o dZ_i[s][o] W_i[o][j]) cos(Z_{i-1})[s][j]
       TiledArgs d = {};
@@ -608,8 +692,96 @@ extern "C" int sunerf_mlp_backward_exact_chunked(const float* const* weights_hos
       if ((rc = launch_tiled<true, false, EPI_MULC>(d, 1, st))) return rc;
       dz = dzb[flip]; dz_cols = D; flip ^= 1;
     }
+    if (!in) continue;
+    // dz is dZ_0 now: g_enc = dZ_0 W_0 (Cn x 84), then the encoder's derivative and, in ray mode, the per-ray sums
+    float* genc = (float*)(ws + IL->genc);
+    double* gx = (double*)(ws + IL->gx);
+    double* carry = (double*)(ws + IL->carry);
+    TiledArgs e = {};
+    e.A = dz; e.lda = dz_cols;
+    e.B = weights_host[0]; e.ldb = SUNERF_ENC_DIM;
+    e.M = Cn; e.N = SUNERF_ENC_DIM; e.K = D;
+    e.out0 = genc; e.ldo = SUNERF_ENC_DIM;
+    if ((rc = launch_tiled<true, false, EPI_STORE>(e, 1, st))) return rc;
+    hipLaunchKernelGGL(encoding_grad_kernel, dim3((unsigned)((Cn + 255) / 256)), dim3(256), 0, st, genc, enc, (long)c0, (long)Cn,
+                       n_samples, rays_d, points ? in->points : nullptr, gx, points ? nullptr : in->z);
+    SUNERF_CHECK_LAUNCH();
+    if (points || (!in->rays_o && !in->rays_d && !in->times)) continue;
+    const long rays = (c0 + Cn - 1) / n_samples - c0 / n_samples + 1;
+    hipLaunchKernelGGL(ray_sums_kernel, dim3((unsigned)((rays + 255) / 256)), dim3(256), 0, st, gx, (long)c0, (long)Cn, n_samples,
+                       z_vals, in->rays_o, in->rays_d, in->times, carry + (chunk & 1) * RAY_CARRY, carry + ((chunk + 1) & 1) * RAY_CARRY);
+    SUNERF_CHECK_LAUNCH();
   }
+  if (!params) return 0;
   hipLaunchKernelGGL(cast_grads_kernel, dim3((unsigned)((max_count + 255) / 256), (unsigned)n_linear), dim3(256), 0, st, ca);
   SUNERF_CHECK_LAUNCH();
   return 0;
+}
+
+// the argument checks both entry points share (parameter gradients optional: both arrays NULL, or both given)
+int check_chunked_args(const float* const* weights_host, const float* const* biases_host, int n_linear, int d_filter, int d_out,
+                       const float* rays_o, const float* rays_d, const float* times, const float* z_vals, const float* points,
+                       int64_t n_rays, int n_samples, const float* g_raw, const void* workspace, float* const* grad_weights_host,
+                       float* const* grad_biases_host) {
+  if (!weights_host || !biases_host || !g_raw || !workspace) return SUNERF_E_BADARG;
+  if (!grad_weights_host != !grad_biases_host) return SUNERF_E_BADARG;
+  if (n_rays <= 0 || n_samples < 1 || d_filter < 1 || d_out < 1) return SUNERF_E_BADARG;
+  if (n_linear < 2 || n_linear > SUNERF_MAX_LAYERS || d_filter > 512 || d_out > CHUNKED_MAX_OUT) return SUNERF_E_UNSUPPORTED;
+  if (!points && (!rays_o || !rays_d || !times || !z_vals)) return SUNERF_E_BADARG;
+  for (int i = 0; i < n_linear; ++i) {
+    if (!weights_host[i] || !biases_host[i]) return SUNERF_E_BADARG;
+    if (grad_weights_host && (!grad_weights_host[i] || !grad_biases_host[i])) return SUNERF_E_BADARG;
+  }
+  if (n_rays > ((int64_t)1 << 40) / n_samples) return SUNERF_E_UNSUPPORTED;      // 64-bit sample indices throughout
+  return 0;
+}
+
+}  // namespace
+
+extern "C" size_t sunerf_mlp_backward_exact_chunked_workspace_bytes(int d_filter, int n_linear) {
+  if (d_filter < 1 || d_filter > 512 || n_linear < 2 || n_linear > SUNERF_MAX_LAYERS) return 0;
+  return ChunkedLayout(d_filter, n_linear).total;
+}
+
+extern "C" int sunerf_mlp_backward_exact_chunked(const float* const* weights_host, const float* const* biases_host, int n_linear,
+                                                 int d_filter, int d_out, const float* rays_o, const float* rays_d,
+                                                 const float* times, const float* z_vals, const float* points, int64_t n_rays,
+                                                 int n_samples, const float* g_raw, void* workspace, size_t workspace_bytes,
+                                                 float* const* grad_weights_host, float* const* grad_biases_host, int accumulate,
+                                                 void* stream) {
+  if (!grad_weights_host || !grad_biases_host) return SUNERF_E_BADARG;
+  int rc = check_chunked_args(weights_host, biases_host, n_linear, d_filter, d_out, rays_o, rays_d, times, z_vals, points, n_rays,
+                              n_samples, g_raw, workspace, grad_weights_host, grad_biases_host);
+  if (rc) return rc;
+  const ChunkedLayout L(d_filter, n_linear);
+  if (workspace_bytes < L.total) return SUNERF_E_WORKSPACE;
+  return chunked_backward(weights_host, biases_host, n_linear, d_filter, d_out, rays_o, rays_d, times, z_vals, points,
+                          n_rays * n_samples, n_samples, g_raw, (char*)workspace, L, grad_weights_host, grad_biases_host, accumulate,
+                          nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" size_t sunerf_mlp_input_grad_exact_workspace_bytes(int d_filter, int n_linear) {
+  if (d_filter < 1 || d_filter > 512 || n_linear < 2 || n_linear > SUNERF_MAX_LAYERS) return 0;
+  return InputGradLayout(d_filter, n_linear).total;
+}
+
+extern "C" int sunerf_mlp_input_grad_exact(const float* const* weights_host, const float* const* biases_host, int n_linear,
+                                           int d_filter, int d_out, const float* rays_o, const float* rays_d, const float* times,
+                                           const float* z_vals, const float* points, int64_t n_rays, int n_samples,
+                                           const float* g_raw, void* workspace, size_t workspace_bytes,
+                                           float* const* grad_weights_host, float* const* grad_biases_host, int accumulate,
+                                           float* grad_points, float* grad_rays_o, float* grad_rays_d, float* grad_times,
+                                           float* grad_z, void* stream) {
+  int rc = check_chunked_args(weights_host, biases_host, n_linear, d_filter, d_out, rays_o, rays_d, times, z_vals, points, n_rays,
+                              n_samples, g_raw, workspace, grad_weights_host, grad_biases_host);
+  if (rc) return rc;
+  // points mode writes grad_points and no ray gradient; ray mode writes at least one ray gradient and no point gradient
+  const bool ray_out = grad_rays_o || grad_rays_d || grad_times || grad_z;
+  if (points ? (!grad_points || ray_out) : (grad_points || !ray_out)) return SUNERF_E_BADARG;
+  const InputGradLayout IL(d_filter, n_linear);
+  if (workspace_bytes < IL.total) return SUNERF_E_WORKSPACE;
+  const InputGrads in = {grad_points, grad_rays_o, grad_rays_d, grad_times, grad_z};
+  return chunked_backward(weights_host, biases_host, n_linear, d_filter, d_out, rays_o, rays_d, times, z_vals, points,
+                          n_rays * n_samples, n_samples, g_raw, (char*)workspace, IL.base, grad_weights_host, grad_biases_host,
+                          accumulate, &in, &IL, (hipStream_t)stream);
 }

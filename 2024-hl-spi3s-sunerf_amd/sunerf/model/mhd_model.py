@@ -139,8 +139,8 @@ class MHDModel(nn.Module):
 
     Per frame, ``rho`` and ``t`` must share a grid (as PSI's do); the two frames of a pair may have different grids: each
     is interpolated on its own grid, then the two are blended in time.  Grids and data are held in fp32 (the coordinates
-    are fp32 in the reference too).  No gradient w.r.t. the cube or the points; ``log_absortpion`` and
-    ``volumetric_constant`` receive theirs through the DT integral."""
+    are fp32 in the reference too).  No gradient w.r.t. the cube or the points (a ``NeRF`` has one: DESIGN.md section 8c);
+    ``log_absortpion`` and ``volumetric_constant`` receive theirs through the DT integral."""
 
     time_dependent = True       # functional.dt_pass hands the rays' times to field_on_rays
 

@@ -64,7 +64,8 @@ class SimpleStar(nn.Module):
 
     def forward(self, query_points):
         """(M, >=3) query points -> {'inferences': (M, 2), 'log_abs', 'vol_c'} (stellar_model.py:53-102).  The inferences are
-        differentiable w.r.t. the stellar parameters like :meth:`field_on_rays`, not w.r.t. the query points."""
+        differentiable w.r.t. the stellar parameters like :meth:`field_on_rays`, not w.r.t. the query points (unlike ``NeRF``'s:
+        DESIGN.md section 8c)."""
         pts = query_points.reshape(-1, query_points.shape[-1]).detach()
         o = torch.zeros(pts.shape[0], 3, dtype=torch.float32, device=pts.device)
         z = torch.ones(pts.shape[0], 1, dtype=torch.float32, device=pts.device)    # o + d * 1 = the point itself, exactly

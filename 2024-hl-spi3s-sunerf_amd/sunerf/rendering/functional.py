@@ -16,20 +16,30 @@ def _differentiable(params):
 
 class _MlpOnPoints(torch.autograd.Function):
     """``NeRF.forward`` on free-standing query points (model.py:44-57) as an autograd node: the fused render kernel fed with the
-    points themselves (32 per chunk, no ray, its integral unused), differentiable w.r.t. the model's parameters."""
+    points themselves (32 per chunk, no ray, its integral unused), differentiable w.r.t. the model's parameters and the points.
+    When the points need a gradient the backward is one fp32 call (:func:`_input_backward`) that also forms the parameter
+    gradients, and the forward writes no activation stash."""
 
     @staticmethod
     def forward(ctx, model, points, *params):
-        training = any(ctx.needs_input_grad[2:])
+        ctx.input_grad = ctx.needs_input_grad[1]
+        training = any(ctx.needs_input_grad[2:]) and not ctx.input_grad
         packed = model.packed()
         out = ops.mlp_points_fwd(packed, points, training=training)
         if training:
             ctx.packed, ctx.params, ctx.n_padded = packed, params, out['n_padded']
             ctx.save_for_backward(out['stash'], points)
+        elif ctx.input_grad:
+            ctx.packed, ctx.params = packed, params
+            ctx.save_for_backward(points)
         return out['raw'][:, :packed.d_out] if packed.d_out < 2 else out['raw']
 
     @staticmethod
     def backward(ctx, g_raw):
+        if ctx.input_grad:
+            points, = ctx.saved_tensors
+            g_points, param_grads = _input_backward(ctx, g_raw, ('points', points))
+            return (None, g_points[0]) + param_grads
         stash, points = ctx.saved_tensors
         if points.shape[0] != ctx.n_padded:      # the kernels work on whole 32-point chunks: zero points with zero gradient
             points = torch.cat([points, points.new_zeros(ctx.n_padded - points.shape[0], 4)])
@@ -42,13 +52,32 @@ class _MlpOnPoints(torch.autograd.Function):
             ctx.packed, g, absmax, stash, gW, gb, accumulate=accumulate, query=query))
 
 
+def _input_backward(ctx, g_raw, query, wanted=(True, True, True, True)):
+    """The backward of an MLP node whose query (points, or rays / times / z) needs a gradient: ONE call of the fp32 input-gradient
+    kernel (:func:`sunerf_hip.ops.mlp_input_backward`), with the parameter gradients in it when a parameter needs them.  Returns
+    ``(input gradients as a tuple, parameter gradients as _mlp_param_grads returns them)``.  Second derivatives are not built: under
+    ``create_graph=True`` this raises instead of returning gradients without a graph."""
+    if torch.is_grad_enabled():
+        raise RuntimeError('second derivatives of a NeRF w.r.t. its query points / rays are not implemented (the fp32 input-gradient '
+                           'backward is once-differentiable): call backward / autograd.grad without create_graph=True')
+    g_raw = g_raw.contiguous().float()
+    n_params = len(ctx.params)
+    if not any(ctx.needs_input_grad[-n_params:]):
+        g_in = ops.mlp_input_backward(ctx.packed, g_raw, query, wanted=wanted)
+        return (g_in if isinstance(g_in, tuple) else (g_in,)), (None,) * n_params
+    got = []
+    param_grads = _mlp_param_grads(ctx.params, lambda gW, gb, accumulate: got.append(ops.mlp_input_backward(
+        ctx.packed, g_raw, query, gW, gb, accumulate=accumulate, wanted=wanted)))
+    return (got[0] if isinstance(got[0], tuple) else (got[0],)), param_grads
+
+
 def mlp_points(model, x: torch.Tensor) -> torch.Tensor:
     """NeRF.forward on arbitrary query points (M, 4) -> (M, d_out) (model.py:44-57): the fused kernel's free-standing-points
-    mode (``sunerf_mlp_points_fwd``), every lane of it a query point.  Differentiable w.r.t. the model's parameters like the
-    reference's module call (a loss on free-standing points trains)."""
+    mode (``sunerf_mlp_points_fwd``), every lane of it a query point.  Differentiable w.r.t. the model's parameters and the
+    points like the reference's module call (a loss on free-standing points trains; ``torch.autograd.grad(out, x)`` works)."""
     flat = x.reshape(-1, 4)
     params = _mlp_params(model)
-    if _differentiable(params):
+    if _differentiable(params + [flat]):
         return _MlpOnPoints.apply(model, flat, *params)
     packed = model.packed()
     raw = ops.mlp_points_fwd(packed, flat)['raw']
@@ -179,23 +208,35 @@ def emission_pass(model, rays_o, rays_d, times, z_vals, reg_radius, want_epilogu
 
 class _MlpOnRays(torch.autograd.Function):
     """``NeRF.forward`` (model.py:44-57) on the samples ``o + d z`` of a ray batch as an autograd node: the raw network output
-    (N, S, d_output), differentiable w.r.t. the model's parameters.  This is what the generic ``SuNeRFRendering._render``
-    (base_tracing.py:118-129) hands to a subclass's ``raw2outputs``: the MLP runs in the fused render kernel (whose own
-    integral outputs are ignored) and its backward in the data / weight gradient kernels, fed with whatever gradient the
-    subclass's torch code sends back."""
+    (N, S, d_output), differentiable w.r.t. the model's parameters and w.r.t. ``rays_o``, ``rays_d``, ``times`` and ``z_vals``.
+    This is what the generic ``SuNeRFRendering._render`` (base_tracing.py:118-129) hands to a subclass's ``raw2outputs``: the
+    MLP runs in the fused render kernel (whose own integral outputs are ignored) and its backward in the data / weight gradient
+    kernels, fed with whatever gradient the subclass's torch code sends back -- or, when an input needs a gradient, in one call
+    of the fp32 input-gradient kernel (:func:`_input_backward`; the forward then writes no activation stash)."""
 
     @staticmethod
     def forward(ctx, model, rays_o, rays_d, times, z_vals, *params):
-        training = any(ctx.needs_input_grad[5:])
+        ctx.input_grad = any(ctx.needs_input_grad[1:5])
+        training = any(ctx.needs_input_grad[5:]) and not ctx.input_grad
         packed = model.packed()
         out = ops.emission_render_fwd(packed, rays_o, rays_d, times, z_vals, 0.0, want_raw=True, training=training)
         if training:
             ctx.packed, ctx.params = packed, params
             ctx.save_for_backward(out['stash'], rays_o, rays_d, times, z_vals)
+        elif ctx.input_grad:
+            ctx.packed, ctx.params = packed, params
+            ctx.save_for_backward(rays_o, rays_d, times, z_vals)
         return out['raw'][..., :packed.d_out] if packed.d_out < 2 else out['raw']
 
     @staticmethod
     def backward(ctx, g_raw):
+        if ctx.input_grad:
+            rays_o, rays_d, times, z_vals = ctx.saved_tensors
+            wanted = tuple(ctx.needs_input_grad[1:5])
+            (g_o, g_d, g_t, g_z), param_grads = _input_backward(ctx, g_raw, ('rays', rays_o, rays_d, times, z_vals), wanted)
+            if g_t is not None:
+                g_t = g_t.reshape(times.shape)
+            return (None, g_o, g_d, g_t, g_z) + param_grads
         stash, rays_o, rays_d, times, z_vals = ctx.saved_tensors
         query = ('rays', rays_o, rays_d, times, z_vals)
         if g_raw.shape[-1] < 2:
@@ -208,10 +249,10 @@ class _MlpOnRays(torch.autograd.Function):
 
 
 def mlp_on_rays(model, rays_o, rays_d, times, z_vals) -> torch.Tensor:
-    """(N, S, d_output) raw output of ``model`` (a ``NeRF``) at the samples of the rays; goes through autograd when the
-    model is trainable and gradients are enabled."""
+    """(N, S, d_output) raw output of ``model`` (a ``NeRF``) at the samples of the rays; goes through autograd when gradients are
+    enabled and the model is trainable or a ray tensor (``rays_o``, ``rays_d``, ``times``, ``z_vals``) requires grad."""
     params = _mlp_params(model)
-    if _differentiable(params):
+    if _differentiable(params + [rays_o, rays_d, times, z_vals]):
         return _MlpOnRays.apply(model, rays_o, rays_d, times, z_vals, *params)
     raw = ops.emission_render_fwd(model.packed(), rays_o, rays_d, times, z_vals, 0.0, want_raw=True)['raw']
     return raw[..., :model.packed().d_out] if model.packed().d_out < 2 else raw

@@ -803,6 +803,82 @@ def _mlp_backward_exact(packed: PackedMLP, g_raw, query, grad_weights, grad_bias
             packed.d_out, *args, n, s, _ptr(g), _ptr(ws), nbytes, GW, GB, int(accumulate), _stream(dev))
 
 
+def mlp_input_backward(packed: PackedMLP, g_raw, query, grad_weights=None, grad_biases=None, accumulate: bool = False,
+                       wanted=(True, True, True, True)):
+    """Gradients w.r.t. the query of the MLP from the gradient w.r.t. its raw output (csrc/bwd_exact.hip:
+    sunerf_mlp_input_grad_exact, fp32 throughout).  ``query``: ``('points', points (M, 4))`` with ``g_raw`` (M, >= d_out) -> the
+    (M, 4) point gradient; or ``('rays', rays_o, rays_d, times, z_vals)`` with ``g_raw`` (N, S, >= d_out) -> ``(g_rays_o (N, 3),
+    g_rays_d (N, 3), g_times (N,), g_z_vals (N, S))``, an entry None where ``wanted`` says so.  Given ``grad_weights`` /
+    ``grad_biases`` (model shapes), the parameter gradients are filled / added to (``accumulate``) in the same call, bit-identical
+    to :func:`_mlp_backward_exact` ``(chunked=True)``'s."""
+    lib = _l.load()
+    dev = g_raw.device
+    nl = packed.n_linear
+    f32 = dict(dtype=torch.float32, device=dev)
+    if query[0] == 'rays':
+        _, o, d, t, z = query
+        n, s = z.shape
+        o, d = _dev(o, 'rays_o', (n, 3)), _dev(d, 'rays_d', (n, 3))
+        t, z = _dev(t.reshape(-1), 'times', (n,)), _dev(z, 'z_vals', (n, s))
+        g = g_raw.reshape(n, s, -1)[..., :packed.d_out]
+        outs = [torch.empty(shape, **f32) if w else None for w, shape in zip(wanted, ((n, 3), (n, 3), (n,), (n, s)))]
+        if not any(w is not None for w in outs):
+            raise ValueError('mlp_input_backward: no ray gradient wanted')
+        args = (_ptr(o), _ptr(d), _ptr(t), _ptr(z), None)
+        out_ptrs = (None,) + tuple(_ptr(x) for x in outs)
+    else:
+        n, s = query[1].shape[0], 1
+        pts = _dev(query[1], 'points', (n, 4))
+        g = g_raw.reshape(n, -1)[:, :packed.d_out]
+        outs = torch.empty(n, 4, **f32)
+        args = (None, None, None, None, _ptr(pts))
+        out_ptrs = (_ptr(outs), None, None, None, None)
+    g = _dev(g, 'g_raw')
+    params = grad_weights is not None
+    kernel_w, kernel_b, kernel_accumulate = grad_weights, grad_biases, accumulate
+    if params:
+        if len(grad_weights) != nl or len(grad_biases) != nl:
+            raise ValueError('one weight and one bias gradient buffer per layer')
+        for i, (gw, gb) in enumerate(zip(grad_weights, grad_biases)):
+            d_in = packed.d_in if i == 0 else packed.d_model
+            d_o = packed.d_out if i == nl - 1 else packed.d_model
+            if gw.shape != (d_o, d_in) or gb.shape != (d_o,) or gw.dtype != torch.float32 or gb.dtype != torch.float32 \
+                    or not gw.is_contiguous() or not gb.is_contiguous():
+                raise ValueError(f'grad buffer {i} has the wrong shape / layout')
+        if packed.padded:      # the kernel writes the padded shapes (PackedMLP.__init__); the model's are their leading blocks
+            if getattr(packed, '_pad_gw', None) is None:
+                packed._pad_gw = [torch.empty(ws, **f32) for ws, _ in packed.kernel_shapes()]
+                packed._pad_gb = [torch.empty(bs, **f32) for _, bs in packed.kernel_shapes()]
+            kernel_w, kernel_b, kernel_accumulate = packed._pad_gw, packed._pad_gb, False
+    if n * s == 0:
+        for x in (outs if isinstance(outs, list) else [outs]):
+            if x is not None:
+                x.zero_()
+        if params and not accumulate:
+            for gw, gb in zip(grad_weights, grad_biases):
+                gw.zero_()
+                gb.zero_()
+        return tuple(outs) if isinstance(outs, list) else outs
+    ws_, bs_ = packed._keepalive          # fp32 parameters of the kernel shapes (the padded copies for padded models)
+    nbytes = lib.sunerf_mlp_input_grad_exact_workspace_bytes(packed.d_filter, nl)
+    ws = _workspace(_exact_ws, dev, nbytes)
+    W = (ctypes.c_void_p * nl)(*[w.data_ptr() for w in ws_])
+    B = (ctypes.c_void_p * nl)(*[b.data_ptr() for b in bs_])
+    GW = (ctypes.c_void_p * nl)(*[x.data_ptr() for x in kernel_w]) if params else None
+    GB = (ctypes.c_void_p * nl)(*[x.data_ptr() for x in kernel_b]) if params else None
+    _l.call(dev, 'sunerf_mlp_input_grad_exact', W, B, nl, packed.d_filter, packed.d_out, *args, n, s, _ptr(g), _ptr(ws), nbytes,
+            GW, GB, int(kernel_accumulate), *out_ptrs, _stream(dev))
+    if params and packed.padded:
+        for gw, gb, pw, pb in zip(grad_weights, grad_biases, kernel_w, kernel_b):
+            if accumulate:
+                gw.add_(pw[:gw.shape[0], :gw.shape[1]])
+                gb.add_(pb[:gb.shape[0]])
+            else:
+                gw.copy_(pw[:gw.shape[0], :gw.shape[1]])
+                gb.copy_(pb[:gb.shape[0]])
+    return tuple(outs) if isinstance(outs, list) else outs
+
+
 def mlp_backward(packed: PackedMLP, g_raw, absmax, stash, grad_weights: Sequence[torch.Tensor],
                  grad_biases: Sequence[torch.Tensor], accumulate: bool = False, query=None):
     """dgrad + wgrad of the sine MLP from the gradient w.r.t. its raw output (N,S,2): fills / accumulates the nn.Linear

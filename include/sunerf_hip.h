@@ -252,6 +252,30 @@ int sunerf_mlp_backward_exact_chunked(const float* const* weights_host, const fl
                                       float* const* grad_weights_host, float* const* grad_biases_host, int accumulate,
                                       void* stream);
 
+/* Gradients w.r.t. the QUERY of the MLP -- points, or rays / times / sample positions -- in the arithmetic of the chunked kernel
+ * above, with that kernel's parameter gradients alongside on request.  Replaces torch.autograd of sunerf/model/model.py:44-57 +
+ * 123-132 (and sampling.py:100's o + d z) w.r.t. its inputs: NeRF(points) differentiated w.r.t. `points`, a raw2outputs loss
+ * differentiated w.r.t. the rays.  Per chunk of samples the same fp32 forward and data-gradient chain run down to dZ_0, then
+ * g_enc = dZ_0 W_0 (84 columns, fp32-input MFMA), the derivative of the positional encoding from the chunk's own sin / cos
+ * features, and in ray mode the per-ray sums in fp64 (fixed sample order, a ray straddling a chunk seam carried into the next
+ * chunk; no atomics: two runs are bit-identical).
+ *   arguments                 : as sunerf_mlp_backward_exact_chunked, except that grad_weights / grad_biases may both be NULL
+ *                               (input gradients only: no weight-gradient GEMMs, column sums or fp64 accumulation); given, they
+ *                               are bit-identical to sunerf_mlp_backward_exact_chunked's for the same inputs
+ *   grad_points (N*S, 4)      : points mode (points != NULL): required; every ray gradient NULL
+ *   grad_rays_o, grad_rays_d  : ray mode: (N, 3) each; grad_times (N); grad_z (N, S); any of them NULL (not written), at least
+ *                               one given, grad_points NULL.  Always overwritten (no accumulate)
+ *   workspace                 : sunerf_mlp_input_grad_exact_workspace_bytes(d_filter, n_linear) bytes
+ * Cost: the chunked kernel's forward and data-gradient GEMMs (its weight-gradient work only when asked for) + one 84-column GEMM
+ * per chunk. */
+size_t sunerf_mlp_input_grad_exact_workspace_bytes(int d_filter, int n_linear);
+int sunerf_mlp_input_grad_exact(const float* const* weights_host, const float* const* biases_host, int n_linear, int d_filter,
+                                int d_out, const float* rays_o, const float* rays_d, const float* times, const float* z_vals,
+                                const float* points, int64_t n_rays, int n_samples, const float* g_raw, void* workspace,
+                                size_t workspace_bytes, float* const* grad_weights_host, float* const* grad_biases_host,
+                                int accumulate, float* grad_points, float* grad_rays_o, float* grad_rays_d, float* grad_times,
+                                float* grad_z, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Density / temperature head (run_density_temperature.py path).
  * Replaces DensityTemperatureRadiativeTransfer.raw2outputs / regularization, density_temperature.py:192-274, the base
