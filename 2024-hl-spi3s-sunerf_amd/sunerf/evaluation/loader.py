@@ -17,6 +17,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+from sunerf_hip.maps import render_columns
 from sunerf_hip.rays import pose_spherical, render_frame
 
 AU_IN_SOLAR_RADII = 215.03215567054764      # (1 * u.AU).to(u.solRad), IAU 2012 / 2015 nominal values
@@ -28,6 +29,14 @@ def _radians(x) -> float:
         from astropy import units as u
         return float(x.to_value(u.rad))
     return float(x)
+
+
+def _radians_array(x) -> np.ndarray:
+    """:func:`_radians` of an array of angles (plain numbers: radians) -> float64 array."""
+    if hasattr(x, 'to_value'):
+        from astropy import units as u
+        return np.asarray(x.to_value(u.rad), dtype=np.float64)
+    return np.asarray(x, dtype=np.float64)
 
 
 def _solar_radii(x) -> float:
@@ -180,6 +189,47 @@ class SuNeRFLoader:
         time = normalize_datetime(time, self.seconds_per_dt, self.ref_time)
         return self._render(lat, lon, time, distance, center, resolution, batch_size, None, as_numpy)
 
+    def _columns(self, lat, lon, time: float, grid, r_range, n_samples, batch_size, profiles, wl, as_numpy):
+        wavelengths = None if wl is None else torch.as_tensor(np.asarray(wl), dtype=torch.float32, device=self.device)
+        lat = torch.from_numpy(_radians_array(lat).reshape(-1)).to(self.device)
+        lon = torch.from_numpy(_radians_array(lon).reshape(-1)).to(self.device)
+        r_range = (_solar_radii(r_range[0]), _solar_radii(r_range[1]))
+        out = render_columns(self.rendering, lat, lon, float(time), r_range, n_samples, wavelengths,
+                             None if batch_size is None else int(batch_size), profiles=profiles, grid=grid)
+        if not as_numpy:
+            return out
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def _map(self, time: float, lat_range, lon_range, shape, r_range, n_samples, batch_size, profiles, wl, as_numpy):
+        n_lat, n_lon = (int(shape), int(shape)) if np.isscalar(shape) else (int(shape[0]), int(shape[1]))
+        lat = np.linspace(_radians(lat_range[0]), _radians(lat_range[1]), n_lat)      # pixel centres include both ends
+        lon = np.linspace(_radians(lon_range[0]), _radians(lon_range[1]), n_lon)
+        return self._columns(lat, lon, time, True, r_range, n_samples, batch_size, profiles, wl, as_numpy)
+
+    @torch.no_grad()
+    def render_heliographic_map(self, time: datetime, lat_range=(-np.pi / 2, np.pi / 2), lon_range=(-np.pi, np.pi),
+                                shape=(721, 1441), r_range=(1.0, 1.3), n_samples: int = 512, batch_size: Optional[int] = None,
+                                profiles: bool = False, as_numpy: bool = True):
+        """Heliographic map of the corona at ``time`` (a datetime): one radial column per (latitude, longitude) pixel through
+        the fine model, ``n_samples`` radii ``linspace(*r_range)`` [solar radii] per column (sunerf/evaluation/stash/
+        topographical_map.py:36-66, topographical_profile.py:33-58).  Angles as in :meth:`render_observer_image` (plain
+        numbers: radians); pixel centres ``linspace(*lat_range, shape[0])`` x ``linspace(*lon_range, shape[1])``, row 0 the
+        southernmost latitude, column 0 the smallest longitude.  Returns the outputs of ``sunerf_hip.maps.render_columns``,
+        each ``(n_lat, n_lon, ...)``; heights in solar radii.  ``batch_size``: columns per tile (default: about 1 GiB of
+        scratch per tile)."""
+        time = normalize_datetime(time, self.seconds_per_dt, self.ref_time)
+        return self._map(time, lat_range, lon_range, shape, r_range, n_samples, batch_size, profiles, None, as_numpy)
+
+    @torch.no_grad()
+    def render_radial_profile(self, lats, lons, time: datetime, r_range=(1.0, 1.3), n_samples: int = 512,
+                              batch_size: Optional[int] = None, profiles: bool = True, as_numpy: bool = True):
+        """Radial columns along an arc or at arbitrary points: per-column ``lats`` / ``lons`` of equal length (radians or
+        astropy quantities) at ``time`` (a datetime) (topographical_profile.py:33-58, topographical_slice.py:119-140,
+        eruption_profile.py:76-101).  Returns the outputs of ``sunerf_hip.maps.render_columns``, each ``(n, ...)``, with the
+        per-sample profiles ``(n, n_samples)`` by default."""
+        time = normalize_datetime(time, self.seconds_per_dt, self.ref_time)
+        return self._columns(lats, lons, time, False, r_range, n_samples, batch_size, profiles, None, as_numpy)
+
     def normalize_datetime(self, time):
         return normalize_datetime(time, self.seconds_per_dt, self.ref_time)
 
@@ -225,3 +275,18 @@ class ModelLoader(SuNeRFLoader):
                               as_numpy: bool = True):
         """loader.py:159-242: ``time`` is already normalised here (a float)."""
         return self._render(lat, lon, time, distance, center, resolution, batch_size, wl, as_numpy)
+
+    @torch.no_grad()
+    def render_heliographic_map(self, time: float, lat_range=(-np.pi / 2, np.pi / 2), lon_range=(-np.pi, np.pi),
+                                shape=(721, 1441), r_range=(1.0, 1.3), n_samples: int = 512, wl: Optional[np.ndarray] = None,
+                                batch_size: Optional[int] = None, profiles: bool = False, as_numpy: bool = True):
+        """:meth:`SuNeRFLoader.render_heliographic_map` with ``time`` already normalised (a float) and the channels ``wl`` of a
+        density-temperature rendering."""
+        return self._map(time, lat_range, lon_range, shape, r_range, n_samples, batch_size, profiles, wl, as_numpy)
+
+    @torch.no_grad()
+    def render_radial_profile(self, lats, lons, time: float, r_range=(1.0, 1.3), n_samples: int = 512,
+                              wl: Optional[np.ndarray] = None, batch_size: Optional[int] = None, profiles: bool = True,
+                              as_numpy: bool = True):
+        """:meth:`SuNeRFLoader.render_radial_profile` with ``time`` already normalised (a float) and the channels ``wl``."""
+        return self._columns(lats, lons, time, False, r_range, n_samples, batch_size, profiles, wl, as_numpy)

@@ -365,6 +365,33 @@ int sunerf_observer_rays(const double* tx, const double* ty, int per_pixel, int 
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Heliographic analyses: radial columns from the solar centre, one per (latitude, longitude).
+ * Replaces the host-side point generation of the reference's stash scripts, sunerf/evaluation/stash/
+ * topographical_map.py:36-49, topographical_profile.py:33-45, topographical_slice.py:119-130, eruption_profile.py:76-88.
+ *   lat, lon : [rad], fp64, device, in the convention of render_observer_image (loader.py:63-108).  per_column = 0:
+ *              lat[n_lat] (rows, south first) and lon[n_lon] (columns) are the axes of a regular grid, column
+ *              p = row * n_lon + col;  per_column != 0: lat[p], lon[p] for every column (arcs, point lists)
+ *   columns [col_begin, col_begin + n_cols) are produced (one tile)
+ *   rays_o [n_cols, 3] out (zeros);  rays_d [n_cols, 3] out = fp32(u), u = (-cos lat sin lon, cos lat cos lon, -sin lat)
+ *              evaluated in fp64 (the normalised position of pose_spherical(-lon, lat, d));  times [n_cols] out, filled
+ *              with time_value (may be NULL)
+ * ---------------------------------------------------------------------------------------------------------- */
+int sunerf_column_rays(const double* lat, const double* lon, int per_column, int n_lon, int64_t col_begin, int64_t n_cols,
+                       float time_value, float* rays_o, float* rays_d, float* times, void* stream);
+
+/* Column statistics of a fused emission pass over columns of sunerf_column_rays (one wave64 per column, fp32 sums):
+ *   raw [N,S,2] (sunerf_emission_render_fwd's raw), z_row [S] (the z shared by every column), rays_d [N,3]
+ *   e_j  = exp(raw_j0),  dr_j = (z_j - z_{j-1}) |rays_d| with the first interval duplicated (the integral's own dists,
+ *          emission.py:19-26),  r_j = z_j |rays_d| (the sample's distance from the centre)
+ *   emission_height [N] = height_scale * sum r_j e_j / sum e_j            topographical_profile.py:57
+ *   emission_column [N] = sum e_j dr_j  (optically thin column)          topographical_slice.py:131-140 (there without dr)
+ *   emission [N,S] = e_j, absorption [N,S] = 1 - exp(-relu(raw_j1) dr_j) eruption_profile.py:89-94 (both NULL or both set)
+ * ---------------------------------------------------------------------------------------------------------- */
+int sunerf_column_stats(const float* raw, const float* z_row, const float* rays_d, int64_t n_cols, int n_samples,
+                        float height_scale, float* emission_height, float* emission_column, float* emission,
+                        float* absorption, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Output side of the path: training loss and optimiser step without host synchronisation.
  *
  * sunerf_training_loss replaces EmissionSuNeRFModule.training_step's loss section, sunerf/model/sunerf.py:105-125
