@@ -119,8 +119,7 @@ __global__ void reduce_grads_kernel(ReduceArgs a) {
   int boost = 0;
   if (a.sumsq)
     for (int l = layer + 1; l < a.n_linear; ++l) boost += sunerf_bwd_boost(a.sumsq[l], D);
-  const float inv = ldexpf(sunerf_gscale_inv(*a.g_absmax_bits), -boost);
-  float v = sum * inv;
+  float v = sunerf_gscale_unscale(sum, *a.g_absmax_bits, boost);
   if (a.status && *a.status != 0u) v = __uint_as_float(0x7fc00000u);
   float* dst = (tc == T) ? a.gb[layer] + j : a.gW[layer] + (size_t)j * cols + k;
   *dst = a.accumulate ? *dst + v : v;

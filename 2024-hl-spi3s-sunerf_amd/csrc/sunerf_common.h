@@ -149,14 +149,21 @@ static inline int sunerf_grid_cap(const char* name, int cus) {
 // 2^-18 of the maximum still carries an absolute error of only 2^-29 of the maximum.
 #define SUNERF_GSCALE_LOG2 4
 #if defined(__HIPCC__)
-__device__ __forceinline__ int sunerf_gscale_exponent(unsigned absmax_bits) {   // e with max|g_raw| = f 2^e, f in [0.5, 1)
+// e with max|g_raw| = f 2^e, f in [0.5, 1), but at least SUNERF_GSCALE_LOG2 - 127: the scale 2^(SUNERF_GSCALE_LOG2 - e) must stay a
+// finite fp32 power of two.  Unclamped, max|g_raw| < 2^-124 made it +inf and every zero entry of g_raw 0 * inf = NaN; now such a
+// batch enters the fp16 products below 2^SUNERF_GSCALE_LOG2 (2^-13 at max|g_raw| = 2^-140, still an fp16 normal).
+__device__ __forceinline__ int sunerf_gscale_exponent(unsigned absmax_bits) {
   const float m = __uint_as_float(absmax_bits);
   int e = SUNERF_GSCALE_LOG2;
   if (m > 0.f) frexpf(m, &e);
-  return e;
+  return e < SUNERF_GSCALE_LOG2 - 127 ? SUNERF_GSCALE_LOG2 - 127 : e;
 }
 __device__ __forceinline__ float sunerf_gscale(unsigned absmax_bits) { return ldexpf(1.f, SUNERF_GSCALE_LOG2 - sunerf_gscale_exponent(absmax_bits)); }
-__device__ __forceinline__ float sunerf_gscale_inv(unsigned absmax_bits) { return ldexpf(1.f, sunerf_gscale_exponent(absmax_bits) - SUNERF_GSCALE_LOG2); }
+// the unscale of a sum that carries the scale and `boost` more powers of two: ONE ldexp, so that a result in fp32's subnormals is
+// rounded once (a factor 2^(e - 4 - boost) formed first would itself underflow to 0 below 2^-149)
+__device__ __forceinline__ float sunerf_gscale_unscale(float sum, unsigned absmax_bits, int boost) {
+  return ldexpf(sum, sunerf_gscale_exponent(absmax_bits) - SUNERF_GSCALE_LOG2 - boost);
+}
 // Per-layer power-of-two BOOST of the backward chain (round 2).  The data gradient shrinks (or grows) by the layer's gain
 // -- sqrt(sum W^2 / fan-in) * rms(cos) ~ 0.41 for a default-initialised layer -- every time it passes one: after seven
 // layers it is 2^-9 of g_raw and its small entries reach fp16's subnormals, where the per-tensor relative error of the weight

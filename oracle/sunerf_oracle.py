@@ -250,6 +250,24 @@ def render_pass_f64(params: Params, rays_o, rays_d, times, z_vals, reg_radius: f
     return out
 
 
+def mlp_probe_f64(params: Params, rays_o, rays_d, times, z_vals, idx, g) -> Tuple[torch.Tensor, List[Tuple[torch.Tensor, torch.Tensor]]]:
+    """The MLP of :func:`render_pass_f64` on a few of its samples, with its parameter gradients: a per-sample yardstick for the
+    backward kernels.  ``idx``: (k, 2) (ray, sample) indices (a tensor or a list of pairs); ``g``: (k, d_out), the upstream
+    gradient w.r.t. raw at those samples.  The fp32 points are formed exactly as :func:`render_pass_f64` forms them; the encoder
+    and the MLP then run in float64 on those points only.  Returns ``raw64`` (k, d_out) and [(dW, db)] = float64 autograd of
+    sum(g * raw), i.e. render_pass_f64's autograd with ``g_raw`` zero on every other sample.  Plain torch on the inputs'
+    device."""
+    idx = torch.as_tensor(idx, dtype=torch.long, device=z_vals.device).reshape(-1, 2)
+    r, s = idx[:, 0], idx[:, 1]
+    pts = points_on_rays(rays_o[r], rays_d[r], z_vals[r, s][:, None])[:, 0]          # elementwise: the same fp32 values
+    query = torch.cat([pts, times.reshape(-1, 1)[r]], -1).double()
+    leaves = [(W.detach().double().requires_grad_(True), b.detach().double().requires_grad_(True)) for W, b in params]
+    with torch.enable_grad():
+        raw = mlp_forward(leaves, query)
+        flat = torch.autograd.grad((g.to(raw) * raw).sum(), [x for pair in leaves for x in pair])
+    return raw.detach(), [(flat[2 * i], flat[2 * i + 1]) for i in range(len(leaves))]
+
+
 def emission_outputs(raw, z_vals, rays_o, rays_d, reg_radius: float) -> Dict[str, torch.Tensor]:
     """raw (N, S, 2) -> the emission integral (:func:`emission_integral`) and the single-pass epilogues of base_tracing.py:99-110,
     computed in the dtype of ``raw`` (float32: the fp32 oracle's own expressions; float64: the yardstick of
