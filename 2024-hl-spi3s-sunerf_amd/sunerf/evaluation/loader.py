@@ -172,9 +172,17 @@ class SuNeRFLoader:
         ty = torch.from_numpy(np.ascontiguousarray(coords.Ty.to_value(u.rad), dtype=np.float64)).to(self.device)
         return tx, ty
 
-    def _render(self, lat, lon, time: float, distance, center, resolution, batch_size, wl=None, as_numpy=True):
+    def _render(self, lat, lon, time: float, distance, center, resolution, batch_size, wl=None, as_numpy=True, strides=1):
         target_pose = pose_spherical(-_radians(lon), _radians(lat), _solar_radii(distance), center)
         tx, ty = self._pixel_angles(resolution)
+        strides = int(strides)
+        if strides < 1:
+            raise ValueError(f'strides must be >= 1, got {strides}')
+        if strides > 1:         # pixels [::strides, ::strides] of the full frame (the reference scripts' gt[::s, ::s])
+            if tx.dim() == 2:
+                tx, ty = tx[::strides, ::strides].contiguous(), ty[::strides, ::strides].contiguous()
+            else:
+                tx, ty = tx[::strides].contiguous(), ty[::strides].contiguous()
         wavelengths = None if wl is None else torch.as_tensor(np.asarray(wl), dtype=torch.float32, device=self.device)
         frame = render_frame(self.rendering, tx, ty, target_pose, float(time), wavelengths, tile_rays=int(batch_size))
         if not as_numpy:
@@ -184,10 +192,11 @@ class SuNeRFLoader:
     @torch.no_grad()
     def render_observer_image(self, lat, lon, time: datetime, distance=AU_IN_SOLAR_RADII,
                               center: Tuple[float, float, float] = None, resolution=None, batch_size: int = 1 << 18,
-                              as_numpy: bool = True):
-        """loader.py:63-108: image of the observer at (lat, lon, distance) at ``time`` (a datetime)."""
+                              as_numpy: bool = True, strides: int = 1):
+        """loader.py:63-108: image of the observer at (lat, lon, distance) at ``time`` (a datetime).  ``strides`` renders the
+        pixels ``[::strides, ::strides]`` of that frame only (the evaluation scripts compare with ``gt[::strides, ::strides]``)."""
         time = normalize_datetime(time, self.seconds_per_dt, self.ref_time)
-        return self._render(lat, lon, time, distance, center, resolution, batch_size, None, as_numpy)
+        return self._render(lat, lon, time, distance, center, resolution, batch_size, None, as_numpy, strides)
 
     def _columns(self, lat, lon, time: float, grid, r_range, n_samples, batch_size, profiles, wl, as_numpy):
         wavelengths = None if wl is None else torch.as_tensor(np.asarray(wl), dtype=torch.float32, device=self.device)
@@ -272,9 +281,10 @@ class ModelLoader(SuNeRFLoader):
     @torch.no_grad()
     def render_observer_image(self, lat, lon, time: float, distance=AU_IN_SOLAR_RADII, wl: Optional[np.ndarray] = None,
                               center: Tuple[float, float, float] = None, resolution=None, batch_size: int = 1 << 17,
-                              as_numpy: bool = True):
-        """loader.py:159-242: ``time`` is already normalised here (a float)."""
-        return self._render(lat, lon, time, distance, center, resolution, batch_size, wl, as_numpy)
+                              as_numpy: bool = True, strides: int = 1):
+        """loader.py:159-242: ``time`` is already normalised here (a float); ``strides`` as in
+        :meth:`SuNeRFLoader.render_observer_image`."""
+        return self._render(lat, lon, time, distance, center, resolution, batch_size, wl, as_numpy, strides)
 
     @torch.no_grad()
     def render_heliographic_map(self, time: float, lat_range=(-np.pi / 2, np.pi / 2), lon_range=(-np.pi, np.pi),
@@ -290,3 +300,61 @@ class ModelLoader(SuNeRFLoader):
                               as_numpy: bool = True):
         """:meth:`SuNeRFLoader.render_radial_profile` with ``time`` already normalised (a float) and the channels ``wl``."""
         return self._columns(lats, lons, time, False, r_range, n_samples, batch_size, profiles, wl, as_numpy)
+
+
+class EnsembleLoader:
+    """K trained members of one model (``.snf`` files) rendered from the same observer (uncertainty_correlation.py:56-77,
+    overview_simulation.py:47-52): one :class:`SuNeRFLoader` per file, all on one device.  The members must share
+    ``ref_time``, ``seconds_per_dt``, ``Rs_per_ds``, ``wcs`` and ``resolution``."""
+
+    _SHARED = ('ref_time', 'seconds_per_dt', 'Rs_per_ds', 'wcs', 'resolution')
+
+    def __init__(self, state_paths, device=None):
+        state_paths = list(state_paths)
+        if not state_paths:
+            raise ValueError('EnsembleLoader needs at least one state file')
+        self.loaders = [SuNeRFLoader(path, device=device) for path in state_paths]
+        first = self.loaders[0]
+        for path, member in zip(state_paths[1:], self.loaders[1:]):
+            for field in self._SHARED:
+                if not _same(getattr(member, field), getattr(first, field)):
+                    raise ValueError(f'EnsembleLoader: {path} has a different {field} than {state_paths[0]}')
+        self.device = first.device
+
+    @torch.no_grad()
+    def render_observer_image(self, lat, lon, time: datetime, distance=AU_IN_SOLAR_RADII,
+                              center: Tuple[float, float, float] = None, resolution=None, batch_size: int = 1 << 18,
+                              as_numpy: bool = True, strides: int = 1):
+        """Member 0's :meth:`SuNeRFLoader.render_observer_image` outputs, plus ``ensemble_mean`` and ``ensemble_std`` (ddof 0,
+        as ``np.std(predictions, 0)``) of ``image`` over the members: two passes in fp64, in member order, then fp32."""
+        frames = [m.render_observer_image(lat, lon, time, distance, center, resolution, batch_size, False, strides)
+                  for m in self.loaders]
+        images = [f['image'].double() for f in frames]
+        mean = images[0].clone()
+        for img in images[1:]:
+            mean += img
+        mean /= len(images)
+        var = torch.zeros_like(mean)
+        for img in images:
+            var += (img - mean) ** 2
+        var /= len(images)
+        out = dict(frames[0])
+        out['ensemble_mean'] = mean.float()
+        out['ensemble_std'] = torch.sqrt(var).float()
+        if not as_numpy:
+            return out
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def _same(a, b) -> bool:
+    if isinstance(a, dict) and isinstance(b, dict):
+        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, (np.ndarray, list, tuple)) or isinstance(b, (np.ndarray, list, tuple)):
+        try:
+            return bool(np.array_equal(np.asarray(a), np.asarray(b)))
+        except Exception:
+            return False
+    try:
+        return bool(a == b)
+    except Exception:       # objects without a usable equality (e.g. a WCS that refuses the comparison)
+        return a is b

@@ -4,6 +4,7 @@
 ``run_emission.py`` works unchanged); otherwise a minimal base with the same hook names is used and
 ``fit_steps`` below drives ``training_step`` / ``configure_optimizers`` / ``on_train_batch_end`` directly.
 """
+import math
 import os
 
 import torch
@@ -102,6 +103,32 @@ class BaseSuNeRFModule(LightningModule):
             self.validation_dataset_mapping[i]: {key: torch.cat([b[key] for b in batches]) for key in batches[0]}
             for i, batches in enumerate(per_set)}
 
+    def validation_metrics(self, image_shape, name=None):
+        """The scores the reference's TestImageCallback / TestMultiThermalImageCallback log (callback.py:46-56, 84-86), on the
+        device: ``{'validation.loss', 'validation.ssim', 'validation.psnr'}`` as 0-d fp64 tensors of the validation set
+        ``name`` (default: the first stored set), or None when nothing is stored.  The stored ``fine_image`` and
+        ``target_image`` (N, C) are reshaped to ``image_shape`` (H, W) x C; the loss is the MSE over all channels, the SSIM that
+        of channel 0 (data_range 1), psnr = -10 log10(loss).  Images are scored as fp32 after ``_validation_images``."""
+        if not self.validation_outputs:
+            return None
+        name = next(iter(self.validation_outputs)) if name is None else name
+        if name not in self.validation_outputs:
+            return None
+        from sunerf_hip.metrics import image_metrics
+        outputs = self.validation_outputs[name]
+        height, width = (int(v) for v in image_shape)
+        fine, target = outputs['fine_image'], outputs['target_image']
+        if height * width != fine.shape[0] or target.shape[0] != fine.shape[0]:
+            raise ValueError(f'validation_metrics: image_shape {height} x {width} does not hold the {fine.shape[0]} stored rays')
+        fine, target = self._validation_images(fine.reshape(height, width, -1), target.reshape(height, width, -1))
+        scores = image_metrics(fine.permute(2, 0, 1), target.permute(2, 0, 1), 1.0)      # one call, every channel
+        loss = scores['mse'].mean()
+        return {'validation.loss': loss, 'validation.ssim': scores['ssim'][0], 'validation.psnr': -10. * torch.log10(loss)}
+
+    def _validation_images(self, fine, target):
+        """The images the callback scores, from the stored (H, W, C) outputs: as they are (TestMultiThermalImageCallback)."""
+        return fine, target
+
     def on_load_checkpoint(self, checkpoint):
         """sunerf.py:56-59: non-strict restore (checkpoints written before a module gained a buffer still load)."""
         self.validation_outputs = {}
@@ -161,6 +188,15 @@ class EmissionSuNeRFModule(BaseSuNeRFModule):
                                     asinh_scaling=self._asinh_constants(),
                                     finite_check=_other_outputs(outputs))
         return self._finish_step(loss, stats)
+
+    def _validation_images(self, fine, target):
+        """TestImageCallback's ImageNormalize(vmin=0, vmax=1, stretch=AsinhStretch(0.005), clip=True) (callback.py:35, 46-48;
+        astropy mpl_normalize.py:157-173, stretch.py:31-44, 499-504) in fp64: asinh(clip(x, 0, 1) / a) / asinh(1 / a)."""
+        a = 0.005
+
+        def normalize(x):
+            return torch.asinh(x.double().clamp(0., 1.) / a) / math.asinh(1. / a)
+        return normalize(fine), normalize(target)
 
     def validation_step(self, batch, batch_nb, **kwargs):
         dataloader_idx = kwargs['dataloader_idx'] if 'dataloader_idx' in kwargs else 0

@@ -124,6 +124,9 @@ _SIGNATURES = {
                                               ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_float,
                                               ctypes.c_float, ctypes.c_int64, c_f32p, c_f32p, c_void, ctypes.c_size_t,
                                               c_void, c_void]),
+    'sunerf_image_metrics_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    'sunerf_image_metrics': (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_void,
+                                             c_void, ctypes.c_size_t, c_void]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -434,6 +434,26 @@ int sunerf_clip_adam_step(float* params, float* grads, float* exp_avg, float* ex
                           void* step_counter, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Image scores: replaces the host-side scoring of the reference's TestImageCallback,
+ * sunerf/train/callback.py:46-56 and :84-86 (skimage SSIM, MSE, PSNR), and of its evaluation scripts,
+ * sunerf/evaluation/stash/metrics_simulation.py:41-54 and baseline_simulation.py:30-42 (SSIM, MAE, ME).
+ *   pred, target : [n_images][height][width] fp32, each image contiguous;  all arithmetic fp64
+ *   out [n_images][4] (fp64, device) = ssim, mse, mae, me per image:
+ *     ssim = skimage.metrics.structural_similarity(target, pred, data_range) with its defaults (7 x 7 uniform window,
+ *            sample covariance 49 / 48, scipy 'reflect' boundary, C1 = (0.01 R)^2, C2 = (0.03 R)^2, mean of the SSIM map
+ *            over [3, height - 3) x [3, width - 3));
+ *     mse, mae, me = means of d^2, |d| and d over all pixels, d = pred - target.
+ *   A NaN pixel makes all four outputs of its image NaN and no other.  Two launches, no atomics: bit-identical reruns, and
+ *   an image's scores do not depend on the batch it is scored in.
+ *   workspace : the size the workspace function returns (fp64 partial sums of every tile), 8-byte aligned.
+ *   n_images == 0 does nothing; height or width < 7 (skimage: win_size exceeds image extent), a data_range that is not
+ *   finite or not > 0 and null pointers give SUNERF_E_BADARG; a smaller workspace gives SUNERF_E_WORKSPACE.
+ * ---------------------------------------------------------------------------------------------------------- */
+size_t sunerf_image_metrics_workspace_bytes(int64_t n_images, int height, int width);
+int sunerf_image_metrics(const float* pred, const float* target, int64_t n_images, int height, int width,
+                         double data_range, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Analytic field of SimpleStar: replaces SimpleStar.forward, sunerf/model/stellar_model.py:53-102,
  * evaluated at the sample points o + d z (sampling.py:100) of every ray; the result feeds sunerf_dt_integral_fwd with
  * base_log_density = base_log_temperature = 0 exactly as the MLP output of NeRF_DT does
