@@ -48,9 +48,28 @@ class BaseSuNeRFModule(LightningModule):
         # sunerf.py:31: Adam(lr = start).  ClipAdam is the same update on one flat buffer (and can take the gradient
         # clip that run_emission.py:72 configures on the Trainer: fit_steps below sets optimizer.max_norm).
         self.optimizer = ClipAdam(self.rendering.parameters(), lr=self.lr_config['start'])
+        self.optimizer.nonfinite_source = self._step_nonfinite_count      # (Lightning's step(closure) passes no count)
         self.scheduler = ExponentialLR(self.optimizer, gamma=(self.lr_config['end'] / self.lr_config['start']) ** (
                 1 / self.lr_config['iterations']))
         return [self.optimizer], [self.scheduler]
+
+    def configure_gradient_clipping(self, optimizer, *optimizer_idx, gradient_clip_val=None, gradient_clip_algorithm=None):
+        """Lightning's ``gradient_clip_val`` (run_emission.py:72) as the clip FUSED into ``ClipAdam.step``: after the gradient
+        all-reduce, on the total gradient, as the reference's ``dp`` run clips it.  Lightning's default would clip each rank's
+        local gradient inside the closure, before the all-reduce.  Lightning 1.x passes ``optimizer_idx`` as the second
+        positional argument, 2.x does not; both pass the clip settings as keywords."""
+        if len(optimizer_idx) > 1:
+            raise TypeError('configure_gradient_clipping takes gradient_clip_val / gradient_clip_algorithm as keywords')
+        if not isinstance(optimizer, ClipAdam):
+            raise TypeError(f'configure_gradient_clipping: expected the ClipAdam of configure_optimizers, got {type(optimizer)}')
+        if gradient_clip_val and gradient_clip_algorithm == 'value':
+            raise NotImplementedError("gradient_clip_algorithm='value' is not supported by the fused optimiser step: use 'norm'")
+        optimizer.max_norm = float(gradient_clip_val) if gradient_clip_val else None
+
+    def _step_nonfinite_count(self):
+        """This step's non-finite output count (device scalar) for ``ClipAdam.step(closure)``."""
+        stats = getattr(self, 'last_stats', None)
+        return None if stats is None else stats[5:6]
 
     # sunerf.py:105-107 asserts on NaN / Inf in every step, which costs a device -> host round trip.  True (default)
     # keeps that behaviour with ONE 4-byte read per step; False defers the check to ``check_finite()`` (the optimiser

@@ -16,7 +16,9 @@ wrapper makes the script take its own single-GPU branch in every rank, without e
    ``ClipAdam.step`` -- the optimiser ``configure_optimizers`` returns -- then sums the gradient bucket (and the non-finite
    count at its tail) over the ranks before clipping, every rank applies the same update;
 3. the random generators are seeded per rank (``SUNERF_SEED``, default 0, + rank), so the ranks draw DIFFERENT ray batches from
-   the data module's shuffled loader: N times the rays per optimiser step, the reference's ``dp`` semantics;
+   the data module's shuffled loader: N times the rays per optimiser step, the reference's ``dp`` semantics.  The same seeds
+   make every rank initialise a different network; ``ClipAdam``, built by ``configure_optimizers``, broadcasts rank 0's
+   parameters before the first step, so all ranks train (and rank 0 checkpoints) one model;
 4. the script runs as ``__main__`` with the remaining arguments.
 
 Rank 0 is the only rank that should log and write checkpoints; Lightning's ``rank_zero_only`` reads ``RANK`` from the

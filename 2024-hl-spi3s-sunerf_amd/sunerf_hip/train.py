@@ -138,7 +138,11 @@ class ClipAdam(torch.optim.Optimizer):
     bias-correction step counter untouched.
 
     ``param_groups`` carries ``lr`` / ``betas`` / ``eps`` like torch's Adam, so ``ExponentialLR`` (sunerf.py:32) works
-    unchanged.  ``max_norm=None`` leaves clipping to the caller (e.g. Lightning's ``gradient_clip_val``)."""
+    unchanged.  ``max_norm=None`` leaves clipping to the caller; under data parallelism the clip must act on the all-reduced
+    gradient, so Lightning's ``gradient_clip_val`` reaches ``max_norm`` through ``BaseSuNeRFModule.configure_gradient_clipping``.
+
+    With a process group of two or more ranks, construction broadcasts the parameters from the group's first rank and
+    ``load_state_dict`` broadcasts the moments and the step counter: the replicas hold one model."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_norm: Optional[float] = None, group=None,
                  overlap: bool = False):
@@ -190,6 +194,21 @@ class ClipAdam(torch.optim.Optimizer):
                              'exp_avg_sq': self.exp_avg_sq[off:off + k].view_as(p)}
             _BUCKETS[p] = (weakref.ref(self), off, k)      # lets the backward node announce a finished slice (segment_ready)
             off += k
+        # Replicas start from ONE set of weights: ranks seeded apart (sunerf.run_mi355x) build different networks, and the
+        # all-reduced update alone would never bring them together.  The group's first rank is the source.
+        self._broadcast(self.flat_params)
+        torch.autograd.graph.increment_version(self._params)
+        # callable -> this step's non-finite output count (device scalar) or None: what step(closure) puts at the bucket's tail
+        # when no skip_if_positive is given (Lightning drives the step through a closure; configure_optimizers registers it)
+        self.nonfinite_source = None
+
+    def _broadcast(self, *tensors) -> None:
+        """Copies ``tensors`` from the group's first rank to every rank (no-op without a process group of two or more)."""
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(self.group) < 2:
+            return
+        src = 0 if self.group is None else dist.get_global_rank(self.group, 0)
+        for t in tensors:
+            dist.broadcast(t, src=src, group=self.group)
 
     @property
     def step_count(self) -> int:
@@ -251,6 +270,8 @@ class ClipAdam(torch.optim.Optimizer):
         if closure is not None:                 # torch.optim convention (Lightning's automatic optimisation passes the
             with torch.enable_grad():           # forward + backward of the step as a closure)
                 loss = closure()
+            if skip_if_positive is None and self.nonfinite_source is not None:
+                skip_if_positive = self.nonfinite_source()
         self._collect()
         if skip_if_positive is not None:
             self.nonfinite.copy_(skip_if_positive.reshape(1))
@@ -308,3 +329,4 @@ class ClipAdam(torch.optim.Optimizer):
             if len(set(steps)) != 1:
                 raise ValueError('parameters with different step counts cannot share the fused bias correction')
             self.applied_steps.fill_(steps[0])
+        self._broadcast(self.exp_avg, self.exp_avg_sq, self.applied_steps)      # the replicas' moments stay one
