@@ -1,12 +1,11 @@
 // Input side of the render path: observer rays generated on the device.
 //
-// Restates get_rays, sunerf/data/ray_sampling.py:7-36: helioprojective pixel angles (Tx, Ty) [rad] ->
-//   direction = (sin Tx, -sin Ty cos Tx, -cos Tx cos Ty)      evaluated in fp64, rounded to fp32 (np.stack(..., dtype=float32))
-//   rays_d[r] = sum_c direction[c] * c2w[r][c]               fp32 products, summed left to right (np.sum over 3 elements)
-//   rays_o    = c2w[:3, 3] tiled
+// Restates get_rays, sunerf/data/ray_sampling.py:7-36: helioprojective pixel angles (Tx, Ty) [rad] -> rays_o, rays_d
+// (the arithmetic of one pixel is sunerf_pixel_ray, ray_math.h)
 // and the per-ray time column that evaluation/loader.py:92,214 builds with ones_like(...) * time.
 // One thread per pixel; 48 bytes written per ray, nothing read but the two angles.
 #include "sunerf_common.h"
+#include "ray_math.h"
 #include "../../include/sunerf_hip.h"
 
 namespace {
@@ -26,12 +25,12 @@ __global__ __launch_bounds__(256) void observer_rays_kernel(RayArgs a) {
   const int64_t p = a.pix_begin + i;
   const double Tx = a.per_pixel ? a.tx[p] : a.tx[p % a.width];
   const double Ty = a.per_pixel ? a.ty[p] : a.ty[p / a.width];
-  const double sx = sin(Tx), cx = cos(Tx), sy = sin(Ty), cy = cos(Ty);
-  const float d0 = (float)sx, d1 = (float)(-sy * cx), d2 = (float)(-cx * cy);
+  float o[3], d[3];
+  sunerf_pixel_ray(Tx, Ty, a.c2w, o, d);
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    a.rays_d[i * 3 + r] = (d0 * a.c2w[4 * r + 0] + d1 * a.c2w[4 * r + 1]) + d2 * a.c2w[4 * r + 2];
-    a.rays_o[i * 3 + r] = a.c2w[4 * r + 3];
+    a.rays_d[i * 3 + r] = d[r];
+    a.rays_o[i * 3 + r] = o[r];
   }
   if (a.times) a.times[i] = a.time_value;
 }

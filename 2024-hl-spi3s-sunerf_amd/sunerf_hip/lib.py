@@ -88,6 +88,10 @@ _SIGNATURES = {
                                           c_f32p, c_void]),
     'sunerf_observer_rays': (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.POINTER(ctypes.c_float), ctypes.c_float, c_f32p, c_f32p, c_f32p, c_void]),
+    'sunerf_view_desc_bytes': (ctypes.c_size_t, []),
+    'sunerf_build_ray_pool': (ctypes.c_int, [c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64,
+                                              c_f32p, c_f32p, c_f32p, c_f32p, c_void]),
     'sunerf_column_rays': (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_float, c_f32p, c_f32p, c_f32p, c_void]),
     'sunerf_column_stats': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, c_f32p, c_f32p,

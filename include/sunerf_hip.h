@@ -365,6 +365,49 @@ int sunerf_observer_rays(const double* tx, const double* ty, int per_pixel, int 
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Training sets from observation images: replaces the host assembly of the reference's data modules
+ * (sunerf/data/loader/single_channel.py:44-52, multi_thermal_loader.py:54-61, 209-258) -- per-pixel rays, time broadcast,
+ * flatten, one permutation over all rays -- by one launch that writes a rank's shard of the shuffled pool.
+ *
+ * A training set is a list of views.  View k holds height x width pixels (AFTER its downscale), numbered row-major from
+ * pix_offset (views concatenated in table order: pix_offset[0] = 0, pix_offset[k+1] = pix_offset[k] + height * width),
+ * n_pixels in all.  Record `slot` of the pool is pixel  p = valid_index ? valid_index[pi(slot)] : pi(slot), where pi is a
+ * bijection of [0, n_valid) keyed by (seed, epoch) (permute == 0: the identity): cycle-walking over a 4-round balanced Feistel
+ * network on 2 b bits, b = ceil(bit_length(n_valid - 1) / 2), round function fmix32(R + k_r) & (2^b - 1) (murmur3 finaliser),
+ *   k_r = fmix32((s + 0x9e3779b9 (r + 1)) ^ fmix32(e + 0x85ebca6b (r + 1))),  s / e = lo ^ fmix32(hi + 0x9e3779b9) of the 64-bit seed / epoch,
+ * all in uint32 arithmetic (restated in numpy by tests/observations_reference.py).  No table of size n_valid, no atomics:
+ * two builds with one key are bit-identical, and the shards of one key are disjoint and complete by construction.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SUNERF_OBS_MAX_CHANNELS 16
+
+typedef struct SunerfViewDesc {
+  int64_t pix_offset;        /* number of the view's first pixel                                                       */
+  const double* tx;          /* DEVICE: column angles [width] (per_pixel == 0) or per-pixel angles [height * width]    */
+  const double* ty;          /* DEVICE: row angles [height] or per-pixel angles, of the grid AFTER the downscale       */
+  const float* image;        /* DEVICE: [n_planes, height * downscale, width * downscale], the present channels only   */
+  int32_t height, width;     /* pixels of the view after the downscale                                                 */
+  int32_t downscale;         /* f >= 1: a pixel is the mean of an f x f source block (fp64 sum, row-major, fp32 once)  */
+  int32_t per_pixel;
+  float c2w[12];             /* rows of pose_spherical(...)[:3, :4]                                                    */
+  float time;                /* normalised observation time                                                            */
+  int32_t n_planes;
+  int32_t plane[SUNERF_OBS_MAX_CHANNELS];      /* per output channel: its plane of `image`, or -1 (absent: target 0, wavelength 0) */
+  float wavelength[SUNERF_OBS_MAX_CHANNELS];   /* per output channel: the value written for a present channel                */
+} SunerfViewDesc;
+
+/*   views : DEVICE table of n_views descriptors (size of one: the function below; the caller keeps every pointer in it valid)
+ *   valid_index : DEVICE [n_valid] ascending pixel numbers, or NULL when no pixel was dropped (then n_valid == n_pixels)
+ *   records [slot_begin, slot_begin + n_slots) of the permuted set are written to the FIRST n_slots rows of
+ *   rays [n_slots, 2, 3] (origin, direction: the bits of sunerf_observer_rays for that pixel), time [n_slots, 1],
+ *   target_image [n_slots, n_channels], wavelength [n_slots, n_channels] (the last two may be NULL); outputs 16-byte aligned.
+ *   n_valid < 1 or >= 2^40, n_channels outside [1, SUNERF_OBS_MAX_CHANNELS], negative counts, slots outside [0, n_valid), null
+ *   or misaligned pointers give SUNERF_E_BADARG; n_slots == 0 does nothing. */
+size_t sunerf_view_desc_bytes(void);
+int sunerf_build_ray_pool(const SunerfViewDesc* views, int n_views, int64_t n_pixels, const int64_t* valid_index,
+                          int64_t n_valid, int n_channels, int permute, uint64_t seed, uint64_t epoch, int64_t slot_begin,
+                          int64_t n_slots, float* rays, float* time, float* target_image, float* wavelength, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Heliographic analyses: radial columns from the solar centre, one per (latitude, longitude).
  * Replaces the host-side point generation of the reference's stash scripts, sunerf/evaluation/stash/
  * topographical_map.py:36-49, topographical_profile.py:33-45, topographical_slice.py:119-130, eruption_profile.py:76-88.

@@ -1,0 +1,124 @@
+"""The reference's validation experiment in small (evaluation/image_render.py:264-293, stash/metrics_simulation.py): a ground-truth
+field is rendered from K viewpoints, a model is trained on those frames, an unseen viewpoint is compared -- every stage on the
+device.  ``--views`` frames from as many longitudes go into an ``ObservationSet`` without leaving the device; view ``K // 6`` is
+held out; the module is trained with ``fit_steps`` on the pool (``reshuffle='rays'``: a fresh permutation of all rays per epoch);
+the held-out view is scored with ``validation_metrics`` before and after.
+
+``--module dt`` (default): ``SimpleStar`` frames (7 AIA channels, the DT integral) rendered by a ``ModelLoader``
+(``add_rendered_view``), ``DensityTemperatureSuNeRFModule`` (NeRF_DT 8 x ``--d-filter``); the AIA response table comes from the
+data fixture tests/golden/g9_simple_star.npz.  ``--module emission``: frames of the analytic target of tools/mini_train.py
+(limb-darkened disk + exponential corona) evaluated on the views' own rays, ``EmissionSuNeRFModule``.  One JSON line.
+
+    python tools/closed_loop.py [--module dt|emission] [--views 8] [--size 64] [--steps 300] [--batch 2048] [--d-filter 256]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(R, '2024-hl-spi3s-sunerf_amd'))
+from sunerf.evaluation.loader import ModelLoader                                  # noqa: E402
+from sunerf.model.model import NeRF_DT                                            # noqa: E402
+from sunerf.model.stellar_model import SimpleStar                                 # noqa: E402
+from sunerf.model.sunerf import DensityTemperatureSuNeRFModule, EmissionSuNeRFModule, fit_steps   # noqa: E402
+from sunerf.rendering.density_temperature import DensityTemperatureRadiativeTransfer   # noqa: E402
+from sunerf_hip import ops                                                        # noqa: E402
+from sunerf_hip.feed import training_batches                                      # noqa: E402
+from sunerf_hip.observations import ObservationSet                                # noqa: E402
+
+WL = [94., 131., 171., 193., 211., 304., 335.]
+
+
+def held_out_scores(module, obs, batch_size):
+    (val,) = obs.validation_batches(batch_size)
+    module.validation_dataset_mapping = {0: 'test_image'}
+    module.validation_epoch_end([module.validation_step(b, i) for i, b in enumerate(val['batches'])])
+    scores = {k: float(v) for k, v in module.validation_metrics(val['image_shape']).items()}
+    stored = module.validation_outputs['test_image']
+    scores['mean_target'], scores['mean_fine_image'] = stored['target_image'].mean().item(), stored['fine_image'].mean().item()
+    return scores
+
+
+def density_temperature_problem(args, grid, poses):
+    fx = np.load(os.path.join(R, 'tests', 'golden', 'g9_simple_star.npz'))
+    table = (fx['aia_logte'], fx['aia_tresp'])
+    cfg = dict(sampling_config={'type': 'stratified', 'n_samples': 64, 'perturb': True},
+               hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 128, 'perturb': False})
+    star = DensityTemperatureRadiativeTransfer(Rs_per_ds=1, model=SimpleStar, model_config={}, response_table=table,
+                                               **{k: dict(v) for k, v in cfg.items()}).cuda()
+    with torch.no_grad():
+        for m in (star.coarse_model, star.fine_model):
+            for w in ops.AIA_WAVELENGTHS:
+                m.log_absortpion[str(w)].copy_(torch.from_numpy(fx[f'la__{w}']))
+            m.volumetric_constant.copy_(torch.from_numpy(fx['vol_c']))
+    truth = ModelLoader(rendering=star, model=star.fine_model, ref_map=grid)
+    first = truth.render_observer_image(poses[0][0], poses[0][1], 0.0, wl=np.array(WL), as_numpy=False)['image']
+    scale = 1.0 / first.abs().max().item()           # images of order one, as the reference's loaders normalise them
+    obs = ObservationSet(Rs_per_ds=1.0, seconds_per_dt=1.0, device='cuda')
+    for lat, lon in poses:
+        obs.add_rendered_view(truth, lat, lon, 0.0, wl=np.array(WL), scale=scale)
+    module = DensityTemperatureSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={}, model=NeRF_DT,
+                                            pixel_intensity_factor=1e10, response_table=table,
+                                            model_config={'d_filter': args.d_filter},
+                                            lr_config={'start': 5e-4, 'end': 5e-5, 'iterations': args.steps},
+                                            **{k: dict(v) for k, v in cfg.items()}).cuda()
+    return obs, module
+
+
+def emission_problem(args, grid, poses):
+    from sunerf.evaluation.loader import linear_plate_scale_axes
+    from sunerf_hip.rays import grid_rays, pose_spherical
+    obs = ObservationSet(Rs_per_ds=1.0, seconds_per_dt=1.0, device='cuda')
+    tx, ty = linear_plate_scale_axes(grid, None, 'cuda')
+    for lat, lon in poses:
+        o, d = grid_rays(tx, ty, pose_spherical(-lon, lat, 215.03215567054764))
+        b = torch.linalg.cross(o, d).norm(dim=-1) / d.norm(dim=-1)                        # impact parameter in solar radii
+        image = torch.where(b < 1, 0.25 * torch.sqrt((1 - b * b).clamp_min(0)) + 0.06, 0.06 * torch.exp(-(b - 1) / 0.12))
+        obs.add_view(image.reshape(args.size, args.size), lat, lon, time=0.0, grid=grid)
+    module = EmissionSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={'vmax': 1, 'a': 0.005},
+                                  sampling_config={'type': 'stratified', 'n_samples': 64, 'perturb': True},
+                                  hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 128, 'perturb': True},
+                                  model_config={'d_filter': args.d_filter},
+                                  lr_config={'start': 5e-4, 'end': 5e-5, 'iterations': args.steps}).cuda()
+    return obs, module
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--module', choices=('dt', 'emission'), default='dt')
+    ap.add_argument('--views', type=int, default=8)
+    ap.add_argument('--size', type=int, default=64)
+    ap.add_argument('--steps', type=int, default=300)
+    ap.add_argument('--batch', type=int, default=2048)
+    ap.add_argument('--d-filter', type=int, default=256)
+    args = ap.parse_args()
+    torch.manual_seed(0)
+    grid = {'shape': (args.size, args.size), 'cdelt': (2.2 * 960. / args.size, 2.2 * 960. / args.size),
+            'meta': {'t_obs': '2022-01-01T00:00:00.000'}}
+    poses = [(0.1 * (k % 3 - 1), 0.3 - 6.2832 / args.views * k) for k in range(args.views)]
+    obs, module = (density_temperature_problem if args.module == 'dt' else emission_problem)(args, grid, poses)
+    obs.hold_out('reference')
+    pool = obs.pool(batch_size=args.batch, seed=0, reshuffle='rays')
+    module.strict_finite_check = False
+    before = held_out_scores(module, obs, 1 << 14)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    losses = torch.stack(fit_steps(module, training_batches(pool, args.steps)))
+    torch.cuda.synchronize()
+    seconds = time.perf_counter() - t0
+    module.check_finite(module.optimizer)
+    after = held_out_scores(module, obs, 1 << 14)
+    print(json.dumps({'closed_loop': {
+        'module': args.module, 'views': args.views, 'held_out': obs.held_out, 'size': args.size, 'channels': pool.data['target_image'].shape[1], 'training_rays': pool.n_rays,
+        'steps': args.steps, 'batch': args.batch, 'd_filter': args.d_filter, 'epochs_built': pool.built_epoch + 1,
+        'loss_first_10': losses[:10].mean().item(), 'loss_last_10': losses[-10:].mean().item(), 'train_seconds': seconds,
+        'before': before, 'after': after}}))
+
+
+if __name__ == '__main__':
+    main()
