@@ -92,6 +92,14 @@ _SIGNATURES = {
     'sunerf_build_ray_pool': (ctypes.c_int, [c_void, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int64, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64,
                                               c_f32p, c_f32p, c_f32p, c_f32p, c_void]),
+    'sunerf_observer_desc_bytes': (ctypes.c_size_t, []),
+    'sunerf_synchronic_map': (ctypes.c_int, [c_void, ctypes.c_int, ctypes.c_int, c_void, ctypes.c_int, c_void, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_double, c_f32p, c_void, c_void, c_void]),
+    'sunerf_map_fill_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int]),
+    'sunerf_map_fill': (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double, c_void, c_void,
+                                        ctypes.c_size_t, c_void]),
+    'sunerf_reproject_views': (ctypes.c_int, [c_f32p, ctypes.c_int, c_void, ctypes.c_int, c_void, ctypes.c_int, ctypes.c_double,
+                                               c_void, ctypes.c_int, ctypes.c_int64, ctypes.c_float, c_f32p, c_void, c_void]),
     'sunerf_column_rays': (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_float, c_f32p, c_f32p, c_f32p, c_void]),
     'sunerf_column_stats': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, c_f32p, c_f32p,

@@ -371,6 +371,56 @@ class ObservationSet:
             f.flush()
         return paths
 
+    # ---------------------------------------------------------------- reprojection baseline
+    def _baseline_index(self, index: Optional[int]) -> int:
+        if index is None:
+            held = self.held_out
+            if not held:
+                raise ValueError('no view is held out: name the view (index=) or call hold_out first')
+            return held[0]
+        if not 0 <= int(index) < len(self.views):
+            raise IndexError(f'view {index} of {len(self.views)}')
+        return int(index)
+
+    def synchronic_map(self, indices: Optional[Sequence[int]] = None, **kw):
+        """The :class:`sunerf_hip.reprojection.SynchronicMap` of the training views (default: ``training_views``, so a held-out
+        view is never part of its own baseline) or of the views ``indices``; ``kw`` as ``reprojection.synchronic_map`` takes
+        them (``shape``, ``lat_range``, ``lon_range``, ``fill``, ``rank``, ``world``)."""
+        from .reprojection import synchronic_map
+        indices = self.training_views if indices is None else [int(i) for i in indices]
+        kw.setdefault('Rs_per_ds', self.Rs_per_ds)
+        return synchronic_map([self.views[i] for i in indices], **kw)
+
+    def baseline_view(self, index: Optional[int] = None, off_disk=None, **kw) -> torch.Tensor:
+        """The held-out view (the first one; or view ``index``) as the reprojection baseline predicts it: the synchronic map
+        of the training views -- without view ``index`` -- seen from that view's pose on its own (downscaled) pixel grid,
+        ``(H, W, C)`` fp32 with the set's channels.  Off the disk NaN, or ``off_disk``.  ``kw``: as :meth:`synchronic_map`."""
+        from .reprojection import Observer
+        index = self._baseline_index(index)
+        observer = Observer.of_view(self.views[index])              # (refuses per-pixel grids before anything is built)
+        indices = kw.pop('indices', None)
+        if indices is None:
+            indices = [i for i in self.training_views if i != index]
+        return self.synchronic_map(indices, **kw).reproject_many([observer], off_disk)[0]
+
+    def baseline_metrics(self, index: Optional[int] = None, data_range: float = 1.0, normalize=None, **kw) -> Dict[str, torch.Tensor]:
+        """``image_metrics`` of :meth:`baseline_view` against the view's own image, per channel the view has, as
+        ``baseline_simulation.py:35-42`` scores it: ``nan_to_num(prediction, nan=0)``, then ``normalize`` (an optional callable,
+        e.g. the scripts' asinh stretch) on both.  Keys and shapes ``(C_present,)`` as ``image_metrics``."""
+        from .metrics import image_metrics
+        index = self._baseline_index(index)
+        view = self.views[index]
+        pred = self.baseline_view(index, **kw).permute(2, 0, 1)
+        present = torch.as_tensor(np.nonzero(view.plane >= 0)[0], device=pred.device)
+        pred = torch.nan_to_num(pred.index_select(0, present), nan=0.0)
+        target = view.image
+        if view.downscale > 1:
+            f = view.downscale
+            target = (target.double().view(-1, view.height, f, view.width, f).sum((2, 4)) / float(f * f)).float()
+        if normalize is not None:
+            pred, target = normalize(pred), normalize(target)
+        return image_metrics(pred.contiguous(), target.contiguous(), data_range)
+
     @property
     def config(self) -> dict:
         """What ``save_state`` stores as ``data_config`` (single_channel.py:82-84, multi_thermal_loader.py:88-90), with ``wcs``

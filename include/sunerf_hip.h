@@ -408,6 +408,64 @@ int sunerf_build_ray_pool(const SunerfViewDesc* views, int n_views, int64_t n_pi
                           int64_t n_slots, float* rays, float* time, float* target_image, float* wavelength, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Reprojection baseline: all emission is taken to come from the sphere r = radius (1 R_sun in scene units).
+ * Replaces sunerf/baseline/reprojection.py: create_heliographic_map :52-95 (reproject_and_coadd of the views with
+ * reproject_interp, default mean, match_background=False, then nan_to_num(array, nan=nanmean(array))), transform :98-125 and
+ * load_views :128-168 (h_map.reproject_to(observer) for one observer / a grid of them through a multiprocessing.Pool).
+ * Geometry is this project's pinhole convention (the pixel direction of ray_math.h), all of it in fp64; c2w is promoted.
+ *
+ * Conventions.  Map pixel (i, j) lies at p = radius * u(lat[i], lon[j]), u = (-cos b sin l, cos b cos l, -sin b); lat / lon are
+ * ascending fp64 axes of pixel centres [rad].  A pixel with angles (Tx, Ty) of a view looks along
+ * c2w[:3,:3] (sin Tx, -sin Ty cos Tx, -cos Tx cos Ty); a camera-frame vector (x, y, z) = c2w[:3,:3]^-1 (p - o), o = c2w[:, 3],
+ * has Tx = atan2(x, hypot(y, z)), Ty = atan2(-y, -z) (the inverse by cofactors in fp64, not the transpose: the fp32 pose is
+ * orthonormal to 1e-7 only, and a pixel's own surface point must come back to the pixel).  The fractional pixel coordinate of an angle on an axis: binary search
+ * for the interval, linear interpolation inside it (linear extrapolation of the end intervals outside the axis); ascending or
+ * descending, uniform or not; an axis of one pixel covers its own angle only (any other angle: NaN).
+ * Bilinear sample of an n_y x n_x plane at (y, x): NaN outside [0, n_y - 1] x [0, n_x - 1]; inside i0 = floor, i1 = min(i0 + 1,
+ * n - 1) and the four-term weighted sum in fp64 of the fp32 taps -- scipy.ndimage.map_coordinates(order=1, mode='constant',
+ * cval=nan).  With downscale f > 1 a tap is the block mean the pool kernel forms (fp64 sum, row-major, / f^2, fp32 once).
+ *
+ * sunerf_synchronic_map: rows [row_begin, row_begin + n_rows) of the n_lat x n_lon map from n_views views.  A per_pixel view
+ *   has no closed inverse: the table is on the device, so the entry point cannot see it -- the binding refuses such views with
+ *   an error and the kernel lets one cover nothing.  View v covers channel c of a pixel iff p . o - radius^2 > 0 (p is the near
+ *   intersection of its own line of sight), the view has the channel, and the sample is not NaN.
+ *     map [n_channels][n_rows][n_lon] fp32 = fp64 sum of the covering samples in view order / their number, NaN where none
+ *     footprint [n_channels][n_rows][n_lon] int32 = number of covering views
+ *     coords (NULL, or n_views == 1) [3][n_rows][n_lon] fp64 = x, y on the view's axes and p . o - radius^2
+ * sunerf_map_fill: nan_to_num(map, nan=nanmean(map)) per channel of map [n_channels][n_pixels].  mode 0: only the statistics;
+ *   1: NaNs become the channel's mean; 2: NaNs become `value`.  stats [n_channels][2] fp64 (device) = mean of the non-NaN
+ *   pixels (NaN if there are none), their number.  Two launches, per-workgroup fp64 partial sums in `workspace`
+ *   (the size the workspace function returns, 8-byte aligned) added in a fixed order: no atomics, bit-identical reruns.
+ * sunerf_reproject_views: the map seen by n_observers observers, pixel p of observer k = row * width + col numbered from
+ *   pix_offset (observers concatenated as views are).  Per pixel: unit direction d as above, c = o x d, on the disk iff
+ *   m = radius^2 - |c|^2 > 0 and o . d < 0, near point p = o + d (-(o . d) - sqrt(m)), lat = atan2(-p_z, hypot(p_x, p_y)),
+ *   lon = atan2(-p_x, p_y) brought into [lon[0], lon[0] + 2 pi), bilinear sample of every channel of map [n_channels][n_lat][n_lon].
+ *     out [n_pixels][n_channels] fp32 (16-byte aligned): NaN outside the map's axes; off the disk `off_disk` (pass NaN for
+ *     the reference's behaviour);  coords (may be NULL) [3][n_pixels] fp64 = x (longitude axis), y (latitude axis), m / radius^2
+ * Null pointers, non-positive shapes, n_channels outside [1, SUNERF_OBS_MAX_CHANNELS], rows outside the map, radius that is
+ * not > 0 and finite, coords with n_views != 1, a mode outside 0..2 give SUNERF_E_BADARG; a small workspace SUNERF_E_WORKSPACE.
+ * Monotone axes are the caller's responsibility.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct SunerfObserverDesc {
+  int64_t pix_offset;        /* number of the observer's first pixel                                                   */
+  const double* tx;          /* DEVICE: column angles [width]                                                          */
+  const double* ty;          /* DEVICE: row angles [height]                                                            */
+  int32_t height, width;
+  float c2w[12];             /* rows of pose_spherical(...)[:3, :4]                                                    */
+} SunerfObserverDesc;
+
+size_t sunerf_observer_desc_bytes(void);
+int sunerf_synchronic_map(const SunerfViewDesc* views, int n_views, int n_channels, const double* lat, int n_lat,
+                          const double* lon, int n_lon, int row_begin, int n_rows, double radius, float* map, int32_t* footprint,
+                          double* coords, void* stream);
+size_t sunerf_map_fill_workspace_bytes(int n_channels);
+int sunerf_map_fill(float* map, int n_channels, int64_t n_pixels, int mode, double value, double* stats, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int sunerf_reproject_views(const float* map, int n_channels, const double* lat, int n_lat, const double* lon, int n_lon,
+                           double radius, const SunerfObserverDesc* observers, int n_observers, int64_t n_pixels,
+                           float off_disk, float* out, double* coords, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Heliographic analyses: radial columns from the solar centre, one per (latitude, longitude).
  * Replaces the host-side point generation of the reference's stash scripts, sunerf/evaluation/stash/
  * topographical_map.py:36-49, topographical_profile.py:33-45, topographical_slice.py:119-130, eruption_profile.py:76-88.

@@ -1,0 +1,420 @@
+"""CPU-only checks of the reprojection baseline: the numpy restatement (tests/reprojection_reference.py) against
+scipy and against an analytic truth, its own rounding noise and the decision margins of the GPU tests' inputs, the C entry
+points' argument checks and the host side of ``sunerf_hip.reprojection``.  The kernels are compared with the restatement in
+tests/test_gpu_reprojection.py."""
+import os
+import re
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+import reprojection_reference as ref
+from conftest import load_golden
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N_RANDOM_CASES = 24
+LEAVE_OUT_CAP = 1e-4
+
+
+@pytest.fixture(scope='module')
+def lib():
+    import sunerf_hip
+    if not os.path.exists(sunerf_hip.LIB_PATH):
+        import subprocess
+        subprocess.check_call(['bash', os.path.join(ROOT, '2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh')])
+    return sunerf_hip.load()
+
+
+# ---------------------------------------------------------------------------------------------- 1. the bilinear sample
+def test_bilinear_sample_is_scipys_map_coordinates():
+    from scipy.ndimage import map_coordinates
+    rng = np.random.default_rng(0)
+    for shape in ((17, 23), (2, 2), (1, 9), (9, 1), (64, 3)):
+        plane = (rng.uniform(0.0, 2.0, size=shape) * 10.0 ** rng.integers(-3, 4, size=shape)).astype(np.float32)
+        y = rng.uniform(-1.0, shape[0], size=4000)
+        x = rng.uniform(-1.0, shape[1], size=4000)
+        got = ref.bilinear(plane, y, x)
+        want = map_coordinates(plane.astype(np.float64), [y, x], order=1, mode='constant', cval=np.nan)
+        assert np.array_equal(np.isnan(got), np.isnan(want)), shape
+        ok = ~np.isnan(want)
+        assert ok.sum() > 100 or min(shape) == 1
+        assert (np.abs(got[ok] - want[ok]) <= 1e-12 * np.abs(want[ok])).all(), (shape, np.abs(got[ok] / want[ok] - 1).max())
+
+
+def test_bilinear_edge_cases_exactly():
+    from scipy.ndimage import map_coordinates
+    plane = np.arange(12, dtype=np.float32).reshape(3, 4) + 0.5
+
+    def both(p, y, x):
+        got = ref.bilinear(p, np.float64(y), np.float64(x))
+        want = map_coordinates(np.asarray(p, dtype=np.float64), [[y], [x]], order=1, mode='constant', cval=np.nan)[0]
+        assert (np.isnan(got) and np.isnan(want)) or got == want, (y, x, got, want)
+        return got
+    assert both(plane, 2, 1.25) == 8.5 + 1.25 and both(plane, 0.5, 3) == 0.5 * (3.5 + 7.5)       # last row / last column
+    assert both(plane, 2, 3) == 11.5 and both(plane, 0, 0) == 0.5
+    for y, x in ((-1e-9, 1), (1, -1e-9), (2 + 1e-9, 1), (1, 3 + 1e-9), (np.nan, 1), (1, np.nan)):      # just outside
+        assert np.isnan(both(plane, y, x))
+    holed = plane.copy()
+    holed[2, 1] = np.nan                                         # the tap at i0 + 1 with weight 0 still gives NaN
+    assert np.isnan(both(holed, 1, 1)) and np.isnan(both(holed, 1.5, 1)) and both(holed, 1, 2) == 6.5
+    assert np.isnan(both(holed, 2, 0.5)) and both(holed, 0.5, 1) == 0.5 * (1.5 + 5.5)
+    infinite = plane.copy()
+    infinite[0, 1] = np.inf
+    assert both(infinite, 0, 1) == np.inf and np.isnan(both(infinite, 0, 0)) and both(infinite, 0.25, 1.5) == np.inf
+    one = np.float32([[7.25]])                                   # 1 x 1: its own centre only
+    assert both(one, 0, 0) == 7.25 and np.isnan(both(one, 0, 1e-9)) and np.isnan(both(one, -1e-9, 0))
+    row = np.float32([[1, 2, 4, 8]])                             # 1 x n
+    assert both(row, 0, 2.5) == 6.0 and both(row, 0, 3) == 8.0 and np.isnan(both(row, 0.001, 1))
+
+
+def test_axis_coordinate():
+    uniform = np.linspace(-3e-3, 5e-3, 9)
+    bent = np.cumsum([0.0, 1.0, 0.5, 2.0, 0.25]) * 1e-3 - 1e-3
+    for axis in (uniform, uniform[::-1].copy(), bent, bent[::-1].copy()):
+        n = axis.shape[0]
+        assert np.array_equal(ref.axis_coord(axis, axis), np.arange(n))                   # pixel centres: exactly
+        mid = 0.5 * (axis[1:] + axis[:-1])
+        assert np.allclose(ref.axis_coord(axis, mid), np.arange(n - 1) + 0.5, rtol=0, atol=1e-12)
+        below, above = axis[0] - 0.5 * (axis[1] - axis[0]), axis[-1] + 0.25 * (axis[-1] - axis[-2])
+        assert np.allclose(ref.axis_coord(axis, [below, above]), [-0.5, n - 0.75], rtol=0, atol=1e-12)      # extrapolated
+        assert np.isnan(ref.axis_coord(axis, np.nan))
+    assert ref.axis_coord(np.array([2e-4]), 2e-4) == 0 and np.isnan(ref.axis_coord(np.array([2e-4]), 2.0000001e-4))
+
+
+# ------------------------------------------------------------------------------- 2. the inverse of the pixel direction
+@pytest.mark.parametrize('pose', ['a', 'b'])
+def test_inverse_projection_returns_the_pixel_index(pose):
+    """Direction -> surface point -> (x, y) on fixture g8's axis grid, for both of its poses: the pixel's own index, within
+    8 x the restatement's fp64-vs-long-double noise on this very computation (floored as the GPU tests' bound is)."""
+    from sunerf_hip.rays import pose_spherical
+    g = load_golden('g8_observer_rays')
+    tx, ty = g['tx_axis'].double().numpy(), g['ty_axis'].double().numpy()
+    theta, phi, radius, sx, sy, sz, has_shift = [float(v) for v in g[f'pose_{pose}']]
+    c2w = pose_spherical(theta, phi, radius, (sx, sy, sz) if has_shift else None)[:3, :4].numpy()
+    view = dict(tx=tx, ty=ty, c2w=c2w)
+    out = {}
+    for dtype in (np.float64, np.longdouble):
+        p, _, on_disk = ref.surface_points(view, 1.0, dtype)
+        x, y, margin = ref.view_coords(view, np.stack(p, -1), 1.0, dtype)
+        out[dtype] = (x, y)
+        assert on_disk.sum() > 0.2 * on_disk.size and (margin[on_disk] > 0).all()
+    noise = max(ref.coordinate_noise(out[np.float64][k][on_disk], out[np.longdouble][k][on_disk]) for k in (0, 1))
+    bound = ref.coordinate_bound(noise, tx.shape[0], ty.shape[0])
+    cols, rows = np.meshgrid(np.arange(tx.shape[0]), np.arange(ty.shape[0]))
+    ex = np.abs(out[np.float64][0] - cols)[on_disk].max()
+    ey = np.abs(out[np.float64][1] - rows)[on_disk].max()
+    print(f'pose {pose}: {on_disk.sum()} pixels on the disk, |x - col| <= {ex:.2e}, |y - row| <= {ey:.2e}, noise {noise:.2e}, bound {bound:.2e}')
+    assert ex <= bound and ey <= bound
+
+
+# ------------------------------------------------------------------------------------------- 3. second-order convergence
+def _analytic_views(n, a, poses, fov):
+    from sunerf_hip.rays import pose_spherical
+    axis = np.linspace(-fov / 2, fov / 2, n)
+    views = []
+    for lat, lon, dist in poses:
+        v = dict(tx=axis, ty=axis, c2w=pose_spherical(-lon, lat, dist)[:3, :4].numpy(), wavelengths=[193.], downscale=1)
+        p, _, on_disk = ref.surface_points(v, 1.0)
+        g = 1.0 + (a[0] * p[0] + a[1] * p[1] + a[2] * p[2])
+        v['planes'] = np.where(on_disk, g, np.nan).astype(np.float64)[None]       # analytic, fp64: no fp32 rounding of the taps
+        views.append(v)
+    return views
+
+
+def test_map_converges_at_second_order():
+    """g(u) = 1 + a . u on the sphere, three views holding g at every pixel's surface point: the map's maximum error over the
+    pixels that every covering view sees at mu >= 0.5 falls by a factor of 4 (between 3 and 5) per halving of the pixel size."""
+    a = (0.3, -0.2, 0.25)
+    poses = [(0.1, 0.3, 215.0), (-0.15, 2.2, 215.0), (0.05, -1.9, 215.0)]
+    fov = 2400. * np.pi / 180. / 3600.
+    lat, lon = ref.map_axes('full')
+    points = ref.column_points(lat, lon, 1.0)
+    truth = 1.0 + (a[0] * points[..., 0] + a[1] * points[..., 1] + a[2] * points[..., 2])
+    errors = []
+    for n in (32, 64, 128):
+        views = _analytic_views(n, a, poses, fov)
+        total, count, keep = np.zeros(truth.shape), np.zeros(truth.shape, dtype=int), np.ones(truth.shape, dtype=bool)
+        for v in views:
+            x, y, margin = ref.view_coords(v, points, 1.0)
+            value = _bilinear64(v['planes'][0], y, x)
+            covers = (margin > 0) & ~np.isnan(value)
+            o = v['c2w'][:, 3].astype(np.float64)
+            mu = (points @ o) / np.linalg.norm(o)
+            total += np.where(covers, value, 0.)
+            count += covers
+            keep &= ~covers | (mu >= 0.5)
+        keep &= count > 0
+        assert keep.sum() > 2000
+        errors.append(np.abs(total[keep] / count[keep] - truth[keep]).max())
+    factors = [errors[0] / errors[1], errors[1] / errors[2]]
+    print('max errors', ['%.3e' % e for e in errors], 'factors', ['%.2f' % f for f in factors])
+    assert all(3.0 <= f <= 5.0 for f in factors), (errors, factors)
+
+
+def _bilinear64(plane, y, x):
+    """:func:`reprojection_reference.bilinear` on an fp64 plane (the restatement's takes fp32 taps): the same weights."""
+    ny, nx = plane.shape
+    with np.errstate(invalid='ignore'):
+        inside = (y >= 0) & (y <= ny - 1) & (x >= 0) & (x <= nx - 1)
+    ys, xs = np.where(inside, y, 0.), np.where(inside, x, 0.)
+    y0, x0 = np.floor(ys).astype(int), np.floor(xs).astype(int)
+    y1, x1 = np.minimum(y0 + 1, ny - 1), np.minimum(x0 + 1, nx - 1)
+    wy, wx = ys - y0, xs - x0
+    value = (((1 - wy) * (1 - wx) * plane[y0, x0] + (1 - wy) * wx * plane[y0, x1]) + wy * (1 - wx) * plane[y1, x0]) + wy * wx * plane[y1, x1]
+    return np.where(inside, value, np.nan)
+
+
+# ------------------------------------------------------------------- 4. + 5. noise and margins of the GPU tests' inputs
+def test_noise_and_decision_margins_of_the_gpu_inputs():
+    """The restatement alone must leave no pixel of the GPU tests' fixed inputs undecided, so that those tests compare every
+    pixel; its fp64-vs-long-double noise per case is printed (it sets the GPU tests' coordinate bounds)."""
+    _, views = ref.observation_set(ref.view_specs(), 'cpu')
+    if not ref.LONG_DOUBLE_IS_WIDER:
+        print('np.longdouble is no wider than fp64 here: the noise reads 0 and the floor of the bound applies')
+    for name in ref.MAPS:
+        lat, lon = ref.map_axes(name)
+        points, wide = ref.column_points(lat, lon, 1.0), ref.column_points(lat, lon, 1.0, np.longdouble)
+        for k, v in enumerate(views):
+            undecided, rel, edge = ref.view_margins(v, lat, lon, 1.0)
+            x, y, _ = ref.view_coords(v, points, 1.0)
+            xw, yw, _ = ref.view_coords(v, wide, 1.0, np.longdouble)
+            print(f'map {name} view {k}: noise {max(ref.coordinate_noise(x, xw), ref.coordinate_noise(y, yw)):.2e} view pixels, '
+                  f'min |p.o - R^2| / (R |o|) {rel:.2e}, min edge distance {edge:.2e}')
+            assert undecided.sum() == 0, (name, k, int(undecided.sum()))
+            if len(v['tx']) == 1 and len(v['ty']) == 1:
+                assert np.isnan(x).all() or np.isnan(y).all() or not (np.isfinite(x) & np.isfinite(y)).any()   # the point hull is never hit
+        image = ref.synchronic_map(views, lat, lon, 1.0)['map']
+        for oname, specs in ref.observer_specs().items():
+            noise, least_m, least_edge = 0.0, np.inf, np.inf
+            for spec in specs:
+                o = ref.observer_dict(spec)
+                undecided, m, edge = ref.observer_margins(o, image, lat, lon, 1.0)
+                assert undecided.sum() == 0, (name, oname, int(undecided.sum()))
+                x, y, _, _ = ref.observer_coords(o, lat, lon, 1.0)
+                xw, yw, _, _ = ref.observer_coords(o, lat, lon, 1.0, np.longdouble)
+                noise = max(noise, ref.coordinate_noise(x, xw), ref.coordinate_noise(y, yw))
+                least_m, least_edge = min(least_m, m), min(least_edge, edge)
+            print(f'map {name} observers {oname}: noise {noise:.2e} map pixels, min |1 - |c|^2 / R^2| {least_m:.2e}, '
+                  f'min edge distance {least_edge:.2e}')
+
+
+def test_random_cases_leave_out_few_samples():
+    """The randomised sweep may leave out samples inside the margins: at most 1e-4 of a case's pixels."""
+    for seed in range(N_RANDOM_CASES):
+        case = ref.random_case(seed)
+        _, views = ref.observation_set(case['views'], 'cpu')
+        radius = 1.0 / case['Rs_per_ds']
+        m = case['map']
+        lat = np.linspace(m['lat_range'][0], m['lat_range'][1], m['shape'][0])
+        lon = np.linspace(m['lon_range'][0], m['lon_range'][1], m['shape'][1])
+        left_out = np.zeros(m['shape'], dtype=bool)
+        for v in views:
+            left_out |= ref.view_margins(v, lat, lon, radius)[0]
+        image = ref.synchronic_map(views, lat, lon, radius)['map']
+        o = ref.observer_dict(case['observer'])
+        left_out_view = ref.observer_margins(o, image, lat, lon, radius)[0]
+        covered = float((~np.isnan(image)).mean())
+        print(f'case {seed}: {len(views)} views, map {m["shape"]}, covered {covered:.3f}, left out {int(left_out.sum())} of '
+              f'{left_out.size} map pixels, {int(left_out_view.sum())} of {left_out_view.size} observer pixels')
+        assert left_out.sum() <= LEAVE_OUT_CAP * left_out.size and left_out_view.sum() <= LEAVE_OUT_CAP * left_out_view.size
+
+
+# ----------------------------------------------------------------------------------------------- 6. the entry points
+NEW_SYMBOLS = ('sunerf_synchronic_map', 'sunerf_reproject_views', 'sunerf_map_fill', 'sunerf_map_fill_workspace_bytes',
+               'sunerf_observer_desc_bytes')
+
+
+def test_entry_points_are_declared_bound_and_exported(lib):
+    import sunerf_hip
+    from sunerf_hip.lib import _SIGNATURES
+    from sunerf_hip.observations import VIEW_DESC
+    from sunerf_hip.reprojection import OBSERVER_DESC
+    header = open(os.path.join(ROOT, 'include', 'sunerf_hip.h')).read()
+    for name in NEW_SYMBOLS:
+        declaration = re.search(r'^(?:int|size_t)\s+' + name + r'\s*\(([^;]*)\)\s*;', header, re.M)
+        assert declaration and name in sunerf_hip.EXPORTED_SYMBOLS and getattr(lib, name) is not None, name
+        params = declaration.group(1).strip()
+        n_params = 0 if params == 'void' else params.count(',') + 1
+        assert n_params == len(_SIGNATURES[name][1]), (name, n_params, len(_SIGNATURES[name][1]))
+    assert re.search(r'#define\s+SUNERF_ABI_VERSION\s+9\b', header) and lib.sunerf_abi_version() == 9
+    assert lib.sunerf_observer_desc_bytes() == OBSERVER_DESC.itemsize == 80
+    assert lib.sunerf_view_desc_bytes() == VIEW_DESC.itemsize == 232          # layout unchanged
+    assert lib.sunerf_map_fill_workspace_bytes(1) == 128 * 2 * 8 and lib.sunerf_map_fill_workspace_bytes(16) == 16 * 128 * 2 * 8
+    assert lib.sunerf_map_fill_workspace_bytes(0) == 0 and lib.sunerf_map_fill_workspace_bytes(17) == 0
+
+
+def test_argument_errors_without_gpu(lib):
+    """Refused before anything touches a device (the pointers below are never dereferenced on the host)."""
+    p = 0x1000          # non-null, 16-byte aligned stand-in
+
+    def smap(views=p, n_views=2, channels=1, lat=p, n_lat=10, lon=p, n_lon=20, begin=0, n_rows=10, radius=1.0, out=p, fp=p,
+             coords=None):
+        return lib.sunerf_synchronic_map(views, n_views, channels, lat, n_lat, lon, n_lon, begin, n_rows, radius, out, fp, coords, None)
+    assert smap(views=None) == -1 and smap(lat=None) == -1 and smap(lon=None) == -1 and smap(out=None) == -1 and smap(fp=None) == -1
+    assert smap(n_views=0) == -1 and smap(n_lat=0) == -1 and smap(n_lon=-2) == -1
+    assert smap(channels=0) == -1 and smap(channels=17) == -1
+    assert smap(radius=0.0) == -1 and smap(radius=-1.0) == -1 and smap(radius=float('nan')) == -1 and smap(radius=float('inf')) == -1
+    assert smap(begin=-1) == -1 and smap(n_rows=-1) == -1 and smap(begin=5, n_rows=6) == -1 and smap(begin=11, n_rows=0) == -1
+    assert smap(coords=p) == -1                                   # coordinates are those of ONE view
+    assert smap(n_rows=0) == 0 and smap(begin=10, n_rows=0) == 0 and smap(n_rows=0, out=None, fp=None) == 0      # nothing to do
+
+    def fill(image=p, channels=1, n=100, mode=1, stats=p, ws=p, nbytes=1 << 20):
+        return lib.sunerf_map_fill(image, channels, n, mode, 0.0, stats, ws, nbytes, None)
+    assert fill(image=None) == -1 and fill(stats=None) == -1 and fill(ws=None) == -1 and fill(n=0) == -1
+    assert fill(channels=0) == -1 and fill(channels=17) == -1 and fill(mode=-1) == -1 and fill(mode=3) == -1
+    assert fill(stats=p + 4) == -1 and fill(ws=p + 4) == -1
+    assert fill(nbytes=128 * 2 * 8 - 1) == -3 and fill(channels=2, nbytes=128 * 2 * 8) == -3
+
+    def views(image=p, channels=1, lat=p, n_lat=10, lon=p, n_lon=20, radius=1.0, obs=p, n_obs=1, n=64, out=p):
+        return lib.sunerf_reproject_views(image, channels, lat, n_lat, lon, n_lon, radius, obs, n_obs, n, float('nan'), out, None, None)
+    assert views(image=None) == -1 and views(lat=None) == -1 and views(lon=None) == -1 and views(obs=None) == -1 and views(out=None) == -1
+    assert views(n_lat=0) == -1 and views(n_lon=0) == -1 and views(n_obs=0) == -1 and views(n=0) == -1 and views(n=-4) == -1
+    assert views(channels=0) == -1 and views(channels=17) == -1 and views(radius=0.0) == -1 and views(radius=float('nan')) == -1
+    assert views(out=p + 4) == -1                                 # 16-byte alignment of the output rows
+
+
+# ------------------------------------------------------------------------------------------------ 7. the Python side
+def _cpu_set(n_views=7, per_pixel_at=None):
+    from sunerf_hip.observations import ObservationSet
+    obs = ObservationSet(device='cpu')
+    for k in range(n_views):
+        if k == per_pixel_at:
+            tx, ty = np.meshgrid(np.linspace(-5e-3, 5e-3, 8), np.linspace(-5e-3, 5e-3, 8))
+            obs.add_view(torch.zeros(8, 8), 0.1, 0.5 * k, 215.0, tx=tx, ty=ty)
+        else:
+            obs.add_view(torch.zeros(8, 8), 0.1, 0.5 * k, 215.0, grid={'shape': (8, 8), 'cdelt': (300., 300.)})
+    return obs
+
+
+def test_per_pixel_views_are_refused():
+    from sunerf_hip.reprojection import Observer, synchronic_map
+    obs = _cpu_set(3, per_pixel_at=1)
+    with pytest.raises(ValueError, match='per-pixel'):
+        synchronic_map(obs.views)
+    with pytest.raises(ValueError, match='per-pixel'):
+        obs.synchronic_map()
+    with pytest.raises(ValueError, match='per-pixel'):
+        Observer.of_view(obs.views[1])
+    with pytest.raises(ValueError, match='per-pixel'):
+        obs.baseline_view(1)
+    with pytest.raises(ValueError):
+        synchronic_map([])
+
+
+def test_there_is_no_cpu_path():
+    from sunerf_hip.lib import SunerfHipError
+    from sunerf_hip.reprojection import SynchronicMap, fill_map, synchronic_map
+    obs = _cpu_set(3)
+    with pytest.raises(SunerfHipError):
+        synchronic_map(obs.views, shape=(8, 16))
+    with pytest.raises(SunerfHipError):
+        fill_map(torch.zeros(1, 4, 4))
+    m = SynchronicMap(torch.zeros(1, 4, 8), torch.zeros(1, 4, 8, dtype=torch.int32), torch.linspace(-1, 1, 4, dtype=torch.float64),
+                      torch.linspace(-3, 3, 8, dtype=torch.float64), 1.0, np.float32([193.]), 1.0, torch.zeros(1))
+    with pytest.raises(SunerfHipError):
+        m.reproject(0., 0., 215., grid={'shape': (8, 8), 'cdelt': (300., 300.)})
+
+
+def test_argument_checks_of_the_python_side():
+    from sunerf_hip.reprojection import Observer, map_axes, synchronic_map
+    obs = _cpu_set(3)
+    for kw in (dict(shape=(0, 8)), dict(lat_range=(0.5, 0.5)), dict(lon_range=(1.0, -1.0)), dict(Rs_per_ds=0.0), dict(fill='median')):
+        with pytest.raises(ValueError):
+            synchronic_map(obs.views, **kw)
+    obs = _cpu_set(2)
+    obs.add_view(torch.zeros(8, 8), 0.1, 0.2, 215.0, tx=[0.0, 1e-3, 1e-3, 2e-3, 3e-3, 4e-3, 5e-3, 6e-3],       # not strictly monotone
+                 ty=np.linspace(-4e-3, 4e-3, 8))
+    with pytest.raises(ValueError, match='monotone'):
+        synchronic_map(obs.views)
+    with pytest.raises(ValueError):
+        Observer(0., 0., 215.)
+    lat, lon = map_axes()                                          # the reference's default shape, both ends included
+    assert lat.shape == (1024,) and lon.shape == (2048,) and lat[0] == -np.pi / 2 and lat[-1] == np.pi / 2 and lon[-1] == np.pi
+    lat, lon = map_axes((5, 9), (-0.5, 0.5), (0.0, 2.0))
+    assert np.array_equal(lat, np.linspace(-0.5, 0.5, 5)) and np.array_equal(lon, np.linspace(0.0, 2.0, 9))
+
+
+def test_default_indices_exclude_the_held_out_view(monkeypatch):
+    import sunerf_hip.reprojection as rp
+    obs = _cpu_set(7)
+    obs.hold_out('reference')
+    seen = []
+
+    class FakeMap:
+        def reproject_many(self, observers, off_disk=None):
+            seen.append(('observers', [o.c2w for o in observers], off_disk))
+            return [torch.zeros(8, 8, 1)]
+
+    def fake(views, **kw):
+        seen.append(('views', [v.name for v in views], kw))
+        return FakeMap()
+    monkeypatch.setattr(rp, 'synchronic_map', fake)
+    obs.synchronic_map(shape=(4, 8))
+    assert seen[-1] == ('views', ['view0', 'view2', 'view3', 'view4', 'view5', 'view6'], {'shape': (4, 8), 'Rs_per_ds': 1.0})
+    obs.synchronic_map([1, 3])
+    assert seen[-1][1] == ['view1', 'view3']
+    out = obs.baseline_view(off_disk=0.0)
+    assert out.shape == (8, 8, 1) and seen[-2][1] == ['view0', 'view2', 'view3', 'view4', 'view5', 'view6']
+    assert seen[-1][0] == 'observers' and torch.equal(seen[-1][1][0], obs.views[1].c2w) and seen[-1][2] == 0.0
+    obs.baseline_view(4)                                          # a named training view is left out of its own baseline too
+    assert seen[-2][1] == ['view0', 'view2', 'view3', 'view5', 'view6']
+    obs.hold_out(None)
+    with pytest.raises(ValueError):
+        obs.baseline_view()
+    with pytest.raises(IndexError):
+        obs.baseline_view(9)
+
+
+def test_view_grid_is_load_views_grid():
+    from sunerf_hip.reprojection import view_grid_coordinates
+    coords = view_grid_coordinates(10)
+    assert coords.shape == (19 * 37, 2) and coords.dtype == np.float32
+    assert coords[0].tolist() == [-90., 0.] and coords[1].tolist() == [-90., 10.] and coords[-1].tolist() == [90., 360.]
+    assert np.array_equal(coords.reshape(19, 37, 2)[:, 0, 0], np.arange(-90, 91, 10))
+    assert view_grid_coordinates(60).shape == (4 * 7, 2)
+
+
+def test_mirror_module_routes_to_the_device_code(monkeypatch):
+    import sunerf.baseline.reprojection as mirror
+    import sunerf_hip.reprojection as rp
+    assert mirror.synchronic_map is rp.synchronic_map
+    for name in ('create_heliographic_map', 'transform', 'load_views'):
+        assert callable(getattr(mirror, name))
+    obs = _cpu_set(3)
+    calls = []
+
+    class FakeMap:
+        def reproject(self, lat, lon, distance, **kw):
+            calls.append(('reproject', lat, lon, distance, sorted(kw)))
+            return 'view'
+
+        def view_grid(self, strides, distance, **kw):
+            calls.append(('view_grid', strides, sorted(kw)))
+            yield (0., 0.), 'view'
+
+    def fake(views, **kw):
+        calls.append(('map', len(views), kw))
+        return FakeMap()
+    monkeypatch.setattr(mirror, 'synchronic_map', fake)
+    assert isinstance(mirror.create_heliographic_map(*obs.views), FakeMap)
+    assert calls[-1] == ('map', 3, {'shape': (1024, 2048), 'Rs_per_ds': 1.0})             # the reference's default shape
+    assert mirror.transform(*obs.views, lat=0.1, lon=0.2, distance=215.0) == 'view'
+    assert calls[-1][:4] == ('reproject', 0.1, 0.2, 215.0)
+    assert list(mirror.load_views(*obs.views, strides=30)) == [((0., 0.), 'view')] and calls[-1][:2] == ('view_grid', 30)
+    assert list(mirror.load_views(*obs.views, resolution=(4, 4)))[0][1] == 'view' and 'grid' in calls[-1][2]
+    assert 'not built' in mirror.__doc__.lower()
+
+
+def test_low_coverage_warns_as_the_reference_logs(monkeypatch):
+    import sunerf_hip.reprojection as rp
+    monkeypatch.setattr(rp, 'fill_map', lambda image, fill: torch.tensor([[0.5, 3.0]], dtype=torch.float64))
+    image = torch.zeros(1, 2, 4)
+    with pytest.warns(UserWarning, match='50 percent'):
+        m = rp.finish_map(image, None, None, None, 1.0, None)
+    assert m.covered_fraction == 3 / 8 and m.fill_value.tolist() == [0.5]
+    monkeypatch.setattr(rp, 'fill_map', lambda image, fill: torch.tensor([[0.5, 4.0]], dtype=torch.float64))
+    with warnings.catch_warnings():
+        warnings.simplefilter('error')
+        assert rp.finish_map(image, None, None, None, 1.0, None).covered_fraction == 0.5

@@ -9,7 +9,11 @@ the held-out view is scored with ``validation_metrics`` before and after.
 data fixture tests/golden/g9_simple_star.npz.  ``--module emission``: frames of the analytic target of tools/mini_train.py
 (limb-darkened disk + exponential corona) evaluated on the views' own rays, ``EmissionSuNeRFModule``.  One JSON line.
 
-    python tools/closed_loop.py [--module dt|emission] [--views 8] [--size 64] [--steps 300] [--batch 2048] [--d-filter 256]
+``--baseline``: also the reprojection baseline of the held-out view (``ObservationSet.baseline_metrics``: the synchronic map of
+the training views seen from the held-out pose), scored as ``validation_metrics`` scores the model -- the same
+images, the MSE over all channels, the SSIM of channel 0 -- and printed next to the model's scores.
+
+    python tools/closed_loop.py [--module dt|emission] [--views 8] [--size 64] [--steps 300] [--batch 2048] [--d-filter 256] [--baseline]
 """
 import argparse
 import json
@@ -42,6 +46,16 @@ def held_out_scores(module, obs, batch_size):
     stored = module.validation_outputs['test_image']
     scores['mean_target'], scores['mean_fine_image'] = stored['target_image'].mean().item(), stored['fine_image'].mean().item()
     return scores
+
+
+def baseline_scores(module, obs):
+    """What the surface assumption alone reaches on the held-out view, under the scoring of ``validation_metrics``."""
+    def as_scored(planes):                                                 # (C, H, W) -> the images the callback scores
+        image = planes.permute(1, 2, 0)
+        return module._validation_images(image, image)[0].permute(2, 0, 1)
+    scores = obs.baseline_metrics(data_range=1.0, normalize=as_scored)
+    loss = scores['mse'].mean()
+    return {'baseline.loss': loss.item(), 'baseline.ssim': scores['ssim'][0].item(), 'baseline.psnr': (-10. * torch.log10(loss)).item()}
 
 
 def density_temperature_problem(args, grid, poses):
@@ -96,6 +110,7 @@ def main():
     ap.add_argument('--steps', type=int, default=300)
     ap.add_argument('--batch', type=int, default=2048)
     ap.add_argument('--d-filter', type=int, default=256)
+    ap.add_argument('--baseline', action='store_true')
     args = ap.parse_args()
     torch.manual_seed(0)
     grid = {'shape': (args.size, args.size), 'cdelt': (2.2 * 960. / args.size, 2.2 * 960. / args.size),
@@ -113,11 +128,15 @@ def main():
     seconds = time.perf_counter() - t0
     module.check_finite(module.optimizer)
     after = held_out_scores(module, obs, 1 << 14)
+    baseline = baseline_scores(module, obs) if args.baseline else None
+    if baseline is not None:
+        print(f"held-out view {obs.held_out[0]}: model PSNR {after['validation.psnr']:.2f} dB, SSIM {after['validation.ssim']:.4f}; "
+              f"reprojection baseline PSNR {baseline['baseline.psnr']:.2f} dB, SSIM {baseline['baseline.ssim']:.4f}", file=sys.stderr)
     print(json.dumps({'closed_loop': {
         'module': args.module, 'views': args.views, 'held_out': obs.held_out, 'size': args.size, 'channels': pool.data['target_image'].shape[1], 'training_rays': pool.n_rays,
         'steps': args.steps, 'batch': args.batch, 'd_filter': args.d_filter, 'epochs_built': pool.built_epoch + 1,
         'loss_first_10': losses[:10].mean().item(), 'loss_last_10': losses[-10:].mean().item(), 'train_seconds': seconds,
-        'before': before, 'after': after}}))
+        'before': before, 'after': after, **({} if baseline is None else {'baseline': baseline})}}))
 
 
 if __name__ == '__main__':
