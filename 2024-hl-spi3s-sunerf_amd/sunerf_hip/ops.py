@@ -4,6 +4,7 @@ PyTorch is used for device memory and streams only; every numerical op of the re
 kernels of ``csrc/``.
 """
 import ctypes
+import functools
 import os
 import threading
 from typing import Optional, Sequence, Tuple
@@ -59,7 +60,6 @@ def default_precision(d_filter: int) -> int:
     probe above), ``fast`` (fp16 head product + two block-scaled fp8 correction products), ``exact`` (three fp16
     products per term) or ``half`` (opt-in: single fp16 operands -- the bf16-class arithmetic of BASELINE config 3; NOT
     within 1e-4 of the fp32 reference)."""
-    import os
     mode = os.environ.get('SUNERF_FORWARD_PRECISION', 'auto').lower()
     names = {v: k for k, v in PRECISION_NAMES.items()}
     if mode not in names:
@@ -88,22 +88,6 @@ def _stash_wanted(training: bool) -> bool:
 
 _workspaces = {}                        # (device, stream) -> scratch of the d_filter = 512 render kernel
 STASH_FP16, STASH_PHASE = 0, 1          # include/sunerf_hip.h: SUNERF_STASH_*
-
-
-def training_stash_format(packed, n_rays: int, n_samples: int) -> int:
-    """What the training forward leaves for the backward: 16-bit phases (half the bytes; what the layer-pipelined backward reads)
-    whenever that backward is going to run -- d_filter 256 on a 256-CU device, SUNERF_BACKWARD not 'classic', no rank sharing the
-    card --, fp16 sin + cos fragments for the two-kernel backward otherwise.  ``SUNERF_STASH=fp16`` forces the latter (and with
-    it the two-kernel backward)."""
-    if os.environ.get('SUNERF_STASH', '').strip().lower() == 'fp16' or n_rays <= 0:
-        return STASH_FP16
-    if backward_mode() != 'pipe':
-        return STASH_FP16
-    with torch.cuda.device(packed.device):
-        ok = _l.load().sunerf_bwd_pipe_workspace_bytes(n_rays, n_samples, packed.d_filter, packed.n_linear) > 0
-    if not ok or _shared_device(packed.device):
-        return STASH_FP16
-    return STASH_PHASE
 
 
 def stash_format_of(stash, n_rays: int, n_samples: int, packed) -> int:
@@ -152,6 +136,28 @@ def _workspace(cache, dev, nbytes: int) -> torch.Tensor:
     return ws
 
 
+def _ptr_array(tensors: Sequence[torch.Tensor]):
+    """The host array of device pointers the C ABI takes for per-layer tensor lists."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+class _DeferredWord:
+    """A device scalar on its way to the host: copied into a pinned word behind an event on the current stream of ``device``.
+    What is done with it, and when, is the policy of its owner (the two probes below differ in that)."""
+
+    def __init__(self, scalar: torch.Tensor, device):
+        self.host = torch.empty(1, dtype=torch.float32, pin_memory=True)
+        self.host.copy_(scalar, non_blocking=True)
+        self.event = torch.cuda.Event()
+        self.event.record(torch.cuda.current_stream(device))
+
+    def ready(self, wait: bool = False) -> bool:
+        """Has the word arrived (``wait``: blocks until it has)?  Once it has, ``float(self.host[0])`` is the scalar."""
+        if wait:
+            self.event.synchronize()
+        return wait or self.event.query()
+
+
 class PackedMLP:
     """fp16 hi/lo A-fragment image of one NeRF MLP (see csrc/sunerf_common.h).  Re-pack after every
     parameter update (``repack``)."""
@@ -176,7 +182,14 @@ class PackedMLP:
         self.probe_due = self.auto
         self.last_probe = None            # gate units measured by the last probe (AUTO only)
         self._versions_since_probe = 0
-        self._pending_probe = None        # (pinned host word, event, sensitivity) of a probe whose result has not been read yet
+        self._pending_probe = None        # (_DeferredWord, sensitivity, version, collective) of a probe whose result has not been read yet
+        self._version = 0                 # parameter version: counts the (re)packs
+        self._alt_buffer = None           # image of the OTHER arithmetic (AUTO): what the probe compares against, what a mode change swaps in
+        self._alt_version = None          # the parameter version `_alt_buffer` holds, None: re-pack it on use
+        # the W^T probe of the pipelined backward (_pipe_w_probe below): its two sets of scratch gradients, its word in flight, the
+        # parameter version it ran at, the last measured difference, and the decision taken from it (single fp16 W^T)
+        self._pipe_probe_bufs = self._pipe_w_pending = self._pipe_probe_version = self.pipe_w_probe = None
+        self.pipe_hi_only = False
         # evaluation/loader.py:226-229 calls the renderer from a ThreadPoolExecutor: (re)packing, probing and the buffer swap of
         # a mode change are serialised; a render call works on the (buffer, precision) pair it read under the lock
         self._lock = threading.RLock()
@@ -189,21 +202,32 @@ class PackedMLP:
         self.buffer = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self.buffer_t = None        # transposed image for the backward pass, packed on demand
         self._t_valid = False
-        self._pad_w = self._pad_b = None
+        self._keepalive = None      # (weights, biases): the fp32 parameters of the last (re)pack in the kernel shapes, see kernel_params
+        self._pad_w = self._pad_b = None        # zero-padded models: the kernel-shaped copies of the parameters ...
+        self._pad_gw = self._pad_gb = None      # ... and the kernel-shaped gradients the backward kernels write (stage_grads)
         self.repack(weights, biases)
+
+    def _shapes(self, d_in: int, d: int):
+        return [((self.d_out if i == self.n_linear - 1 else d, d_in if i == 0 else d), (self.d_out if i == self.n_linear - 1 else d,))
+                for i in range(self.n_linear)]            # [(weight shape, bias shape)] with the given input and hidden widths
 
     def kernel_shapes(self):
         """[(weight shape, bias shape)] of the (padded) network the kernels see."""
-        D = self.d_filter
-        return [((self.d_out if i == self.n_linear - 1 else D, 84 if i == 0 else D), (self.d_out if i == self.n_linear - 1 else D,))
-                for i in range(self.n_linear)]
+        return self._shapes(84, self.d_filter)
+
+    def model_shapes(self):
+        """[(weight shape, bias shape)] of the model's own nn.Linear layers."""
+        return self._shapes(self.d_in, self.d_model)
+
+    def kernel_shaped(self, make=torch.empty):
+        """(weights, biases): new fp32 device tensors of ``kernel_shapes``."""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        return [make(ws, **f32) for ws, _ in self.kernel_shapes()], [make(bs, **f32) for _, bs in self.kernel_shapes()]
 
     def _padded(self, weights, biases):
         """Copies the model's parameters into zero-initialised tensors of the kernel's shapes (device copies only)."""
         if self._pad_w is None:
-            f32 = dict(dtype=torch.float32, device=self.device)
-            self._pad_w = [torch.zeros(ws, **f32) for ws, _ in self.kernel_shapes()]
-            self._pad_b = [torch.zeros(bs, **f32) for _, bs in self.kernel_shapes()]
+            self._pad_w, self._pad_b = self.kernel_shaped(torch.zeros)
         for W, b, pw, pb in zip(weights, biases, self._pad_w, self._pad_b):
             pw[:W.shape[0], :W.shape[1]].copy_(W.detach())
             pb[:b.shape[0]].copy_(b.detach())
@@ -212,35 +236,65 @@ class PackedMLP:
     def repack(self, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor]):
         assert len(weights) == self.n_linear and len(biases) == self.n_linear
         if self.padded:
-            for i, (w, b) in enumerate(zip(weights, biases)):
-                d_in = self.d_in if i == 0 else self.d_model
-                d_o = self.d_out if i == self.n_linear - 1 else self.d_model
-                _dev(w.detach(), f'weight[{i}]', (d_o, d_in)); _dev(b.detach(), f'bias[{i}]', (d_o,))
+            for i, (w, b, (w_shape, b_shape)) in enumerate(zip(weights, biases, self.model_shapes())):
+                _dev(w.detach(), f'weight[{i}]', w_shape); _dev(b.detach(), f'bias[{i}]', b_shape)
             weights, biases = self._padded(weights, biases)
         ws, bs = [], []
-        for i, (w, b) in enumerate(zip(weights, biases)):
-            d_in = 84 if i == 0 else self.d_filter
-            d_o = self.d_out if i == self.n_linear - 1 else self.d_filter
-            ws.append(_dev(w.detach(), f'weight[{i}]', (d_o, d_in)))
-            bs.append(_dev(b.detach(), f'bias[{i}]', (d_o,)))
-        W = (ctypes.c_void_p * self.n_linear)(*[w.data_ptr() for w in ws])
-        B = (ctypes.c_void_p * self.n_linear)(*[b.data_ptr() for b in bs])
-        _l.call(self.device, 'sunerf_pack_mlp', W, B, self.n_linear, self.d_filter, self.d_out, self.precision,
-                _ptr(self.buffer), _stream(self.device))
-        self._keepalive = (ws, bs)   # until the pack kernel has run on the stream
+        for i, (w, b, (w_shape, b_shape)) in enumerate(zip(weights, biases, self.kernel_shapes())):
+            ws.append(_dev(w.detach(), f'weight[{i}]', w_shape))
+            bs.append(_dev(b.detach(), f'bias[{i}]', b_shape))
+        self._keepalive = (ws, bs)
+        self._pack_into(self.buffer, self.precision)
         self._t_valid = False
-        self._version = getattr(self, '_version', 0) + 1
+        self._version += 1
         if self.auto:
             self._versions_since_probe += 1
             if self._versions_since_probe >= PROBE_EVERY:
                 self.probe_due = True
 
+    def kernel_params(self):
+        """(weights, biases): the fp32 parameters of the last (re)pack in ``kernel_shapes`` -- the model's own tensors, the zero-padded
+        copies for a padded model -- for the packers and the fp32 backward kernels (kept alive here until those have run)."""
+        return self._keepalive
+
     def _pack_into(self, buffer: torch.Tensor, precision: int):
-        ws, bs = self._keepalive
-        W = (ctypes.c_void_p * self.n_linear)(*[w.data_ptr() for w in ws])
-        B = (ctypes.c_void_p * self.n_linear)(*[b.data_ptr() for b in bs])
-        _l.call(self.device, 'sunerf_pack_mlp', W, B, self.n_linear, self.d_filter, self.d_out, precision, _ptr(buffer),
-                _stream(self.device))
+        ws, bs = self.kernel_params()
+        _l.call(self.device, 'sunerf_pack_mlp', _ptr_array(ws), _ptr_array(bs), self.n_linear, self.d_filter, self.d_out, precision,
+                _ptr(buffer), _stream(self.device))
+
+    def stage_grads(self, grad_weights: Sequence[torch.Tensor], grad_biases: Sequence[torch.Tensor], accumulate: bool):
+        """Checks the caller's gradient buffers (per layer one contiguous fp32 tensor of the model's shape) -> ``(kernel weights, kernel
+        biases, kernel accumulate, fold)``: what a backward kernel writes, and the step to run after it.  These are the caller's own
+        buffers and a no-op, unless the model is zero-padded (``__init__``): then the kernel fills staging buffers of the padded shapes
+        and ``fold`` copies (``accumulate``: adds) their leading blocks, the model's gradients, into the caller's (the padding's own
+        gradients are discarded: those weights are not parameters)."""
+        if len(grad_weights) != self.n_linear or len(grad_biases) != self.n_linear:
+            raise ValueError('one weight and one bias gradient buffer per layer')
+        for i, (gw, gb, (w_shape, b_shape)) in enumerate(zip(grad_weights, grad_biases, self.model_shapes())):
+            if gw.shape != w_shape or gb.shape != b_shape or gw.dtype != torch.float32 or gb.dtype != torch.float32 \
+                    or not gw.is_contiguous() or not gb.is_contiguous():
+                raise ValueError(f'grad buffer {i} has the wrong shape / layout')
+        if not self.padded:
+            return grad_weights, grad_biases, accumulate, lambda: None
+        if self._pad_gw is None:
+            self._pad_gw, self._pad_gb = self.kernel_shaped()
+        pad_w, pad_b = self._pad_gw, self._pad_gb
+        into = torch.Tensor.add_ if accumulate else torch.Tensor.copy_
+
+        def fold():
+            for gw, gb, pw, pb in zip(grad_weights, grad_biases, pad_w, pad_b):
+                into(gw, pw[:gw.shape[0], :gw.shape[1]])
+                into(gb, pb[:gb.shape[0]])
+        return pad_w, pad_b, False, fold
+
+    def image_for_call(self, probe=None):
+        """``(image buffer, kernel precision)`` of one forward call, read under the lock: this call's image, whatever other threads
+        decide next.  Before that a finished probe's decision is taken and, when one is due (AUTO), ``probe()`` runs it on the caller's rays."""
+        with self._lock:
+            self._apply_probe()
+            if self.auto and self.probe_due and probe is not None:
+                probe()
+            return self.buffer, self.precision
 
     def probe(self, rays_o, rays_d, times, z_vals, reg_radius: float, sensitivity: float = 1.0) -> float:
         """AUTO: renders PROBE_RAYS rays of the call in both arithmetics, keeps FAST if it is inside the gate with margin,
@@ -261,18 +315,14 @@ class PackedMLP:
             sel = slice(0, (total // n) * n, total // n)
             rays_o, rays_d, z_vals = rays_o[sel].contiguous(), rays_d[sel].contiguous(), z_vals[sel].contiguous()
             times = times.reshape(-1)[sel].contiguous()
-            if getattr(self, '_alt_buffer', None) is None:
+            if self._alt_buffer is None:
                 self._alt_buffer = torch.empty_like(self.buffer)
             other = PRECISION_EXACT if self.precision == PRECISION_FAST else PRECISION_FAST
             self._pack_into(self._alt_buffer, other)
             self._alt_version = self._version
             views = {self.precision: self.buffer, other: self._alt_buffer}
-            outs = {}
-            for mode, buf in views.items():
-                shadow = object.__new__(PackedMLP)
-                shadow.__dict__.update(self.__dict__)
-                shadow.buffer, shadow.precision, shadow.auto, shadow._pending_probe = buf, mode, False, None
-                outs[mode] = emission_render_fwd(shadow, rays_o, rays_d, times, z_vals, reg_radius, want_epilogues=True)
+            outs = {mode: _emission_render(self, image, mode, rays_o, rays_d, times, z_vals, reg_radius, want_epilogues=True)
+                    for mode, image in views.items()}
             for k in ('image', 'height_map', 'absorption_map'):
                 f, e = outs[PRECISION_FAST][k].reshape(-1), outs[PRECISION_EXACT][k].reshape(-1)
                 # absorption_map = sum(1 - a): the reference forms 1 - a in fp32, i.e. with 2^-24 absolute noise per sample.
@@ -286,12 +336,8 @@ class PackedMLP:
             import torch.distributed as dist
             # every rank probes at the same parameter version and takes part whatever its own batch holds: one decision
             dist.all_reduce(units, op=dist.ReduceOp.MAX, group=probe_group)
-        host = torch.empty(1, dtype=torch.float32, pin_memory=True)
-        host.copy_(units, non_blocking=True)
-        event = torch.cuda.Event()
-        event.record(torch.cuda.current_stream(self.device))
         first = self.last_probe is None
-        self._pending_probe = (host, event, float(sensitivity), self._version, world > 1)
+        self._pending_probe = (_DeferredWord(units, self.device), float(sensitivity), self._version, world > 1)
         self._apply_probe(block=first or not PROBE_ASYNC)
         return self.last_probe
 
@@ -300,25 +346,22 @@ class PackedMLP:
         pending = self._pending_probe
         if pending is None:
             return
-        host, event, sensitivity, version, collective = pending
-        if block:
-            event.synchronize()
-        elif collective:
+        word, sensitivity, version, collective = pending
+        if collective and not block:
             # ranks must switch at the same parameter version: a fixed distance behind the probe, not "when the event is seen"
             if self._version < version + PROBE_APPLY_AFTER:
                 return
-            event.synchronize()
-        elif not event.query():
+        if not word.ready(wait=block or collective):
             return
         self._pending_probe = None
-        units = float(host[0]) * sensitivity
+        units = float(word.host[0]) * sensitivity
         self.last_probe = units
         want = PRECISION_FAST if units <= PROBE_LIMIT else PRECISION_EXACT
         if want != self.precision:
             # A render call of another thread may still hold (self.buffer, old precision) as the pair it read under the lock:
             # the live buffer is never re-packed in another arithmetic.  The image of the wanted mode goes into the alternate
             # buffer (the probe left it there if the parameters have not changed since) and the two are swapped.
-            if getattr(self, '_alt_version', None) != self._version:
+            if self._alt_version != self._version:
                 self._alt_buffer = torch.empty_like(self.buffer)      # a fresh one: the old alternate may be some call's snapshot too
                 self._pack_into(self._alt_buffer, want)
             self.buffer, self._alt_buffer = self._alt_buffer, self.buffer
@@ -333,14 +376,11 @@ class PackedMLP:
 
     def transposed(self) -> torch.Tensor:
         """fp16 W^T image consumed by sunerf_mlp_dgrad (packed lazily, once per parameter version)."""
-        lib = _l.load()
         if self.buffer_t is None:
-            self.buffer_t = torch.empty(lib.sunerf_packed_mlp_t_bytes(self.d_filter, self.n_linear), dtype=torch.uint8,
+            self.buffer_t = torch.empty(_l.load().sunerf_packed_mlp_t_bytes(self.d_filter, self.n_linear), dtype=torch.uint8,
                                         device=self.device)
         if not self._t_valid:
-            ws = self._keepalive[0]
-            W = (ctypes.c_void_p * self.n_linear)(*[w.data_ptr() for w in ws])
-            _l.call(self.device, 'sunerf_pack_mlp_t', W, self.n_linear, self.d_filter, self.d_out,
+            _l.call(self.device, 'sunerf_pack_mlp_t', _ptr_array(self.kernel_params()[0]), self.n_linear, self.d_filter, self.d_out,
                     _ptr(self.buffer_t), _stream(self.device))
             self._t_valid = True
         return self.buffer_t
@@ -348,7 +388,6 @@ class PackedMLP:
 
 def sample_z(kind: int, rays_o, rays_d, t_vals, distance: float, solar_R: float,
              t_rand: Optional[torch.Tensor] = None) -> torch.Tensor:
-    lib = _l.load()
     n = rays_o.shape[0]
     rays_o = _dev(rays_o, 'rays_o', (n, 3))
     rays_d = _dev(rays_d, 'rays_d', (n, 3))
@@ -362,6 +401,21 @@ def sample_z(kind: int, rays_o, rays_d, t_vals, distance: float, solar_R: float,
     return z
 
 
+def _forward_scratch(packed: PackedMLP, dev, n_rays: int, n_samples: int, training: bool):
+    """What a forward launch of ``n_rays`` x ``n_samples`` needs beside its outputs -> ``(workspace or None, its bytes, stash or None,
+    stash format)``: the scratch of the d_filter = 512 render kernel, and for a training forward the activation stash in the format
+    of the backward that is going to read it (none under ``SUNERF_BACKWARD_PRECISION=exact``)."""
+    lib = _l.load()
+    ws_bytes = lib.sunerf_render_workspace_bytes(packed.d_filter)
+    ws = _workspace(_workspaces, dev, ws_bytes) if ws_bytes else None
+    stash, fmt = None, STASH_FP16
+    if _stash_wanted(training):
+        fmt = training_stash_format(packed, n_rays, n_samples)
+        stash = torch.empty(lib.sunerf_act_stash_bytes(n_rays, n_samples, packed.d_filter, packed.n_linear, fmt), dtype=torch.uint8,
+                            device=dev)
+    return ws, ws_bytes, stash, fmt
+
+
 def emission_render_fwd(packed: PackedMLP, rays_o, rays_d, times, z_vals, reg_radius: float,
                         want_raw: bool = False, want_epilogues: bool = False, training: bool = False,
                         probe_sensitivity: float = 1.0):
@@ -369,20 +423,23 @@ def emission_render_fwd(packed: PackedMLP, rays_o, rays_d, times, z_vals, reg_ra
     [, height_map (N,), absorption_map (N,), regularization (N,S)][, stash]).  ``training=True`` also writes the
     activation stash needed by :func:`emission_render_bwd` (and implies ``want_raw``); under
     ``SUNERF_BACKWARD_PRECISION=exact`` the backward does not read one and ``stash`` is None."""
-    lib = _l.load()
     n, s = z_vals.shape
-    dev = z_vals.device
     rays_o = _dev(rays_o, 'rays_o', (n, 3))
     rays_d = _dev(rays_d, 'rays_d', (n, 3))
     times = _dev(times.reshape(-1), 'times', (n,))
     z_vals = _dev(z_vals, 'z_vals', (n, s))
-    if packed.device != dev:
+    if packed.device != z_vals.device:
         raise _l.SunerfHipError('packed weights and rays are on different devices')
-    with packed._lock:
-        packed._apply_probe()
-        if packed.auto and packed.probe_due:
-            packed.probe(rays_o, rays_d, times, z_vals, reg_radius, probe_sensitivity)
-        weights_image, precision = packed.buffer, packed.precision        # this call's image, whatever other threads decide next
+    image, precision = packed.image_for_call(lambda: packed.probe(rays_o, rays_d, times, z_vals, reg_radius, probe_sensitivity))
+    return _emission_render(packed, image, precision, rays_o, rays_d, times, z_vals, reg_radius, want_raw, want_epilogues, training)
+
+
+def _emission_render(packed: PackedMLP, image, precision: int, rays_o, rays_d, times, z_vals, reg_radius: float,
+                     want_raw: bool = False, want_epilogues: bool = False, training: bool = False):
+    """:func:`emission_render_fwd` on validated inputs with a GIVEN packed image and its arithmetic (the call's own, or one of the
+    two the probe compares)."""
+    n, s = z_vals.shape
+    dev = z_vals.device
     f32 = dict(dtype=torch.float32, device=dev)
     out = {'image': torch.empty(n, 1, **f32), 'weights': torch.empty(n, s, **f32),
            'absorption': torch.empty(n, s, **f32)}
@@ -390,18 +447,12 @@ def emission_render_fwd(packed: PackedMLP, rays_o, rays_d, times, z_vals, reg_ra
     if training and packed.d_filter not in TRAINABLE_D_FILTER:
         raise NotImplementedError(f'training with d_filter={packed.d_filter} is not implemented (inference only); '
                                   f'trainable widths: {TRAINABLE_D_FILTER}')
-    ws_bytes = lib.sunerf_render_workspace_bytes(packed.d_filter)
-    ws = _workspace(_workspaces, dev, ws_bytes) if ws_bytes else None
+    ws, ws_bytes, stash, fmt = _forward_scratch(packed, dev, n, s, training)
     raw = torch.empty(n, s, 2, **f32) if want_raw else None
-    stash, fmt = None, STASH_FP16
-    if _stash_wanted(training):
-        fmt = training_stash_format(packed, n, s)
-        stash = torch.empty(lib.sunerf_act_stash_bytes(n, s, packed.d_filter, packed.n_linear, fmt), dtype=torch.uint8,
-                            device=dev)
     hm = am = reg = None
     if want_epilogues:
         hm, am, reg = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, s, **f32)
-    _l.call(dev, 'sunerf_emission_render_fwd', _ptr(weights_image), packed.d_filter, packed.n_linear,
+    _l.call(dev, 'sunerf_emission_render_fwd', _ptr(image), packed.d_filter, packed.n_linear,
             precision, _ptr(rays_o), _ptr(rays_d), _ptr(times), _ptr(z_vals), n, s, _ptr(out['image']),
             _ptr(out['weights']), _ptr(out['absorption']), _ptr(raw), _ptr(hm), _ptr(am), _ptr(reg),
             float(reg_radius), _ptr(stash), fmt, _ptr(ws), ws_bytes, _stream(dev))
@@ -418,35 +469,29 @@ def mlp_points_fwd(packed: PackedMLP, points: torch.Tensor, training: bool = Fal
     """NeRF.forward on free-standing points (M, 4) -> dict(raw (M, 2)[, stash, n_padded]).  The points are padded to whole
     32-point chunks; ``training=True`` also writes the activation stash :func:`mlp_backward` needs (with ``g_raw`` of shape
     (n_padded / 32, 32, 2)); ``stash`` is None under ``SUNERF_BACKWARD_PRECISION=exact``."""
-    lib = _l.load()
     m = points.shape[0]
     dev = points.device
     points = _dev(points, 'points', (m, 4))
     if packed.device != dev:
         raise _l.SunerfHipError('packed weights and points are on different devices')
-    with packed._lock:
-        packed._apply_probe()
-        if packed.auto and packed.probe_due and (m > 0 or _probe_world() > 1):
-            # the measured choice of the arithmetic (AUTO) needs rays: PROBE_RAYS of the points as two-sample rays o = 0, d = xyz, z = 1
-            # (a rank without points still takes part in the probe's all-reduce, with zero units)
+
+    def probe():
+        # the measured choice of the arithmetic (AUTO) needs rays: PROBE_RAYS of the points as two-sample rays o = 0, d = xyz, z = 1
+        # (a rank without points still takes part in the probe's all-reduce, with zero units)
+        if m > 0 or _probe_world() > 1:
             k = min(PROBE_RAYS, m)
             idx = torch.linspace(0, max(m - 1, 0), k, device=dev).long()
             sel = points[idx]
             packed.probe(torch.zeros(k, 3, device=dev), sel[:, :3].contiguous(), sel[:, 3].contiguous(), torch.ones(k, 2, device=dev), 0.0)
-        weights_image, precision = packed.buffer, packed.precision
+    image, precision = packed.image_for_call(probe)
     m_pad = (m + 31) // 32 * 32
     if m_pad != m:
         points = torch.cat([points, points.new_zeros(m_pad - m, 4)])
     if training and packed.d_filter not in TRAINABLE_D_FILTER:
         raise NotImplementedError(f'training with d_filter={packed.d_filter} is not implemented (inference only)')
-    ws_bytes = lib.sunerf_render_workspace_bytes(packed.d_filter)
-    ws = _workspace(_workspaces, dev, ws_bytes) if ws_bytes else None
+    ws, ws_bytes, stash, fmt = _forward_scratch(packed, dev, m_pad // 32, 32, training)
     raw = torch.empty(m_pad, 2, dtype=torch.float32, device=dev)
-    stash, fmt = None, STASH_FP16
-    if _stash_wanted(training):
-        fmt = training_stash_format(packed, m_pad // 32, 32)
-        stash = torch.empty(lib.sunerf_act_stash_bytes(m_pad // 32, 32, packed.d_filter, packed.n_linear, fmt), dtype=torch.uint8, device=dev)
-    _l.call(dev, 'sunerf_mlp_points_fwd', _ptr(weights_image), packed.d_filter, packed.n_linear, precision, _ptr(points),
+    _l.call(dev, 'sunerf_mlp_points_fwd', _ptr(image), packed.d_filter, packed.n_linear, precision, _ptr(points),
             m_pad, _ptr(raw), _ptr(stash), fmt, _ptr(ws), ws_bytes, _stream(dev))
     out = {'raw': raw[:m], 'n_padded': m_pad}
     if training:
@@ -456,7 +501,6 @@ def mlp_points_fwd(packed: PackedMLP, points: torch.Tensor, training: bool = Fal
 
 def hier_resample(z_vals, weights, u: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """``u``: (S_f,) shared sample positions (perturb=False) or (N, S_f) per-ray (perturb=True)."""
-    lib = _l.load()
     n, sc = z_vals.shape
     z_vals = _dev(z_vals, 'z_vals', (n, sc))
     weights = _dev(weights.detach(), 'weights', (n, sc))
@@ -493,14 +537,6 @@ def sample_pdf(bins, weights, u: torch.Tensor) -> torch.Tensor:
     return samples
 
 
-def wgrad_split(n_linear: int, n_cus: int = 256, d_filter: int = 256) -> int:
-    """Partial sums per layer in sunerf_mlp_wgrad: n_linear * split (* 4 workgroup blocks at d_filter = 512) workgroups
-    must fit the chip in ONE wave (one workgroup per CU, all about equally long): 9 layers -> 28 (252 workgroups);
-    288 would take two rounds."""
-    blocks = 4 if d_filter > 256 else 1
-    return max(1, n_cus // (n_linear * blocks))
-
-
 def emission_render_bwd(packed: PackedMLP, rays_o, rays_d, z_vals, raw, stash, g_image, g_reg, g_reg_const: float,
                         reg_radius: float, grad_weights: Sequence[torch.Tensor], grad_biases: Sequence[torch.Tensor],
                         accumulate: bool = False, times=None):
@@ -509,24 +545,10 @@ def emission_render_bwd(packed: PackedMLP, rays_o, rays_d, z_vals, raw, stash, g
     (``g_reg`` (N,S) tensor or None + the constant ``g_reg_const``).  ``times`` (N,): the forward's time coordinate -- with it
     the small-batch fp32 backward can recompute the activations (``mlp_backward(query=...)``); without it the fp16 kernels run.
     Under ``SUNERF_BACKWARD_PRECISION=exact`` ``times`` is required."""
-    lib = _l.load()
     if times is None and backward_precision() == 'exact':
         raise _l.SunerfHipError(_NO_QUERY)
-    n, s = z_vals.shape
-    dev = z_vals.device
-    rays_o = _dev(rays_o, 'rays_o', (n, 3))
-    rays_d = _dev(rays_d, 'rays_d', (n, 3))
-    z_vals = _dev(z_vals, 'z_vals', (n, s))
-    raw = _dev(raw, 'raw', (n, s, 2))
-    g_image = _dev(g_image.reshape(-1), 'g_image', (n,))
-    if g_reg is not None:
-        g_reg = _dev(g_reg, 'g_reg', (n, s))
-    D, nl = packed.d_filter, packed.n_linear
-    g_raw = torch.empty(n, s, 2, dtype=torch.float32, device=dev)
-    absmax = torch.empty(1, dtype=torch.int32, device=dev)
-    stream = _stream(dev)
-    _l.call(dev, 'sunerf_emission_integral_bwd', _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(g_image),
-            _ptr(g_reg), None, None, float(g_reg_const), float(reg_radius), n, s, _ptr(g_raw), _ptr(absmax), stream)
+    g_raw, absmax = emission_integral_bwd(raw, z_vals, rays_d, g_image, rays_o=rays_o, g_reg=g_reg, g_reg_const=g_reg_const,
+                                          reg_radius=reg_radius, return_absmax=True)
     mlp_backward(packed, g_raw, absmax, stash, grad_weights, grad_biases, accumulate,
                  query=None if times is None else ('rays', rays_o, rays_d, times, z_vals))
     return g_raw
@@ -573,15 +595,26 @@ def emission_integral_bwd(raw, z_vals, rays_d, g_image=None, g_weights=None, g_a
     return (g_raw, absmax) if return_absmax else g_raw
 
 
-# ---- which backward runs -------------------------------------------------------------------------
+# ---- which backward runs (DESIGN.md sections 5.4 and 5.5): the whole policy ------------------------------------------------------
 # 'pipe' (default): the layer-pipelined kernel of csrc/bwd_pipe.hip where it applies (d_filter 256, n_linear >= 3, a 256-CU
-# device), the two-kernel dgrad + wgrad elsewhere; 'classic': always the two kernels.  The pipelined launch needs all of its
-# 256 workgroups resident at once: ranks that SHARE one GPU (the CPU-rehearsal tests) must use 'classic'.
+# device), the two-kernel dgrad + wgrad elsewhere; 'classic' (SUNERF_BACKWARD, or SUNERF_STASH=fp16): always the two kernels.  The
+# pipelined launch needs all of its 256 workgroups resident at once: ranks that SHARE one GPU (the CPU-rehearsal tests) must use
+# 'classic' (_shared_device), and a launch that gives up switches the process to it (pipe_status).
+# Small batches take the reference's arithmetic (csrc/bwd_exact.hip).  The fp16 backward kernels carry ~2^-12 of relative rounding
+# error per term of a gradient sum (dZ, cos, H are single fp16 operands).  A training batch averages that away (every tensor within
+# 1e-3 of the fp32 oracle from ~1e4 samples on); a batch of a few hundred samples whose bias sums cancel to a few per cent of their
+# terms does not (tests/tools/bias_conditioning.py).  Up to EXACT_BACKWARD_SAMPLES samples per call -- where the fp16 kernels are
+# launch-latency-bound anyway -- the backward therefore recomputes the activations and runs the chain in fp32.
+# SUNERF_EXACT_BACKWARD_SAMPLES overrides the limit (0: never); a backward kernel asked for BY NAME (SUNERF_BACKWARD, tests forcing a
+# mode, and the two automatic switches above: they set the same _backward_forced) is always honoured.
+# SUNERF_BACKWARD_PRECISION=exact sends EVERY batch that has a query to the any-size fp32 kernel, a forced SUNERF_BACKWARD included.
+# The forward decides first (training_stash_format): it leaves the stash for the backward it expects -- phases are read by the
+# pipelined kernel only, fp16 sin + cos fragments by the two kernels only, the fp32 kernels read none (_stash_wanted).  The backward
+# (_backward_path) goes by the stash it is handed, and refuses a phase stash where the pipelined kernel can no longer run.
 _backward_forced = None
-pipe_timing = False                       # True: every pipelined launch is bracketed by library-owned HIP events (flags bit 7)
-_pipe_ws = {}                             # (device, stream) -> workspace
-_pipe_checked = {}                        # workspaces whose sticky status word has not been looked at yet
-PIPE_WS_STICKY, PIPE_WS_DEBUG = 0, 256    # include/sunerf_hip.h: fixed offsets of the sticky status block / the debug counters
+EXACT_BACKWARD_SAMPLES = 4096
+_NO_QUERY = ('SUNERF_BACKWARD_PRECISION=exact: the fp32 backward recomputes the activations from the query points, and this '
+             'backward was given none (pass times= / query=); the fp16 kernels are not run in its place')
 
 
 def backward_mode() -> str:
@@ -591,6 +624,11 @@ def backward_mode() -> str:
     if mode not in ('pipe', 'classic'):
         raise ValueError(f"SUNERF_BACKWARD must be 'pipe' or 'classic', not {mode!r}")
     return mode
+
+
+def exact_backward_limit() -> int:
+    v = os.environ.get('SUNERF_EXACT_BACKWARD_SAMPLES', '').strip()
+    return EXACT_BACKWARD_SAMPLES if v == '' else max(0, int(v))
 
 
 def _shared_device(dev) -> bool:
@@ -608,6 +646,109 @@ def _shared_device(dev) -> bool:
     return False
 
 
+def training_stash_format(packed, n_rays: int, n_samples: int) -> int:
+    """What the training forward leaves for the backward: 16-bit phases (half the bytes; what the layer-pipelined backward reads)
+    whenever that backward is going to run -- d_filter 256 on a 256-CU device, SUNERF_BACKWARD not 'classic', no rank sharing the
+    card --, fp16 sin + cos fragments for the two-kernel backward otherwise.  ``SUNERF_STASH=fp16`` forces the latter (and with
+    it the two-kernel backward)."""
+    if os.environ.get('SUNERF_STASH', '').strip().lower() == 'fp16' or n_rays <= 0:
+        return STASH_FP16
+    if backward_mode() != 'pipe':
+        return STASH_FP16
+    with torch.cuda.device(packed.device):
+        ok = _l.load().sunerf_bwd_pipe_workspace_bytes(n_rays, n_samples, packed.d_filter, packed.n_linear) > 0
+    if not ok or _shared_device(packed.device):
+        return STASH_FP16
+    return STASH_PHASE
+
+
+def _backward_path(n_rays: int, n_samples: int, has_query: bool, stash_format, pipe_available) -> str:
+    """The backward of one :func:`mlp_backward` call on ``n_rays`` x ``n_samples`` samples: 'fp32_chunked', 'fp32', 'pipe' or 'classic';
+    'empty' when there is nothing to launch.  Touches no device and reads nothing but ``_backward_forced`` and the SUNERF_*
+    environment.  ``stash_format`` and ``pipe_available`` are zero-argument callables -- the format of the stash handed to the
+    backward, and whether the workspace query of the pipelined backward is positive for this shape and device -- asked only when
+    the rows before them have not decided (an fp32 backward may have been given no stash at all)."""
+    total = n_rays * n_samples
+    if backward_precision() == 'exact':
+        if not has_query:
+            raise _l.SunerfHipError(_NO_QUERY)
+        return 'fp32_chunked' if total else 'empty'
+    by_name = _backward_forced is not None or bool(os.environ.get('SUNERF_BACKWARD', '').strip())
+    if has_query and total > 0 and not by_name and total <= exact_backward_limit():
+        return 'fp32'
+    if n_rays > 0 and stash_format() == STASH_PHASE:
+        if backward_mode() != 'pipe':
+            raise _l.SunerfHipError('this activation stash holds 16-bit phases (written for the layer-pipelined backward) but the '
+                                    'two-kernel backward was selected after the forward ran: choose SUNERF_BACKWARD before the forward, '
+                                    'or SUNERF_STASH=fp16')
+        if not pipe_available():
+            raise _l.SunerfHipError('phase stash but no pipelined backward for this shape / device')
+        return 'pipe'
+    return 'classic'
+
+
+def mlp_backward(packed: PackedMLP, g_raw, absmax, stash, grad_weights: Sequence[torch.Tensor],
+                 grad_biases: Sequence[torch.Tensor], accumulate: bool = False, query=None):
+    """dgrad + wgrad of the sine MLP from the gradient w.r.t. its raw output (N,S,2): fills / accumulates the nn.Linear
+    gradients.  ``absmax``: 4-byte device scalar with the bit pattern of max |g_raw| (written by the integral backward).
+    ``query``: what the forward was evaluated on -- ``('rays', rays_o, rays_d, times, z_vals)`` or ``('points', points (N*S, 4))``;
+    given it, batches of at most ``exact_backward_limit()`` samples take the fp32 backward (csrc/bwd_exact.hip), and under
+    ``SUNERF_BACKWARD_PRECISION=exact`` every batch does (the any-size kernel; no stash is read, ``stash`` may be None)."""
+    n, s = g_raw.shape[0], g_raw.shape[1]
+    dev = g_raw.device
+    kernel_w, kernel_b, kernel_accumulate, fold = packed.stage_grads(grad_weights, grad_biases, accumulate)
+
+    @functools.cache
+    def pipe_bytes():       # one workspace query per call: the decision asks whether it is positive, the pipelined launcher for the size
+        with torch.cuda.device(dev):
+            return _l.load().sunerf_bwd_pipe_workspace_bytes(n, s, packed.d_filter, packed.n_linear)
+    path = _backward_path(n, s, query is not None, lambda: stash_format_of(stash, n, s, packed), lambda: pipe_bytes() > 0)
+    if path == 'empty':
+        if not kernel_accumulate:
+            for t in (*kernel_w, *kernel_b):
+                t.zero_()
+    elif path in ('fp32', 'fp32_chunked'):
+        _mlp_backward_exact(packed, g_raw, query, kernel_w, kernel_b, kernel_accumulate, chunked=path == 'fp32_chunked')
+    elif path == 'pipe':
+        _mlp_backward_pipe(packed, g_raw, absmax, stash, pipe_bytes(), kernel_w, kernel_b, kernel_accumulate)
+    else:
+        _mlp_backward_classic(packed, g_raw, absmax, stash, kernel_w, kernel_b, kernel_accumulate)
+    fold()
+
+
+# ---- the two-kernel backward (csrc/render_bwd.hip, csrc/wgrad.hip) ---------------------------------------------------------------
+def wgrad_split(n_linear: int, n_cus: int = 256, d_filter: int = 256) -> int:
+    """Partial sums per layer in sunerf_mlp_wgrad: n_linear * split (* 4 workgroup blocks at d_filter = 512) workgroups
+    must fit the chip in ONE wave (one workgroup per CU, all about equally long): 9 layers -> 28 (252 workgroups);
+    288 would take two rounds."""
+    blocks = 4 if d_filter > 256 else 1
+    return max(1, n_cus // (n_linear * blocks))
+
+
+def _mlp_backward_classic(packed: PackedMLP, g_raw, absmax, stash, grad_weights, grad_biases, accumulate: bool):
+    lib = _l.load()
+    n, s = g_raw.shape[0], g_raw.shape[1]
+    dev = g_raw.device
+    D, nl = packed.d_filter, packed.n_linear
+    stream = _stream(dev)
+    dz = torch.empty(lib.sunerf_dz_stash_bytes(n, s, D, nl), dtype=torch.uint8, device=dev)
+    _l.call(dev, 'sunerf_mlp_dgrad', _ptr(packed.transposed()), D, nl, _ptr(g_raw), _ptr(absmax), _ptr(stash),
+            _ptr(dz), n, s, stream)
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    cap = int(os.environ.get('SUNERF_GRID_CAP_WGRAD', 0))        # experiment knob, see csrc/sunerf_common.h
+    split = wgrad_split(nl, cap if 0 < cap < cus else cus, D)
+    ws = torch.empty(lib.sunerf_wgrad_workspace_bytes(D, nl, split), dtype=torch.uint8, device=dev)
+    _l.call(dev, 'sunerf_mlp_wgrad', D, nl, packed.d_out, _ptr(packed.transposed()), _ptr(stash), _ptr(dz), _ptr(g_raw), _ptr(absmax), n, s,
+            _ptr(ws), split, _ptr_array(grad_weights), _ptr_array(grad_biases), int(accumulate), stream)
+
+
+# ---- the pipelined backward (csrc/bwd_pipe.hip) --------------------------------------------------------------------------------
+pipe_timing = False                       # True: every pipelined launch is bracketed by library-owned HIP events (flags bit 7)
+_pipe_ws = {}                             # (device, stream) -> workspace
+_pipe_checked = {}                        # workspaces whose sticky status word has not been looked at yet
+PIPE_WS_STICKY, PIPE_WS_DEBUG = 0, 256    # include/sunerf_hip.h: fixed offsets of the sticky status block / the debug counters
+
+
 def _env_on(name: str) -> bool:
     return os.environ.get(name, '0').lower() not in ('', '0', 'false', 'no', 'off')
 
@@ -623,63 +764,6 @@ def pipe_w_mode() -> str:
 
 def _pipe_flags() -> int:
     return (1 if pipe_w_mode() == 'hi' else 0) | (2 if _env_on('SUNERF_PIPE_DEBUG') else 0) | (0x80 if pipe_timing else 0)
-
-
-# ---- single or split W^T in the pipelined backward: chosen by measurement, like the forward arithmetic -----------------------
-# The data-gradient waves multiply dZ by W^T as fp16 head + fp16 remainder (32 matrix instructions per chunk) or by the head
-# alone (16: the kernel -5.7 %, the training step -3.3 %, tools/experiments/r4_pipe_ab.sh).  The head alone is a SYSTEMATIC
-# perturbation of the weights (2^-12 per element, the same for every sample), so its effect on the weight gradients does not
-# average over the batch -- and for the same reason it can be measured on a few rays: the relative difference between the two
-# arithmetics on the first 64 rays of a batch predicts the difference on 8192 rays within 2 %
-# (tools/experiments/r4_hi_only_accuracy.py, profiles/r4_ab/r4_hi_only_accuracy.log: probe 5.2e-4 at default initialisation, 5.0e-4 with
-# hidden weights x 2, 7.5e-4 at x 3, 8.5e-4 at x 4; against fp32 gradients: head + remainder 2.3 ... 2.8e-4 / 4.0e-4 / 6.6e-4, head
-# alone 5.3 ... 6.0e-4 / 9.2e-4 / 8.4e-4).  Every PROBE_EVERY-th parameter version (and at the first pipelined backward of a model)
-# both arithmetics run on those rays; the head alone is used while the worst weight tensor differs by at most PIPE_W_LIMIT, which
-# keeps the gradients within ~0.6 of SURVEY 8d's 1e-3.  No collective: under data parallelism every rank decides for itself (the
-# all-reduced gradient, and with it every replica, is the same on all ranks whichever arithmetic produced a rank's share).
-PIPE_W_PROBE_RAYS = 64
-PIPE_W_LIMIT = 6e-4
-
-
-def _pipe_w_probe(packed, call_prefix):
-    """Runs the pipelined backward on the first PIPE_W_PROBE_RAYS rays in both arithmetics into scratch gradients and leaves the
-    worst relative difference of a weight tensor in a pinned host word behind an event (read at once for the first probe)."""
-    dev = packed.device
-    if getattr(packed, '_pipe_probe_bufs', None) is None:
-        f32 = dict(dtype=torch.float32, device=dev)
-        packed._pipe_probe_bufs = [([torch.empty(ws, **f32) for ws, _ in packed.kernel_shapes()],
-                                    [torch.empty(bs, **f32) for _, bs in packed.kernel_shapes()]) for _ in range(2)]
-    nl = packed.n_linear
-    for hi_only, (gW, gb) in zip((0, 1), packed._pipe_probe_bufs):
-        GW = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gW])
-        GB = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gb])
-        call_prefix(GW, GB, hi_only)
-    (a, _), (b, _) = packed._pipe_probe_bufs
-    diff = torch._foreach_norm(torch._foreach_sub(b, a))
-    base = torch._foreach_norm(a)
-    units = torch.nan_to_num((torch.stack(diff) / torch.stack(base)).max().reshape(1), nan=float('inf'))
-    host = torch.empty(1, dtype=torch.float32, pin_memory=True)
-    host.copy_(units, non_blocking=True)
-    event = torch.cuda.Event()
-    event.record(torch.cuda.current_stream(dev))
-    first = getattr(packed, 'pipe_w_probe', None) is None
-    packed._pipe_w_pending = (host, event)
-    packed._pipe_probe_version = packed._version
-    _pipe_w_apply(packed, block=first or not PROBE_ASYNC)
-
-
-def _pipe_w_apply(packed, block: bool = False):
-    pending = getattr(packed, '_pipe_w_pending', None)
-    if pending is None:
-        return
-    host, event = pending
-    if block:
-        event.synchronize()
-    elif not event.query():
-        return
-    packed._pipe_w_pending = None
-    packed.pipe_w_probe = float(host[0])
-    packed.pipe_hi_only = packed.pipe_w_probe <= PIPE_W_LIMIT
 
 
 def pipe_kernel_time():
@@ -744,32 +828,72 @@ def pipe_status(raise_on_failure: Optional[bool] = None) -> int:
     return worst
 
 
-# ---- small batches: the reference's arithmetic (csrc/bwd_exact.hip) ---------------------------------------------------------
-# The fp16 backward kernels carry ~2^-12 of relative rounding error per term of a gradient sum (dZ, cos, H are single fp16
-# operands).  A training batch averages that away (every tensor within 1e-3 of the fp32 oracle from ~1e4 samples on); a batch of a
-# few hundred samples whose bias sums cancel to a few per cent of their terms does not (tests/tools/bias_conditioning.py).  Up to
-# EXACT_BACKWARD_SAMPLES samples per call -- where the fp16 kernels are launch-latency-bound anyway -- the backward therefore
-# recomputes the activations and runs the chain in fp32.  SUNERF_EXACT_BACKWARD_SAMPLES overrides the limit (0: never); a
-# backward kernel asked for BY NAME (SUNERF_BACKWARD, tests forcing a mode) is always honoured.
-EXACT_BACKWARD_SAMPLES = 4096
+# ---- single or split W^T in the pipelined backward: chosen by measurement, like the forward arithmetic -----------------------
+# The data-gradient waves multiply dZ by W^T as fp16 head + fp16 remainder (32 matrix instructions per chunk) or by the head
+# alone (16: the kernel -5.7 %, the training step -3.3 %, tools/experiments/r4_pipe_ab.sh).  The head alone is a SYSTEMATIC
+# perturbation of the weights (2^-12 per element, the same for every sample), so its effect on the weight gradients does not
+# average over the batch -- and for the same reason it can be measured on a few rays: the relative difference between the two
+# arithmetics on the first 64 rays of a batch predicts the difference on 8192 rays within 2 %
+# (tools/experiments/r4_hi_only_accuracy.py, profiles/r4_ab/r4_hi_only_accuracy.log: probe 5.2e-4 at default initialisation, 5.0e-4 with
+# hidden weights x 2, 7.5e-4 at x 3, 8.5e-4 at x 4; against fp32 gradients: head + remainder 2.3 ... 2.8e-4 / 4.0e-4 / 6.6e-4, head
+# alone 5.3 ... 6.0e-4 / 9.2e-4 / 8.4e-4).  Every PROBE_EVERY-th parameter version (and at the first pipelined backward of a model)
+# both arithmetics run on those rays; the head alone is used while the worst weight tensor differs by at most PIPE_W_LIMIT, which
+# keeps the gradients within ~0.6 of SURVEY 8d's 1e-3.  No collective: under data parallelism every rank decides for itself (the
+# all-reduced gradient, and with it every replica, is the same on all ranks whichever arithmetic produced a rank's share).
+PIPE_W_PROBE_RAYS = 64
+PIPE_W_LIMIT = 6e-4
 
 
-def exact_backward_limit() -> int:
-    v = os.environ.get('SUNERF_EXACT_BACKWARD_SAMPLES', '').strip()
-    return EXACT_BACKWARD_SAMPLES if v == '' else max(0, int(v))
+def _pipe_w_probe(packed, call_prefix):
+    """Runs the pipelined backward on the first PIPE_W_PROBE_RAYS rays in both arithmetics into scratch gradients and leaves the
+    worst relative difference of a weight tensor in a pinned host word behind an event (read at once for the first probe)."""
+    dev = packed.device
+    if packed._pipe_probe_bufs is None:
+        packed._pipe_probe_bufs = [packed.kernel_shaped(), packed.kernel_shaped()]
+    for hi_only, (gW, gb) in zip((0, 1), packed._pipe_probe_bufs):
+        call_prefix(gW, gb, hi_only)
+    (a, _), (b, _) = packed._pipe_probe_bufs
+    diff = torch._foreach_norm(torch._foreach_sub(b, a))
+    base = torch._foreach_norm(a)
+    units = torch.nan_to_num((torch.stack(diff) / torch.stack(base)).max().reshape(1), nan=float('inf'))
+    first = packed.pipe_w_probe is None
+    packed._pipe_w_pending = _DeferredWord(units, dev)
+    packed._pipe_probe_version = packed._version
+    _pipe_w_apply(packed, block=first or not PROBE_ASYNC)
 
 
-def _use_exact_backward(n_samples: int, query) -> bool:
-    if query is None or n_samples <= 0:
-        return False
-    if _backward_forced is not None or os.environ.get('SUNERF_BACKWARD', '').strip():
-        return False
-    return n_samples <= exact_backward_limit()
+def _pipe_w_apply(packed, block: bool = False):
+    word = packed._pipe_w_pending
+    if word is None or not word.ready(wait=block):
+        return
+    packed._pipe_w_pending = None
+    packed.pipe_w_probe = float(word.host[0])
+    packed.pipe_hi_only = packed.pipe_w_probe <= PIPE_W_LIMIT
 
 
+def _mlp_backward_pipe(packed: PackedMLP, g_raw, absmax, stash, pipe_bytes: int, grad_weights, grad_biases, accumulate: bool):
+    n, s = g_raw.shape[0], g_raw.shape[1]
+    dev = g_raw.device
+    ws = _pipe_workspace(dev, pipe_bytes)
+    flags = _pipe_flags()
+
+    def launch(n_rays, gw, gb, acc, fl):
+        _l.call(dev, 'sunerf_mlp_backward_pipe', packed.d_filter, packed.n_linear, packed.d_out, _ptr(packed.transposed()), _ptr(stash),
+                _ptr(g_raw), _ptr(absmax), n_rays, s, _ptr(ws), pipe_bytes, _ptr_array(gw), _ptr_array(gb), int(acc), fl, _stream(dev))
+    if pipe_w_mode() == 'auto':
+        with packed._lock:
+            due = packed._pipe_probe_version is None or packed._version - packed._pipe_probe_version >= PROBE_EVERY
+            if due and n >= PIPE_W_PROBE_RAYS and packed._pipe_w_pending is None:
+                # on the first rays: a prefix of g_raw and of the (ray-major) stash
+                _pipe_w_probe(packed, lambda gw, gb, hi_only: launch(PIPE_W_PROBE_RAYS, gw, gb, 0, (flags & ~0x81) | hi_only))
+            _pipe_w_apply(packed)
+            if packed.pipe_hi_only:
+                flags |= 1
+    launch(n, grad_weights, grad_biases, accumulate, flags)
+
+
+# ---- the fp32 backward (csrc/bwd_exact.hip) ------------------------------------------------------------------------------------
 _exact_ws = {}          # (device, stream) -> workspace of the fp32 backward (either kernel)
-_NO_QUERY = ('SUNERF_BACKWARD_PRECISION=exact: the fp32 backward recomputes the activations from the query points, and this '
-             'backward was given none (pass times= / query=); the fp16 kernels are not run in its place')
 
 
 def _mlp_backward_exact(packed: PackedMLP, g_raw, query, grad_weights, grad_biases, accumulate: bool, chunked: bool = False):
@@ -778,17 +902,13 @@ def _mlp_backward_exact(packed: PackedMLP, g_raw, query, grad_weights, grad_bias
     lib = _l.load()
     dev = g_raw.device
     n, s = g_raw.shape[0], g_raw.shape[1]
-    ws_, bs_ = packed._keepalive          # fp32 parameters of the kernel shapes (the padded copies for padded models)
+    weights, biases = packed.kernel_params()
     nl = packed.n_linear
     if chunked:
         nbytes = lib.sunerf_mlp_backward_exact_chunked_workspace_bytes(packed.d_filter, nl)
     else:
         nbytes = lib.sunerf_mlp_backward_exact_workspace_bytes(n * s, packed.d_filter, nl)
     ws = _workspace(_exact_ws, dev, nbytes)
-    W = (ctypes.c_void_p * nl)(*[w.data_ptr() for w in ws_])
-    B = (ctypes.c_void_p * nl)(*[b.data_ptr() for b in bs_])
-    GW = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in grad_weights])
-    GB = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in grad_biases])
     if query[0] == 'rays':
         _, o, d, t, z = query
         o, d = _dev(o, 'rays_o', (n, 3)), _dev(d, 'rays_d', (n, 3))
@@ -799,8 +919,9 @@ def _mlp_backward_exact(packed: PackedMLP, g_raw, query, grad_weights, grad_bias
         args = (None, None, None, None, _ptr(pts))
     g = g_raw if g_raw.shape[-1] == packed.d_out else g_raw[..., :packed.d_out]       # (N, S, d_out), densely packed
     g = _dev(g, 'g_raw')
-    _l.call(dev, 'sunerf_mlp_backward_exact_chunked' if chunked else 'sunerf_mlp_backward_exact', W, B, nl, packed.d_filter,
-            packed.d_out, *args, n, s, _ptr(g), _ptr(ws), nbytes, GW, GB, int(accumulate), _stream(dev))
+    _l.call(dev, 'sunerf_mlp_backward_exact_chunked' if chunked else 'sunerf_mlp_backward_exact', _ptr_array(weights), _ptr_array(biases),
+            nl, packed.d_filter, packed.d_out, *args, n, s, _ptr(g), _ptr(ws), nbytes, _ptr_array(grad_weights), _ptr_array(grad_biases),
+            int(accumulate), _stream(dev))
 
 
 def mlp_input_backward(packed: PackedMLP, g_raw, query, grad_weights=None, grad_biases=None, accumulate: bool = False,
@@ -826,158 +947,37 @@ def mlp_input_backward(packed: PackedMLP, g_raw, query, grad_weights=None, grad_
             raise ValueError('mlp_input_backward: no ray gradient wanted')
         args = (_ptr(o), _ptr(d), _ptr(t), _ptr(z), None)
         out_ptrs = (None,) + tuple(_ptr(x) for x in outs)
+        result = tuple(outs)
     else:
         n, s = query[1].shape[0], 1
         pts = _dev(query[1], 'points', (n, 4))
         g = g_raw.reshape(n, -1)[:, :packed.d_out]
-        outs = torch.empty(n, 4, **f32)
+        result = torch.empty(n, 4, **f32)
+        outs = [result]
         args = (None, None, None, None, _ptr(pts))
-        out_ptrs = (_ptr(outs), None, None, None, None)
+        out_ptrs = (_ptr(result), None, None, None, None)
     g = _dev(g, 'g_raw')
     params = grad_weights is not None
-    kernel_w, kernel_b, kernel_accumulate = grad_weights, grad_biases, accumulate
+    GW = GB = None
+    kernel_accumulate, fold = accumulate, None
     if params:
-        if len(grad_weights) != nl or len(grad_biases) != nl:
-            raise ValueError('one weight and one bias gradient buffer per layer')
-        for i, (gw, gb) in enumerate(zip(grad_weights, grad_biases)):
-            d_in = packed.d_in if i == 0 else packed.d_model
-            d_o = packed.d_out if i == nl - 1 else packed.d_model
-            if gw.shape != (d_o, d_in) or gb.shape != (d_o,) or gw.dtype != torch.float32 or gb.dtype != torch.float32 \
-                    or not gw.is_contiguous() or not gb.is_contiguous():
-                raise ValueError(f'grad buffer {i} has the wrong shape / layout')
-        if packed.padded:      # the kernel writes the padded shapes (PackedMLP.__init__); the model's are their leading blocks
-            if getattr(packed, '_pad_gw', None) is None:
-                packed._pad_gw = [torch.empty(ws, **f32) for ws, _ in packed.kernel_shapes()]
-                packed._pad_gb = [torch.empty(bs, **f32) for _, bs in packed.kernel_shapes()]
-            kernel_w, kernel_b, kernel_accumulate = packed._pad_gw, packed._pad_gb, False
+        kernel_w, kernel_b, kernel_accumulate, fold = packed.stage_grads(grad_weights, grad_biases, accumulate)
+        GW, GB = _ptr_array(kernel_w), _ptr_array(kernel_b)
     if n * s == 0:
-        for x in (outs if isinstance(outs, list) else [outs]):
-            if x is not None:
-                x.zero_()
+        zero = [x for x in outs if x is not None]
         if params and not accumulate:
-            for gw, gb in zip(grad_weights, grad_biases):
-                gw.zero_()
-                gb.zero_()
-        return tuple(outs) if isinstance(outs, list) else outs
-    ws_, bs_ = packed._keepalive          # fp32 parameters of the kernel shapes (the padded copies for padded models)
+            zero += [*grad_weights, *grad_biases]
+        for t in zero:
+            t.zero_()
+        return result
+    weights, biases = packed.kernel_params()
     nbytes = lib.sunerf_mlp_input_grad_exact_workspace_bytes(packed.d_filter, nl)
     ws = _workspace(_exact_ws, dev, nbytes)
-    W = (ctypes.c_void_p * nl)(*[w.data_ptr() for w in ws_])
-    B = (ctypes.c_void_p * nl)(*[b.data_ptr() for b in bs_])
-    GW = (ctypes.c_void_p * nl)(*[x.data_ptr() for x in kernel_w]) if params else None
-    GB = (ctypes.c_void_p * nl)(*[x.data_ptr() for x in kernel_b]) if params else None
-    _l.call(dev, 'sunerf_mlp_input_grad_exact', W, B, nl, packed.d_filter, packed.d_out, *args, n, s, _ptr(g), _ptr(ws), nbytes,
-            GW, GB, int(kernel_accumulate), *out_ptrs, _stream(dev))
-    if params and packed.padded:
-        for gw, gb, pw, pb in zip(grad_weights, grad_biases, kernel_w, kernel_b):
-            if accumulate:
-                gw.add_(pw[:gw.shape[0], :gw.shape[1]])
-                gb.add_(pb[:gb.shape[0]])
-            else:
-                gw.copy_(pw[:gw.shape[0], :gw.shape[1]])
-                gb.copy_(pb[:gb.shape[0]])
-    return tuple(outs) if isinstance(outs, list) else outs
-
-
-def mlp_backward(packed: PackedMLP, g_raw, absmax, stash, grad_weights: Sequence[torch.Tensor],
-                 grad_biases: Sequence[torch.Tensor], accumulate: bool = False, query=None):
-    """dgrad + wgrad of the sine MLP from the gradient w.r.t. its raw output (N,S,2): fills / accumulates the nn.Linear
-    gradients.  ``absmax``: 4-byte device scalar with the bit pattern of max |g_raw| (written by the integral backward).
-    ``query``: what the forward was evaluated on -- ``('rays', rays_o, rays_d, times, z_vals)`` or ``('points', points (N*S, 4))``;
-    given it, batches of at most ``exact_backward_limit()`` samples take the fp32 backward (csrc/bwd_exact.hip), and under
-    ``SUNERF_BACKWARD_PRECISION=exact`` every batch does (the any-size kernel; no stash is read, ``stash`` may be None)."""
-    lib = _l.load()
-    n, s = g_raw.shape[0], g_raw.shape[1]
-    dev = g_raw.device
-    D, nl = packed.d_filter, packed.n_linear
-    stream = _stream(dev)
-    exact_any = backward_precision() == 'exact'
-    if exact_any and query is None:
-        raise _l.SunerfHipError(_NO_QUERY)
-    exact = exact_any or _use_exact_backward(n * s, query)
-    pipe_bytes = 0
-    if n > 0 and not exact:
-        # the forward chose the stash format for the backward it expected (training_stash_format): phases are read by the
-        # pipelined kernel only, fp16 sin + cos fragments by the two kernels only
-        fmt = stash_format_of(stash, n, s, packed)
-        if fmt == STASH_PHASE:
-            if backward_mode() != 'pipe':
-                raise _l.SunerfHipError('this activation stash holds 16-bit phases (written for the layer-pipelined backward) but the '
-                                        'two-kernel backward was selected after the forward ran: choose SUNERF_BACKWARD before the forward, '
-                                        'or SUNERF_STASH=fp16')
-            with torch.cuda.device(dev):
-                pipe_bytes = lib.sunerf_bwd_pipe_workspace_bytes(n, s, D, nl)
-            if not pipe_bytes:
-                raise _l.SunerfHipError('phase stash but no pipelined backward for this shape / device')
-    if not pipe_bytes and not exact:
-        dz = torch.empty(lib.sunerf_dz_stash_bytes(n, s, D, nl), dtype=torch.uint8, device=dev)
-        _l.call(dev, 'sunerf_mlp_dgrad', _ptr(packed.transposed()), D, nl, _ptr(g_raw), _ptr(absmax), _ptr(stash),
-                _ptr(dz), n, s, stream)
-        cus = torch.cuda.get_device_properties(dev).multi_processor_count
-        cap = int(os.environ.get('SUNERF_GRID_CAP_WGRAD', 0))        # experiment knob, see csrc/sunerf_common.h
-        split = wgrad_split(nl, cap if 0 < cap < cus else cus, D)
-        ws = torch.empty(lib.sunerf_wgrad_workspace_bytes(packed.d_filter, nl, split), dtype=torch.uint8, device=dev)
-    out_w, out_b = list(grad_weights), list(grad_biases)
-    if packed.padded:
-        # zero-padded model (PackedMLP.__init__): the kernels produce gradients of the padded shapes; the model's are their
-        # leading blocks (the padding's own gradients are discarded: those weights are not parameters)
-        for i, (gw, gb) in enumerate(zip(out_w, out_b)):
-            d_in = packed.d_in if i == 0 else packed.d_model
-            d_o = packed.d_out if i == nl - 1 else packed.d_model
-            if gw.shape != (d_o, d_in) or gb.shape != (d_o,) or gw.dtype != torch.float32:
-                raise ValueError(f'grad buffer {i} has the wrong shape / layout')
-        if getattr(packed, '_pad_gw', None) is None:
-            f32 = dict(dtype=torch.float32, device=dev)
-            packed._pad_gw = [torch.empty(ws, **f32) for ws, _ in packed.kernel_shapes()]
-            packed._pad_gb = [torch.empty(bs, **f32) for _, bs in packed.kernel_shapes()]
-        grad_weights, grad_biases, kernel_accumulate = packed._pad_gw, packed._pad_gb, False
-    else:
-        kernel_accumulate = accumulate
-    for i, (gw, gb) in enumerate(zip(grad_weights, grad_biases)):
-        d_in = 84 if i == 0 else D
-        d_o = packed.d_out if i == nl - 1 else D
-        if gw.shape != (d_o, d_in) or gb.shape != (d_o,) or not gw.is_contiguous() or gw.dtype != torch.float32:
-            raise ValueError(f'grad buffer {i} has the wrong shape / layout')
-    GW = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in grad_weights])
-    GB = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in grad_biases])
-    if exact_any and n * s == 0:
-        if not kernel_accumulate:
-            for gw, gb in zip(grad_weights, grad_biases):
-                gw.zero_()
-                gb.zero_()
-    elif exact:
-        _mlp_backward_exact(packed, g_raw, query, grad_weights, grad_biases, kernel_accumulate, chunked=exact_any)
-    elif pipe_bytes:
-        ws = _pipe_workspace(dev, pipe_bytes)
-        flags = _pipe_flags()
-        if pipe_w_mode() == 'auto':
-            with packed._lock:
-                due = (getattr(packed, '_pipe_probe_version', None) is None
-                       or packed._version - packed._pipe_probe_version >= PROBE_EVERY)
-                if due and n >= PIPE_W_PROBE_RAYS and getattr(packed, '_pipe_w_pending', None) is None:
-                    k = PIPE_W_PROBE_RAYS
-
-                    def call_prefix(gw, gb, hi_only):      # the first k rays: a prefix of g_raw and of the (ray-major) stash
-                        _l.call(dev, 'sunerf_mlp_backward_pipe', D, nl, packed.d_out, _ptr(packed.transposed()), _ptr(stash),
-                                _ptr(g_raw), _ptr(absmax), k, s, _ptr(ws), pipe_bytes, gw, gb, 0, (flags & ~0x81) | hi_only, stream)
-                    _pipe_w_probe(packed, call_prefix)
-                _pipe_w_apply(packed)
-                if getattr(packed, 'pipe_hi_only', False):
-                    flags |= 1
-        pargs = (D, nl, packed.d_out, _ptr(packed.transposed()), _ptr(stash), _ptr(g_raw), _ptr(absmax), n, s, _ptr(ws),
-                 pipe_bytes, GW, GB, int(kernel_accumulate))
-        _l.call(dev, 'sunerf_mlp_backward_pipe', *pargs, flags, stream)
-    else:
-        _l.call(dev, 'sunerf_mlp_wgrad', D, nl, packed.d_out, _ptr(packed.transposed()), _ptr(stash), _ptr(dz), _ptr(g_raw), _ptr(absmax), n, s, _ptr(ws),
-                split, GW, GB, int(kernel_accumulate), stream)
-    if packed.padded:
-        for gw, gb, pw, pb in zip(out_w, out_b, grad_weights, grad_biases):
-            if accumulate:
-                gw.add_(pw[:gw.shape[0], :gw.shape[1]])
-                gb.add_(pb[:gb.shape[0]])
-            else:
-                gw.copy_(pw[:gw.shape[0], :gw.shape[1]])
-                gb.copy_(pb[:gb.shape[0]])
+    _l.call(dev, 'sunerf_mlp_input_grad_exact', _ptr_array(weights), _ptr_array(biases), nl, packed.d_filter, packed.d_out, *args, n, s,
+            _ptr(g), _ptr(ws), nbytes, GW, GB, int(kernel_accumulate), *out_ptrs, _stream(dev))
+    if params:
+        fold()
+    return result
 
 
 AIA_WAVELENGTHS = (94, 131, 171, 193, 211, 304, 335)
@@ -986,7 +986,6 @@ AIA_WAVELENGTHS = (94, 131, 171, 193, 211, 304, 335)
 def dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_resp, log_abs, vol_c, base_log_density,
                     base_log_temperature, pixel_intensity_factor, reg_radius, want_epilogues=False):
     """DT radiative-transfer integral on the raw MLP output (density_temperature.py:192-274)."""
-    lib = _l.load()
     n, s = z_vals.shape
     dev = z_vals.device
     w = wavelengths.shape[1]
@@ -1011,7 +1010,6 @@ def dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_
 
 def simple_star_field(rays_o, rays_d, z_vals, rho_0: float, h0: float, T0: float, Rs: float, t_photosphere: float):
     """SimpleStar.forward (stellar_model.py:53-102) at the sample points of every ray -> raw (N, S, 2) = (ln rho, log10 T)."""
-    lib = _l.load()
     n, s = z_vals.shape
     rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3)); z_vals = _dev(z_vals, 'z_vals', (n, s))
     raw = torch.empty(n, s, 2, dtype=torch.float32, device=z_vals.device)

@@ -1,5 +1,5 @@
 """The fp32 backward for small batches (csrc/bwd_exact.hip, sunerf_mlp_backward_exact) against the oracle's autograd, the
-policy that selects it (sunerf_hip/ops.py:_use_exact_backward), and a fixed slice of the randomised parity sweep
+policy that selects it (sunerf_hip/ops.py:_backward_path), and a fixed slice of the randomised parity sweep
 (tests/tools/fuzz_parity.py) with every gradient tensor -- biases included -- at SURVEY 8d's 1e-3."""
 import os
 import sys

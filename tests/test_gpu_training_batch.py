@@ -324,8 +324,9 @@ def test_bench_training_step_against_float64(ops, default_policy):
         errs += [(_rel(gw, W.grad), f'W{i}'), (_rel(gbias, b.grad), f'b{i}')]
     norm64 = torch.sqrt(sum((W.grad ** 2).sum() + (b.grad ** 2).sum() for W, b in leaves)).item()
     e_norm = abs(norm - norm64) / norm64
-    print(f'\n(c) bench step, {N} rays x {S}, AUTO forward {arith}, W^T single fp16: {getattr(model.packed(), "pipe_hi_only", None)}'
-          f' (probe {getattr(model.packed(), "pipe_w_probe", float("nan")):.2e})')
+    w_probe = model.packed().pipe_w_probe            # None: no W^T probe ran (not the pipelined backward, or its arithmetic was forced)
+    print(f'\n(c) bench step, {N} rays x {S}, AUTO forward {arith}, W^T single fp16: {model.packed().pipe_hi_only}'
+          f' (probe {float("nan") if w_probe is None else w_probe:.2e})')
     print(f'    loss {loss.item():.6e} vs float64 {loss64:.6e}: {e_loss:.1e} (bound 2e-4); gradient norm {norm:.6e} vs {norm64:.6e}: '
           f'{e_norm:.1e} (bound 1e-3)')
     print('    gradient tensors vs float64: ' + ' '.join(f'{w} {e:.1e}' for e, w in errs) + f'; worst {max(errs)[0]:.2e}')

@@ -110,6 +110,83 @@ def test_environment_switches(monkeypatch):
     assert ops.pipe_w_mode() == 'hilo' and ops._pipe_flags() == 2
 
 
+def test_backward_path_table(monkeypatch):
+    """ops._backward_path, row by row (the policy stated above it in ops.py; tests/test_gpu_exact.py pins the same on the device).
+    "By name" = ``_backward_forced`` set or SUNERF_BACKWARD non-empty.  The stash format and the pipelined workspace query are
+    asked lazily: an fp32 backward may have no stash at all, so the fp32 rows must not touch them."""
+    from sunerf_hip import ops, SunerfHipError
+    for name in ('SUNERF_BACKWARD', 'SUNERF_BACKWARD_PRECISION', 'SUNERF_EXACT_BACKWARD_SAMPLES'):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setattr(ops, '_backward_forced', None)
+    limit = ops.exact_backward_limit()
+    assert limit == ops.EXACT_BACKWARD_SAMPLES == 4096
+
+    def untouched():
+        raise AssertionError('asked for the stash format / the pipelined workspace on a row that is decided without them')
+
+    def path(n, s, query, fmt=untouched, pipe=untouched):
+        fmt_of = fmt if callable(fmt) else (lambda: fmt)
+        pipe_ok = pipe if callable(pipe) else (lambda: pipe)
+        return ops._backward_path(n, s, query, fmt_of, pipe_ok)
+    phase, fp16 = ops.STASH_PHASE, ops.STASH_FP16
+
+    # SUNERF_BACKWARD_PRECISION=exact: no query is an error, an empty batch launches nothing, everything else is the any-size kernel
+    monkeypatch.setenv('SUNERF_BACKWARD_PRECISION', 'exact')
+    with pytest.raises(SunerfHipError, match='was given none'):
+        path(64, 128, False)
+    with pytest.raises(SunerfHipError, match='was given none'):
+        path(0, 128, False)
+    assert path(0, 128, True) == 'empty' and path(64, 0, True) == 'empty'
+    assert path(1, 1, True) == 'fp32_chunked' and path(32768, 128, True) == 'fp32_chunked'
+    monkeypatch.setenv('SUNERF_BACKWARD', 'classic')            # a forced kernel does not outrank the precision
+    assert path(32768, 128, True) == 'fp32_chunked'
+    monkeypatch.setattr(ops, '_backward_forced', 'pipe')
+    assert path(8, 128, True) == 'fp32_chunked'
+    monkeypatch.setattr(ops, '_backward_forced', None)
+    monkeypatch.delenv('SUNERF_BACKWARD')
+    monkeypatch.setenv('SUNERF_BACKWARD_PRECISION', 'default')
+
+    # small batches with a query: fp32, up to the limit inclusive, unless a kernel was asked for by name
+    assert path(1, 1, True) == 'fp32' and path(32, 128, True) == 'fp32' and path(1, limit, True) == 'fp32'
+    assert path(1, limit + 1, True, fp16) == 'classic'
+    assert path(32, 128, False, fp16) == 'classic'               # no query: nothing to recompute the activations from
+    monkeypatch.setenv('SUNERF_EXACT_BACKWARD_SAMPLES', '100')
+    assert path(1, 100, True) == 'fp32' and path(1, 101, True, fp16) == 'classic'
+    monkeypatch.setenv('SUNERF_EXACT_BACKWARD_SAMPLES', '0')
+    assert path(1, 1, True, fp16) == 'classic'
+    monkeypatch.delenv('SUNERF_EXACT_BACKWARD_SAMPLES')
+    for forced, env in (('classic', None), ('pipe', None), (None, 'classic'), (None, 'pipe')):
+        monkeypatch.setattr(ops, '_backward_forced', forced)
+        if env is not None:
+            monkeypatch.setenv('SUNERF_BACKWARD', env)
+        assert path(32, 128, True, fp16) == 'classic', (forced, env)
+        if 'classic' not in (forced, env):
+            assert path(32, 128, True, phase, True) == 'pipe', (forced, env)
+        monkeypatch.delenv('SUNERF_BACKWARD', raising=False)
+    monkeypatch.setattr(ops, '_backward_forced', None)
+    monkeypatch.setenv('SUNERF_BACKWARD', '  ')                  # blank is not a name
+    assert path(32, 128, True) == 'fp32'
+    monkeypatch.delenv('SUNERF_BACKWARD')
+
+    # a phase stash: the pipelined kernel, or an error where it can no longer run
+    assert path(32768, 128, True, phase, True) == 'pipe' and path(32768, 128, False, phase, True) == 'pipe'
+    with pytest.raises(SunerfHipError, match='phase stash but no pipelined backward'):
+        path(32768, 128, True, phase, False)
+    for forced, env in (('classic', None), (None, 'classic')):
+        monkeypatch.setattr(ops, '_backward_forced', forced)
+        if env is not None:
+            monkeypatch.setenv('SUNERF_BACKWARD', env)
+        with pytest.raises(SunerfHipError, match='selected after the forward ran'):
+            path(32768, 128, True, phase)                        # ... and the workspace query is not even made
+        monkeypatch.delenv('SUNERF_BACKWARD', raising=False)
+    monkeypatch.setattr(ops, '_backward_forced', None)
+
+    # everything else: the two kernels -- an fp16 stash (the workspace query is not made), and n == 0 whatever the stash
+    assert path(32768, 128, True, fp16) == 'classic' and path(32768, 128, False, fp16) == 'classic'
+    assert path(0, 128, True) == 'classic' and path(0, 128, False) == 'classic'
+    assert path(64, 0, True, fp16) == 'classic'                  # rays without samples: the stash is looked at, fp32 is not taken
+
+
 def test_bucket_registry_is_keyed_by_identity_and_holds_no_strong_references():
     """The optimiser finds its flat bucket through an identity-keyed weak registry, not through an attribute on the Parameter
     (the attribute pickled the optimiser into every checkpoint)."""
