@@ -20,6 +20,7 @@
 // emission integral (render_fwd.hip, render_bwd.hip).  (The first version walked the samples with ONE thread per ray and
 // channel: 1.2 ms for the backward of 8192 rays x 256 samples x 7 channels, 10 % of a config-5 training step.)
 #include "sunerf_common.h"
+#include "dt_response.h"      // NCH, NTAB, channel_of(), response(): shared with volume.hip
 #include "../../include/sunerf_hip.h"
 
 namespace {
@@ -27,8 +28,6 @@ namespace {
 constexpr int DT_THREADS = 256;
 constexpr int DT_RAYS = DT_THREADS / 32;      // rays per workgroup (and per step of its walk over the batch)
 constexpr int DT_MAX_GRID = 1024;             // backward: workgroups of the grid
-constexpr int NCH = 7;
-constexpr int NTAB = NCH * 101;
 constexpr int DT_BWD_LDS_HEAD = 2 * NTAB + 8 + DT_THREADS / 64;   // backward LDS floats before the exp(-A) slabs
 
 struct DtArgs {
@@ -61,26 +60,6 @@ struct DtArgs {
   const float* g_weights;    // (N,S) or null (EXTRA backward only)
   const float* g_reg_q;      // (N,S) or null (EXTRA backward only)
 };
-
-__device__ __forceinline__ int channel_of(float wl) {
-  const float w[NCH] = {94.f, 131.f, 171.f, 193.f, 211.f, 304.f, 335.f};
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) if (wl == w[c]) return c;
-  return -1;
-}
-
-// linear interpolation on the 101-point grid; returns value and slope (both 0 outside [x0, x100])
-__device__ __forceinline__ void response(const float* lt, const float* rs, float x, float& val, float& slope) {
-  val = 0.f; slope = 0.f;
-  if (!(x >= lt[0] && x <= lt[100])) return;
-  int i = (int)((x - lt[0]) * 20.f);              // grid step 0.05
-  i = max(0, min(99, i));
-  while (i < 99 && lt[i + 1] <= x) ++i;            // searchsorted(right=True) - 1, clamped to the last interval
-  while (i > 0 && lt[i] > x) --i;
-  const float x0 = lt[i], x1 = lt[i + 1], y0 = rs[i], y1 = rs[i + 1];
-  slope = (y1 - y0) / (x1 - x0);
-  val = y0 + (x - x0) * (y1 - y0) / (x1 - x0);
-}
 
 __device__ __forceinline__ float scan_up32(float v, int n) {      // inclusive prefix sum over the 32 lanes of a ray
 #pragma unroll

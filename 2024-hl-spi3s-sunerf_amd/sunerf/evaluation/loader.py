@@ -19,6 +19,7 @@ import torch
 
 from sunerf_hip.maps import render_columns
 from sunerf_hip.rays import pose_spherical, render_frame
+from sunerf_hip.volume import QUANTITIES, CartesianGrid, Plane, sample_volume
 
 AU_IN_SOLAR_RADII = 215.03215567054764      # (1 * u.AU).to(u.solRad), IAU 2012 / 2015 nominal values
 ARCSEC = np.pi / 180. / 3600.
@@ -239,6 +240,55 @@ class SuNeRFLoader:
         time = normalize_datetime(time, self.seconds_per_dt, self.ref_time)
         return self._columns(lats, lons, time, False, r_range, n_samples, batch_size, profiles, None, as_numpy)
 
+    def _volume(self, time: float, grid, wl, quantities, r_range, fill, batch_size, as_numpy):
+        out = sample_volume(self.rendering, grid, float(time), None if wl is None else np.asarray(wl, dtype=np.float32),
+                            quantities, r_range, fill, tile_points=None if batch_size is None else int(batch_size))
+        if not as_numpy:
+            return out
+        return {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in out.items()}
+
+    @staticmethod
+    def _cube(half_width, shape, grid):
+        if grid is not None:
+            return grid
+        n = (int(shape),) * 3 if np.isscalar(shape) else tuple(int(s) for s in shape)
+        hw = (_solar_radii(half_width),) * 3 if np.isscalar(half_width) or hasattr(half_width, 'to_value') else \
+            tuple(_solar_radii(h) for h in half_width)
+        if len(n) != 3 or len(hw) != 3:
+            raise ValueError('a volume has three axes: shape and half_width are a number or three of them')
+        return CartesianGrid(*(np.linspace(-h, h, k) for h, k in zip(hw, n)))
+
+    @staticmethod
+    def _slice(origin, e_u, e_v, half_width, shape):
+        n = (int(shape),) * 2 if np.isscalar(shape) else tuple(int(s) for s in shape)
+        hw = (_solar_radii(half_width),) * 2 if np.isscalar(half_width) or hasattr(half_width, 'to_value') else \
+            tuple(_solar_radii(h) for h in half_width)
+        if len(n) != 2 or len(hw) != 2:
+            raise ValueError('a slice has two axes: shape and half_width are a number or two of them')
+        return Plane(origin, e_u, e_v, np.linspace(-hw[0], hw[0], n[0]), np.linspace(-hw[1], hw[1], n[1]))
+
+    @torch.no_grad()
+    def render_volume(self, time: datetime, half_width=1.3, shape=256, grid=None, quantities=None, r_range=(1.0, None),
+                      fill: float = float('nan'), batch_size: Optional[int] = None, as_numpy: bool = True):
+        """3-D volume of the fine model at ``time`` (a datetime) (sunerf/evaluation/stash/voxel_volume.py:30-56): the cube
+        ``linspace(-half_width, half_width, shape)`` per axis [solar radii], plain C order ``(x, y, z)`` (the reference's
+        ``np.meshgrid`` default swaps x and y), or any ``grid`` of ``sunerf_hip.volume`` (``CartesianGrid``, ``Plane``,
+        ``SphericalGrid``).  Returns the outputs of ``sunerf_hip.volume.sample_volume``: ``inferences (*grid.shape, 2)``,
+        ``radius``, ``grid``, ``times`` and the physical quantities (``emission`` and ``absorption`` for an emission model),
+        ``fill`` where the radius is outside ``r_range`` (default: inside the Sun).  ``batch_size``: voxels per tile."""
+        time = normalize_datetime(time, self.seconds_per_dt, self.ref_time)
+        return self._volume(time, self._cube(half_width, shape, grid), None, quantities, r_range, fill, batch_size, as_numpy)
+
+    @torch.no_grad()
+    def render_slice(self, time: datetime, origin=(0., 0., 0.), e_u=(1., 0., 0.), e_v=(0., 1., 0.), half_width=1.3, shape=512,
+                     quantities=None, r_range=(1.0, None), fill: float = float('nan'), batch_size: Optional[int] = None,
+                     as_numpy: bool = True):
+        """A plane through the fine model at ``time`` (a datetime): points ``origin + u e_u + v e_v`` [solar radii] with
+        ``u, v = linspace(-half_width, half_width, shape)``; outputs as :meth:`render_volume`, shaped ``(n_u, n_v, ...)``."""
+        time = normalize_datetime(time, self.seconds_per_dt, self.ref_time)
+        return self._volume(time, self._slice(origin, e_u, e_v, half_width, shape), None, quantities, r_range, fill, batch_size,
+                            as_numpy)
+
     def normalize_datetime(self, time):
         return normalize_datetime(time, self.seconds_per_dt, self.ref_time)
 
@@ -301,6 +351,21 @@ class ModelLoader(SuNeRFLoader):
         """:meth:`SuNeRFLoader.render_radial_profile` with ``time`` already normalised (a float) and the channels ``wl``."""
         return self._columns(lats, lons, time, False, r_range, n_samples, batch_size, profiles, wl, as_numpy)
 
+    @torch.no_grad()
+    def render_volume(self, time: float, half_width=1.3, shape=256, grid=None, wl: Optional[np.ndarray] = None, quantities=None,
+                      r_range=(1.0, None), fill: float = float('nan'), batch_size: Optional[int] = None, as_numpy: bool = True):
+        """:meth:`SuNeRFLoader.render_volume` with ``time`` already normalised (a float) and the channels ``wl`` of a
+        density-temperature rendering (``density``, ``log_temperature``, ``emissivity (..., W)``)."""
+        return self._volume(time, self._cube(half_width, shape, grid), wl, quantities, r_range, fill, batch_size, as_numpy)
+
+    @torch.no_grad()
+    def render_slice(self, time: float, origin=(0., 0., 0.), e_u=(1., 0., 0.), e_v=(0., 1., 0.), half_width=1.3, shape=512,
+                     wl: Optional[np.ndarray] = None, quantities=None, r_range=(1.0, None), fill: float = float('nan'),
+                     batch_size: Optional[int] = None, as_numpy: bool = True):
+        """:meth:`SuNeRFLoader.render_slice` with ``time`` already normalised (a float) and the channels ``wl``."""
+        return self._volume(time, self._slice(origin, e_u, e_v, half_width, shape), wl, quantities, r_range, fill, batch_size,
+                            as_numpy)
+
 
 class EnsembleLoader:
     """K trained members of one model (``.snf`` files) rendered from the same observer (uncertainty_correlation.py:56-77,
@@ -344,6 +409,37 @@ class EnsembleLoader:
         if not as_numpy:
             return out
         return {k: v.cpu().numpy() for k, v in out.items()}
+
+    @torch.no_grad()
+    def render_volume(self, time: datetime, half_width=1.3, shape=256, grid=None, quantities=None, r_range=(1.0, None),
+                      fill: float = float('nan'), batch_size: Optional[int] = None, as_numpy: bool = True):
+        """Every member's :meth:`SuNeRFLoader.render_volume` on the same grid: ``radius``, ``grid`` and ``times`` of member 0
+        and, for each quantity ``q``, ``q_mean`` and ``q_std`` (ddof 0) over the members: two passes in fp64, in member order,
+        then fp32, like :meth:`render_observer_image`.  Masked voxels stay ``fill``-like (NaN) in both.  The members are
+        ``.snf`` loaders, whose ``render_volume`` takes no channels: a density-temperature ensemble gives ``density`` and
+        ``log_temperature`` only."""
+        grid = SuNeRFLoader._cube(half_width, shape, grid)
+        vols = [m.render_volume(time, grid=grid, quantities=quantities, r_range=r_range, fill=fill, batch_size=batch_size,
+                                as_numpy=False) for m in self.loaders]
+        first = vols[0]
+        out = {k: first[k] for k in ('radius', 'grid', 'times', 'Rs_per_ds', 'kind') if k in first}
+        for q in QUANTITIES[first['kind']]:
+            if q not in first:
+                continue
+            fields = [vol[q].double() for vol in vols]
+            mean = fields[0].clone()
+            for f in fields[1:]:
+                mean += f
+            mean /= len(fields)
+            var = torch.zeros_like(mean)
+            for f in fields:
+                var += (f - mean) ** 2
+            var /= len(fields)
+            out[q + '_mean'] = mean.float()
+            out[q + '_std'] = torch.sqrt(var).float()
+        if not as_numpy:
+            return out
+        return {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in out.items()}
 
 
 def _same(a, b) -> bool:

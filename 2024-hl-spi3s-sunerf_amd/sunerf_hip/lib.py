@@ -20,6 +20,12 @@ _lib = None
 c_f32p = ctypes.c_void_p   # device pointers travel as raw addresses
 c_void = ctypes.c_void_p
 
+
+class GridFrame(ctypes.Structure):
+    """``SunerfGridFrame``: origin and the three basis vectors of an affine grid, passed by value."""
+    _fields_ = [('origin', ctypes.c_double * 3), ('basis', (ctypes.c_double * 3) * 3)]
+
+
 _SIGNATURES = {
     'sunerf_abi_version': (ctypes.c_int, []),
     'sunerf_packed_mlp_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
@@ -139,6 +145,15 @@ _SIGNATURES = {
     'sunerf_image_metrics_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'sunerf_image_metrics': (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_void,
                                              c_void, ctypes.c_size_t, c_void]),
+    'sunerf_grid_points': (ctypes.c_int, [ctypes.c_int, c_void, c_void, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, GridFrame,
+                                           ctypes.c_double, ctypes.c_float, ctypes.c_int64, ctypes.c_int64, c_f32p, c_f32p,
+                                           c_void]),
+    'sunerf_field_quantities': (ctypes.c_int, [ctypes.c_int, c_f32p, ctypes.c_int, c_f32p, ctypes.c_int64, ctypes.c_float,
+                                                ctypes.c_float, ctypes.c_float, ctypes.c_float, c_f32p, ctypes.c_int, c_f32p,
+                                                c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_void]),
+    'sunerf_volume_metrics_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64]),
+    'sunerf_volume_metrics': (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void,
+                                              c_void, c_void, ctypes.c_size_t, c_void]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

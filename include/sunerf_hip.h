@@ -493,6 +493,70 @@ int sunerf_column_stats(const float* raw, const float* z_row, const float* rays_
                         float* absorption, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * 3-D volumes of the field: query points of a grid, physical quantities of the model's answer and a
+ * weighted 3-D score.  The MLP between the first two is sunerf_mlp_points_fwd (or a field kernel), unchanged.
+ *
+ * sunerf_grid_points replaces the host-side cube of the reference's sunerf/evaluation/stash/voxel_volume.py:30-44
+ * (np.meshgrid of three linspaces + a time column, pushed to the device batch by batch) and the point arrays its
+ * callers hand to load_coords (evaluation/loader.py:119-134).  Voxels [first, first + count) of a grid of n0 x n1 x n2
+ * nodes, voxel index C-order (last axis fastest):
+ *   points [count, 4] out, fp32, 16-byte aligned = (x, y, z, time_value) in model units;  radius [count] out, fp32 [solar radii]
+ *   SUNERF_GRID_AFFINE:    a0[n0], a1[n1], a2[n2] fp64 device axes [solar radii];
+ *       X = origin + a0[i] e0 + a1[j] e1 + a2[k] e2, per component, left to right, in fp64 (e_m = frame.basis[m]);
+ *       point = fp32(X / Rs_per_ds), radius = fp32(sqrt((X_x^2 + X_y^2) + X_z^2)).  A plane is n2 = 1.
+ *   SUNERF_GRID_SPHERICAL: a0 = [cos lat | sin lat] (2 n0 values), a1 = [cos lon | sin lon] (2 n1), a2 = r[n2] [solar radii],
+ *       fp64, the trig values taken on the host;  X = r_k u, u = (-cos b sin l, cos b cos l, -sin b) (sunerf_column_rays' u);
+ *       point = fp32(X / Rs_per_ds), radius = fp32(r_k).  `frame` is not read.
+ * The library is compiled without floating-point contraction, so a host evaluation of the same fp64 expressions gives
+ * the same bits.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SUNERF_GRID_AFFINE    0
+#define SUNERF_GRID_SPHERICAL 1
+typedef struct SunerfGridFrame {
+  double origin[3];
+  double basis[3][3];      /* basis[m] = e_m */
+} SunerfGridFrame;
+int sunerf_grid_points(int kind, const double* a0, const double* a1, const double* a2, int n0, int n1, int n2,
+                       SunerfGridFrame frame, double Rs_per_ds, float time_value, int64_t first, int64_t count,
+                       float* points, float* radius, void* stream);
+
+/* sunerf_field_quantities: the physical fields of a model's answer, one element-wise launch.
+ *   inferences [M, C] fp32 (C = 2 except white light: C >= 1), radius [M] fp32 (sunerf_grid_points'), outputs fp32:
+ *   SUNERF_FIELD_EMISSION   : out0 = emission = exp(raw0)                                voxel_volume.py:47
+ *                             out1 = absorption = relu(raw1), the coefficient kappa     rendering/emission.py:31-37
+ *   SUNERF_FIELD_DT         : out0 = density = exp(relu(inf0)), out1 = log_temperature = relu(inf1), inf with the base
+ *                             offsets as NeRF_DT.forward returns it                     density_temperature.py:237-241
+ *                             emissivity [M, W] = density^2 R_w(log_temperature)         :245-256, :263
+ *                             absorption_w [M, W] = density relu(log_abs[channel w])     :260-261
+ *                             R_w: the response interpolation of sunerf_dt_integral_fwd (the same device function);
+ *                             wavelengths [W] device, W <= 7; a channel that is not one of the seven gives 0.
+ *                             emissivity / absorption_w may be NULL (then wavelengths and tables are not read).
+ *   SUNERF_FIELD_WHITE_LIGHT: out0 = electron_density = exp(kappa raw0), kappa as sunerf_thomson_integral_fwd   thompson.py:39
+ *   out0 / out1 may be NULL.  A voxel whose radius is not inside [r_in, r_out] (a NaN radius included) gets `fill` in
+ *   every output; r_out = +inf: no outer mask.  exp overflows to +inf as the reference's fp32 does.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SUNERF_FIELD_EMISSION    0
+#define SUNERF_FIELD_DT          1
+#define SUNERF_FIELD_WHITE_LIGHT 2
+int sunerf_field_quantities(int mode, const float* inferences, int n_channels, const float* radius, int64_t n_points,
+                            float r_in, float r_out, float fill, float kappa, const float* wavelengths, int n_wavelengths,
+                            const float* table_logt, const float* table_resp, const float* log_abs, float* out0, float* out1,
+                            float* emissivity, float* absorption_w, void* stream);
+
+/* sunerf_volume_metrics: weighted, masked comparison of two scalar volumes a, b [n0][n1][n2] (fp32), in fp64.  Nothing
+ * in the reference scores a volume; its 2-D scores are sunerf_image_metrics'.
+ *   weight of voxel (i, j, k) = (w0[i] w1[j]) w2[k], fp64 device vectors;  a voxel where a or b is not finite is left out
+ *   out [11] fp64 device = sum w, sum w a, sum w b, sum w d, sum w |d|, sum w d^2, sum w a^2, sum w b^2, sum w a b,
+ *                          max |d|, number of voxels counted (exact below 2^53);  d = a - b
+ *   Per-workgroup partial sums go to `workspace` (sunerf_volume_metrics_workspace_bytes, 8-byte aligned) and a second
+ *   launch adds them in a fixed order: no atomics, reruns are bit-identical; the grid depends on the voxel count only.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SUNERF_VOLUME_METRICS_N 11
+size_t sunerf_volume_metrics_workspace_bytes(int64_t n_voxels);
+int sunerf_volume_metrics(const float* a, const float* b, int n0, int n1, int n2, const double* w0, const double* w1,
+                          const double* w2, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Output side of the path: training loss and optimiser step without host synchronisation.
  *
  * sunerf_training_loss replaces EmissionSuNeRFModule.training_step's loss section, sunerf/model/sunerf.py:105-125
