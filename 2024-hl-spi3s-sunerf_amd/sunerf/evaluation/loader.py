@@ -17,6 +17,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+from sunerf_hip.dem import _dt_rendering, render_dem_columns, render_dem_frame
 from sunerf_hip.maps import render_columns
 from sunerf_hip.rays import pose_spherical, render_frame
 from sunerf_hip.volume import QUANTITIES, CartesianGrid, Plane, sample_volume
@@ -173,7 +174,8 @@ class SuNeRFLoader:
         ty = torch.from_numpy(np.ascontiguousarray(coords.Ty.to_value(u.rad), dtype=np.float64)).to(self.device)
         return tx, ty
 
-    def _render(self, lat, lon, time: float, distance, center, resolution, batch_size, wl=None, as_numpy=True, strides=1):
+    def _frame_grid(self, lat, lon, distance, center, resolution, strides):
+        """Pixel angles (``tx``, ``ty``) and camera pose of the observer's frame, every ``strides``-th pixel of it."""
         target_pose = pose_spherical(-_radians(lon), _radians(lat), _solar_radii(distance), center)
         tx, ty = self._pixel_angles(resolution)
         strides = int(strides)
@@ -184,6 +186,10 @@ class SuNeRFLoader:
                 tx, ty = tx[::strides, ::strides].contiguous(), ty[::strides, ::strides].contiguous()
             else:
                 tx, ty = tx[::strides].contiguous(), ty[::strides].contiguous()
+        return tx, ty, target_pose
+
+    def _render(self, lat, lon, time: float, distance, center, resolution, batch_size, wl=None, as_numpy=True, strides=1):
+        tx, ty, target_pose = self._frame_grid(lat, lon, distance, center, resolution, strides)
         wavelengths = None if wl is None else torch.as_tensor(np.asarray(wl), dtype=torch.float32, device=self.device)
         frame = render_frame(self.rendering, tx, ty, target_pose, float(time), wavelengths, tile_rays=int(batch_size))
         if not as_numpy:
@@ -239,6 +245,59 @@ class SuNeRFLoader:
         per-sample profiles ``(n, n_samples)`` by default."""
         time = normalize_datetime(time, self.seconds_per_dt, self.ref_time)
         return self._columns(lats, lons, time, False, r_range, n_samples, batch_size, profiles, None, as_numpy)
+
+    def _dem_image(self, lat, lon, time: float, distance, center, resolution, batch_size, as_numpy, strides, logt_nodes,
+                   attenuation_wavelength, r_range, length_scale):
+        rendering = _dt_rendering(self.rendering, 'render_dem_image')           # before any device work
+        tx, ty, target_pose = self._frame_grid(lat, lon, distance, center, resolution, strides)
+        r_in = _solar_radii(r_range[0]) / rendering.Rs_per_ds
+        r_out = np.inf if r_range[1] is None else _solar_radii(r_range[1]) / rendering.Rs_per_ds
+        out = render_dem_frame(rendering, tx, ty, target_pose, float(time), logt_nodes, attenuation_wavelength, (r_in, r_out),
+                               tile_rays=int(batch_size), length_scale=length_scale)
+        if not as_numpy:
+            return out
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def _dem_map(self, time: float, lat_range, lon_range, shape, r_range, n_samples, batch_size, as_numpy, logt_nodes,
+                 attenuation_wavelength, length_scale):
+        rendering = _dt_rendering(self.rendering, 'render_dem_map')
+        n_lat, n_lon = (int(shape), int(shape)) if np.isscalar(shape) else (int(shape[0]), int(shape[1]))
+        lat = torch.from_numpy(np.linspace(_radians(lat_range[0]), _radians(lat_range[1]), n_lat)).to(self.device)
+        lon = torch.from_numpy(np.linspace(_radians(lon_range[0]), _radians(lon_range[1]), n_lon)).to(self.device)
+        r_range = (_solar_radii(r_range[0]), _solar_radii(r_range[1]))
+        out = render_dem_columns(rendering, lat, lon, float(time), r_range, n_samples, logt_nodes, attenuation_wavelength,
+                                 None if batch_size is None else int(batch_size), length_scale=length_scale)
+        if not as_numpy:
+            return out
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    @torch.no_grad()
+    def render_dem_image(self, lat, lon, time: datetime, distance=AU_IN_SOLAR_RADII,
+                         center: Tuple[float, float, float] = None, resolution=None, batch_size: int = 1 << 18,
+                         as_numpy: bool = True, strides: int = 1, logt_nodes=None, attenuation_wavelength=None,
+                         r_range=(0., None), length_scale: float = 1.0):
+        """The line-of-sight DEM behind every pixel of :meth:`render_observer_image`'s frame (same observer arguments), for a
+        density-temperature rendering: ``dem`` (H, W, K) on ``logt_nodes`` (default: the response table's log T grid), ``em``,
+        ``logt_mean``, ``column`` (H, W) and ``logt_nodes`` (K,) (``sunerf_hip.dem``).  ``attenuation_wavelength``: attenuate
+        with that channel's absorption; ``r_range`` [solar radii]: only samples at these radii count (default: all);
+        ``length_scale`` multiplies ``dem``, ``em`` and ``column`` (default: the model's length unit, like the render).
+        Raises ``TypeError`` for a rendering without a temperature."""
+        _dt_rendering(self.rendering, 'render_dem_image')
+        time = normalize_datetime(time, self.seconds_per_dt, self.ref_time)
+        return self._dem_image(lat, lon, time, distance, center, resolution, batch_size, as_numpy, strides, logt_nodes,
+                               attenuation_wavelength, r_range, length_scale)
+
+    @torch.no_grad()
+    def render_dem_map(self, time: datetime, lat_range=(-np.pi / 2, np.pi / 2), lon_range=(-np.pi, np.pi), shape=(721, 1441),
+                       r_range=(1.0, 1.3), n_samples: int = 512, batch_size: Optional[int] = None, as_numpy: bool = True,
+                       logt_nodes=None, attenuation_wavelength=None, length_scale: float = 1.0):
+        """The DEM of the radial columns of :meth:`render_heliographic_map` (same grid arguments): ``dem`` (n_lat, n_lon, K),
+        ``em``, ``logt_mean``, ``column`` (n_lat, n_lon) and ``logt_nodes`` (K,); the other arguments as
+        :meth:`render_dem_image`."""
+        _dt_rendering(self.rendering, 'render_dem_map')
+        time = normalize_datetime(time, self.seconds_per_dt, self.ref_time)
+        return self._dem_map(time, lat_range, lon_range, shape, r_range, n_samples, batch_size, as_numpy, logt_nodes,
+                             attenuation_wavelength, length_scale)
 
     def _volume(self, time: float, grid, wl, quantities, r_range, fill, batch_size, as_numpy):
         out = sample_volume(self.rendering, grid, float(time), None if wl is None else np.asarray(wl, dtype=np.float32),
@@ -350,6 +409,22 @@ class ModelLoader(SuNeRFLoader):
                               as_numpy: bool = True):
         """:meth:`SuNeRFLoader.render_radial_profile` with ``time`` already normalised (a float) and the channels ``wl``."""
         return self._columns(lats, lons, time, False, r_range, n_samples, batch_size, profiles, wl, as_numpy)
+
+    @torch.no_grad()
+    def render_dem_image(self, lat, lon, time: float, distance=AU_IN_SOLAR_RADII, center: Tuple[float, float, float] = None,
+                         resolution=None, batch_size: int = 1 << 17, as_numpy: bool = True, strides: int = 1, logt_nodes=None,
+                         attenuation_wavelength=None, r_range=(0., None), length_scale: float = 1.0):
+        """:meth:`SuNeRFLoader.render_dem_image` with ``time`` already normalised (a float)."""
+        return self._dem_image(lat, lon, time, distance, center, resolution, batch_size, as_numpy, strides, logt_nodes,
+                               attenuation_wavelength, r_range, length_scale)
+
+    @torch.no_grad()
+    def render_dem_map(self, time: float, lat_range=(-np.pi / 2, np.pi / 2), lon_range=(-np.pi, np.pi), shape=(721, 1441),
+                       r_range=(1.0, 1.3), n_samples: int = 512, batch_size: Optional[int] = None, as_numpy: bool = True,
+                       logt_nodes=None, attenuation_wavelength=None, length_scale: float = 1.0):
+        """:meth:`SuNeRFLoader.render_dem_map` with ``time`` already normalised (a float)."""
+        return self._dem_map(time, lat_range, lon_range, shape, r_range, n_samples, batch_size, as_numpy, logt_nodes,
+                             attenuation_wavelength, length_scale)
 
     @torch.no_grad()
     def render_volume(self, time: float, half_width=1.3, shape=256, grid=None, wl: Optional[np.ndarray] = None, quantities=None,

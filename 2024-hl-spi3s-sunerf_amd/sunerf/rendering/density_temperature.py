@@ -3,7 +3,8 @@ import torch
 
 from sunerf.model.model import NeRF_DT
 from sunerf.rendering.base_tracing import SuNeRFRendering, field_on_query_points
-from sunerf.rendering.functional import dt_pass, dt_raw2outputs
+from sunerf.rendering.functional import _field_raw, dt_pass, dt_raw2outputs
+from sunerf_hip import ops
 from sunerf_hip.genx import CHANNELS, read_aia_temp_resp
 
 
@@ -107,6 +108,68 @@ class DensityTemperatureRadiativeTransfer(SuNeRFRendering):
         return {'z_vals_stratified': z_vals, 'coarse_image': coarse['image'], 'z_vals_hierarchical': new_z,
                 'fine_image': fine['image'], 'image': fine['image'], 'height_map': fine['height_map'],
                 'absorption_map': fine['absorption_map'], 'regularization': fine['regularization']}
+
+    # ---- line-of-sight DEM (sunerf_hip/dem.py) ---------------------------------------------------------------
+    def dem_nodes(self, logt_nodes=None):
+        """The log T nodes of a DEM as a float32 device vector: ``logt_nodes``, or the response table's own grid."""
+        if logt_nodes is None:
+            return self.response_logte[0].contiguous()
+        return torch.as_tensor(logt_nodes, dtype=torch.float32).to(self.response_logte.device).contiguous()
+
+    def attenuation_scalar(self, attenuation_wavelength=None):
+        """The fine model's ``log_absortpion`` scalar of channel ``attenuation_wavelength`` as a one-element device tensor
+        (no host read), or None for an optically thin DEM."""
+        if attenuation_wavelength is None:
+            return None
+        try:
+            key = str(int(attenuation_wavelength))
+            ok = float(attenuation_wavelength) == int(attenuation_wavelength)
+        except (TypeError, ValueError):
+            key, ok = repr(attenuation_wavelength), False
+        if not ok or key not in self.fine_model.log_absortpion:
+            raise ValueError(f'attenuation_wavelength {attenuation_wavelength!r} is not a channel of the model '
+                             f'({", ".join(self.fine_model.log_absortpion.keys())})')
+        return self.fine_model.log_absortpion[key].detach().float().reshape(1)
+
+    @torch.no_grad()
+    def fine_raw(self, rays_o, rays_d, times, z_vals):
+        """The fine field's ``raw`` (N, S, 2) at the samples, without the base offsets, obtained the way ``dt_pass`` obtains
+        it: the fused MLP kernel for a ``NeRF_DT``, ``field_on_rays`` for a ``SimpleStar`` / ``MHDModel``."""
+        model = self.fine_model
+        if hasattr(model, 'field_on_rays'):
+            return _field_raw(model, rays_o, rays_d, z_vals, times)
+        return ops.emission_render_fwd(model.packed(), rays_o, rays_d, times, z_vals, 0.0, want_raw=True,
+                                       probe_sensitivity=2.0)['raw']
+
+    @torch.no_grad()
+    def render_dem(self, rays_o, rays_d, times, logt_nodes=None, attenuation_wavelength=None, r_range=(0., float('inf'))):
+        """The thermal structure behind every pixel of ``forward``: the same samples (sampler -> coarse pass -> hierarchical
+        resample), the fine field's ``raw`` on them, and ``sunerf_hip.dem.dem_integral`` with the model's base offsets.
+        Forward only.
+
+        ``logt_nodes``: (K,) strictly increasing log T grid (default: the response table's, on which ``dem`` folded with a
+        channel's response row, times ``volumetric_constant * pixel_intensity_factor``, is ``forward``'s image of an optically
+        thin channel).  ``attenuation_wavelength``: attenuate with that channel's ``log_absortpion`` (then the identity holds
+        for that channel).  ``r_range``: radius mask in model units.
+        Returns ``dem`` (N, K), ``em``, ``logt_mean``, ``column`` (N,), ``logt_nodes`` (K,) and ``z_vals`` (N, S)."""
+        from sunerf_hip.dem import dem_integral
+        if self._hooks_replaced(DensityTemperatureRadiativeTransfer):
+            raise TypeError('render_dem needs the built-in density-temperature hooks and a NeRF_DT or field model')
+        nodes = self.dem_nodes(logt_nodes)
+        log_abs = self.attenuation_scalar(attenuation_wavelength)
+        tables = (self.response_logte, self.response_table)
+        z_vals = self.sampler.z_vals(rays_o, rays_d)
+        # the coarse weights = relu(inf0) / sum do not depend on the channel: one present channel keeps the pass cheap
+        wl = torch.full((z_vals.shape[0], 1), float(ops.AIA_WAVELENGTHS[2]), dtype=torch.float32, device=z_vals.device)
+        coarse = dt_pass(self.coarse_model, tables, self.pixel_intensity_factor, rays_o, rays_d, times, z_vals, wl,
+                         1.25 / self.Rs_per_ds, want_epilogues=False)
+        _, z_comb = self.sampler_hierarchical.resample(z_vals, coarse['weights'])
+        raw = self.fine_raw(rays_o, rays_d, times, z_comb)
+        model = self.fine_model
+        out = dem_integral(raw, z_comb, nodes, (model.base_log_density, model.base_log_temperature), log_abs, rays_o, rays_d,
+                           r_range)
+        out.update(logt_nodes=nodes, z_vals=z_comb)
+        return out
 
     def _render(self, model, query_points, rays_d, rays_o, z_vals, wavelengths):
         """density_temperature.py:148-190: ``model.forward`` at the query points -- inferences with the base offsets, the

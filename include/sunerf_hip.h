@@ -320,6 +320,37 @@ int sunerf_dt_integral_bwd_full(const float* raw, const float* z_vals, const flo
                                 float* g_raw, float* g_log_abs, float* g_vol_c, void* g_absmax, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Line-of-sight differential emission measure of the density / temperature model: the thermal structure
+ * behind a pixel of sunerf_dt_integral_fwd.  Restates that kernel's forward, density_temperature.py:237-265, with the
+ * temperature response folded out; the reference has no such product (a user bins per-sample profiles on the host).
+ *
+ *   raw (N,S,2), z_vals (N,S), base offsets: as sunerf_dt_integral_fwd.  rho = exp(relu(raw0 + base_log_density)),
+ *   logT = relu(raw1 + base_log_temperature), both sums in fp32 (density_temperature.py:237-241)
+ *   logt_nodes (K) fp32 device, strictly increasing (not checked), need not be uniform, 2 <= K <= 128
+ *   log_abs (1) device or NULL: kappa = relu(log_abs[0]), the absorption scalar of ONE channel; NULL or <= 0: optically thin
+ *   quadrature points j = 0..S-2 (the last sample is not one, exactly as in the render, :263-265):
+ *     q_j = trapezoid weight of z_j on the grid z_0..z_{S-2}  (S = 2: a single point of weight 0, everything 0)
+ *     t_j = exp(-A_{j+1}),  A = cumulative_trapezoid(rho kappa, z)                        :261-263 (the render's index shift)
+ *     m_j = 1 if r_in <= |rays_o + rays_d z_j| <= r_out else 0 (a NaN radius: 0).  r_in <= 0 with r_out = +inf: no mask, and
+ *           rays_o / rays_d may then be NULL
+ *     v_j = q_j t_j m_j rho_j^2
+ *   dem (N,K) or NULL: i = clamp(searchsorted(nodes, logT_j, right) - 1, 0, K-2), f = (logT_j - x_i) / (x_{i+1} - x_i),
+ *     dem[i] += v_j (1 - f), dem[i+1] += v_j f for the samples with x_0 <= logT_j <= x_{K-1}; the others deposit nothing
+ *     (Interp1D's extrap = 0, :245-256).  On the response table's grid:  image_w = vol_c pixel_intensity_factor sum_k dem_k R_w[k]
+ *   em (N) = sum_j v_j over all samples, inside the node grid or not
+ *   logt_mean (N) or NULL = sum_j v_j logT_j / em  (em = 0: NaN);  column (N) or NULL = sum_j q_j m_j rho_j, not attenuated
+ *   fp32 sums in a fixed order without atomics: reruns, and a ray alone or inside a batch, give the same bits.  n_samples has
+ *   no upper limit (nothing per sample lives in LDS).
+ * Checked in this order, before anything is queued: n_rays < 0, n_samples < 2 or n_nodes < 2: SUNERF_E_BADARG;
+ * n_nodes > 128: SUNERF_E_UNSUPPORTED; n_rays == 0: 0; a NULL raw / z_vals / logt_nodes / em, or NULL rays with a mask:
+ * SUNERF_E_BADARG.
+ * ---------------------------------------------------------------------------------------------------------- */
+int sunerf_dem_integral(const float* raw, const float* z_vals, const float* rays_o, const float* rays_d,
+                        const float* logt_nodes, int n_nodes, float base_log_density, float base_log_temperature,
+                        const float* log_abs, float r_in, float r_out, int64_t n_rays, int n_samples, float* dem, float* em,
+                        float* logt_mean, float* column, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * White-light Thomson scattering (total / polarised brightness, Howard & Tappin 2009).
  * Replaces ThompsonScattering.raw2outputs, sunerf/rendering/thompson.py:17-109, with the reference's defects resolved
  * (DESIGN.md 8b): the radius runs over (x, y, z) only (:43, :53 take the time coordinate in), the geometry is fp64 (the

@@ -1,0 +1,189 @@
+"""CPU-only checks of the line-of-sight DEM (no GPU): the identity that ties the DEM to the DT render, in float64
+on the project's own oracle; the new entry point is declared, bound and exported; its argument errors; the post-processing
+helpers against numpy; the loaders refuse a rendering without a temperature."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import dem_reference as ref
+import sunerf_oracle as orc
+from conftest import load_golden
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope='session')
+def lib():
+    import sunerf_hip
+    if not os.path.exists(sunerf_hip.LIB_PATH):
+        import subprocess
+        subprocess.check_call(['bash', os.path.join(ROOT, '2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh')])
+    return sunerf_hip.load()
+
+
+@pytest.fixture(scope='module')
+def tables():
+    """g6's (logT grid (101,), response x exposure time (7, 101)), float32.  All seven rows share one logT grid."""
+    g = load_golden('g6_dt_e2e')
+    lt, resp = g['aia_logte'], (g['aia_tresp'] * float(g['aia_exp_time'])).float()
+    assert bool((lt == lt[0]).all())
+    return lt, resp
+
+
+@pytest.mark.parametrize('absorb', ['none', 'thick'])
+@pytest.mark.parametrize('s', [3, 4, 33, 257])
+def test_dem_folded_with_the_response_is_the_dt_image(tables, s, absorb):
+    """image_w = vol_c pixel_factor sum_k DEM_k R_w[k] on the table's own grid: ``dem_reference`` against
+    ``sunerf_oracle.dt_integral`` in float64, 1e-12 relative, for every channel; optically thin and at optical depth ~3."""
+    lt, resp = tables
+    c = ref.make_case(24, s, lt[0].numpy(), seed=100 + s)
+    log_abs = ref.log_abs_of(c, absorb)
+    if absorb == 'thick':
+        kappa = max(log_abs, 0.0)
+        tau = torch.trapezoid(torch.exp(torch.relu(torch.from_numpy(c['inf'][..., 0]).double())) * kappa,
+                              torch.from_numpy(c['z']).double(), dim=-1).numpy()
+        assert 2.5 < tau.max() <= 3.0 + 1e-6, tau.max()
+    r = ref.dem_reference(c['inf'], c['z'], c['nodes'], log_abs)
+    la = {str(w): torch.tensor(0.0 if log_abs is None else log_abs, dtype=torch.float64) for w in orc.AIA_WAVELENGTHS}
+    wl = torch.tensor(orc.AIA_WAVELENGTHS, dtype=torch.float64).expand(24, 7)
+    vol_c, pixel = 0.7, 1e17
+    want = orc.dt_integral(torch.from_numpy(c['inf']).double(), la, torch.tensor(vol_c, dtype=torch.float64),
+                           torch.from_numpy(c['z']).double(), wl, lt.double(), resp.double(), pixel)['image'].numpy()
+    got = r['dem'] @ resp.double().numpy().T * vol_c * pixel
+    assert want.shape == got.shape == (24, 7)
+    if s > 3:
+        assert (want > 0).any()
+    err = np.abs(got - want)
+    assert (err <= 1e-12 * np.abs(want)).all(), (err / np.maximum(np.abs(want), 1e-300)).max()
+    # rays 2, 7, ...: every log T outside the table
+    assert (r['dem'][2::5] == 0).all() and (want[2::5] == 0).all()
+    if s > 3:
+        assert (r['em'][2::5] > 0).all()
+
+
+def test_reference_conserves_the_emission_measure(tables):
+    """Hat weights add up to 1: with every sample inside the grid sum_k dem = em; with a mask the masked samples count nowhere."""
+    lt, _ = tables
+    c = ref.make_case(9, 40, lt[0].numpy(), seed=5, all_inside=True)
+    r = ref.dem_reference(c['inf'], c['z'], c['nodes'], ref.log_abs_of(c, 'thick'))
+    assert np.allclose(r['dem'].sum(1), r['em'], rtol=1e-13, atol=0)
+    lo, hi = c['nodes'][0], c['nodes'][-1]
+    assert (r['logt_mean'] > lo).all() and (r['logt_mean'] < hi).all()
+    m = ref.add_mask(c)
+    rm = ref.dem_reference(m['inf'], m['z'], m['nodes'], None, m['o'], m['d'], m['r_range'])
+    assert rm['em'][1] == 0 and np.isnan(rm['logt_mean'][1]) and rm['column'][1] == 0 and (rm['dem'][1] == 0).all()
+    assert rm['em'][3] == 0 and np.isnan(rm['logt_mean'][3])
+    full = ref.dem_reference(m['inf'], m['z'], m['nodes'], None)
+    assert (rm['em'][[0, 2, 4, 5]] <= full['em'][[0, 2, 4, 5]]).all() and (rm['em'] < full['em']).any()
+    # S = 2: one quadrature point of weight 0
+    z2 = ref.dem_reference(c['inf'][:, :2], c['z'][:, :2], c['nodes'])
+    assert (z2['dem'] == 0).all() and (z2['em'] == 0).all() and np.isnan(z2['logt_mean']).all() and (z2['column'] == 0).all()
+
+
+def test_entry_point_is_declared_bound_and_exported(lib):
+    import sunerf_hip
+    header = open(os.path.join(ROOT, 'include', 'sunerf_hip.h')).read()
+    declared = set(re.findall(r'\b(sunerf_\w+)\s*\(', header))
+    assert 'sunerf_dem_integral' in declared
+    assert 'sunerf_dem_integral' in sunerf_hip.EXPORTED_SYMBOLS
+    assert getattr(lib, 'sunerf_dem_integral') is not None
+    assert 'density_temperature.py:237-265' in header
+    assert lib.sunerf_abi_version() == 9
+
+
+def test_argument_errors_without_gpu(lib):
+    """include/sunerf_hip.h: sizes first (n_samples < 2 / n_nodes < 2: -1, n_nodes > 128: -2), then the empty batch (0), then
+    null pointers (-1); all before anything touches a device."""
+    inf = float('inf')
+
+    def call(n_nodes=101, n_rays=4, n_samples=8, r_in=0.0, r_out=inf):
+        return lib.sunerf_dem_integral(None, None, None, None, None, n_nodes, 10.0, 5.0, None, r_in, r_out, n_rays, n_samples,
+                                       None, None, None, None, None)
+    assert call() == -1                                   # null pointers
+    assert call(r_in=1.0, r_out=2.0) == -1
+    assert call(n_samples=1) == -1 and call(n_samples=1, n_rays=0) == -1
+    assert call(n_nodes=1) == -1 and call(n_nodes=0) == -1
+    assert call(n_nodes=129) == -2 and call(n_nodes=129, n_rays=0) == -2
+    assert call(n_nodes=128) == -1 and call(n_nodes=2) == -1          # supported sizes: the null pointers are what is wrong
+    assert call(n_rays=0) == 0 and call(n_rays=0, n_samples=2, n_nodes=2) == 0
+    assert call(n_rays=-1) == -1
+
+
+def test_python_op_refuses_cpu_tensors_and_bad_arguments():
+    from sunerf_hip import SunerfHipError
+    from sunerf_hip.dem import dem_integral
+    raw, z, nodes = torch.zeros(4, 8, 2), torch.ones(4, 8), torch.linspace(5, 7, 11)
+    with pytest.raises(SunerfHipError):
+        dem_integral(raw, z, nodes)
+    with pytest.raises(ValueError, match='unknown outputs'):
+        dem_integral(raw, z, nodes, want=('dem', 'temperature'))
+    with pytest.raises(ValueError, match='1-d'):
+        dem_integral(raw, z, nodes[None])
+
+
+def test_per_dex_and_fold_agree_with_numpy():
+    from sunerf_hip.dem import fold, node_widths, per_dex
+    rng = np.random.default_rng(3)
+    nodes = np.sort(rng.random(17)) * 3 + 5
+    dem = rng.random((5, 6, 17))
+    rows = rng.random((7, 17))
+    w = np.empty(17)
+    w[1:-1] = (nodes[2:] - nodes[:-2]) / 2
+    w[0], w[-1] = (nodes[1] - nodes[0]) / 2, (nodes[-1] - nodes[-2]) / 2
+    assert np.allclose(node_widths(torch.from_numpy(nodes)).numpy(), w, rtol=1e-14, atol=0)
+    assert abs(w.sum() - (nodes[-1] - nodes[0])) < 1e-14
+    assert np.allclose(per_dex(torch.from_numpy(dem), torch.from_numpy(nodes)).numpy(), dem / w, rtol=1e-14, atol=0)
+    assert np.allclose(fold(torch.from_numpy(dem), torch.from_numpy(rows)).numpy(), dem @ rows.T, rtol=1e-13, atol=0)
+    assert np.allclose(fold(torch.from_numpy(dem), torch.from_numpy(rows[2])).numpy(), dem @ rows[2], rtol=1e-13, atol=0)
+    # float32 DEM with float64 nodes / rows: the DEM's dtype is kept
+    assert per_dex(torch.from_numpy(dem).float(), torch.from_numpy(nodes)).dtype == torch.float32
+    with pytest.raises(ValueError):
+        fold(torch.from_numpy(dem), torch.from_numpy(rows[:, :16]))
+    with pytest.raises(ValueError):
+        node_widths(torch.tensor([5.0]))
+
+
+def test_loaders_refuse_a_rendering_without_a_temperature():
+    import datetime
+    from sunerf.evaluation.loader import ModelLoader, SuNeRFLoader
+    from sunerf.rendering.emission import EmissionRadiativeTransfer
+    from sunerf_hip.dem import render_dem_columns, render_dem_frame
+    mod = EmissionRadiativeTransfer(Rs_per_ds=1.0, sampling_config={'type': 'stratified', 'n_samples': 8, 'perturb': False},
+                                    hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 8},
+                                    model_config={'d_filter': 64})
+    loader = ModelLoader(rendering=mod, model=mod.fine_model, device='cpu',
+                         ref_map={'shape': (4, 4), 'cdelt': (600., 600.), 'meta': {'t_obs': '2022-01-01T00:00:00.000'}})
+    with pytest.raises(TypeError, match='density-temperature'):
+        loader.render_dem_image(0.1, 0.2, 0.5)
+    with pytest.raises(TypeError, match='density-temperature'):
+        loader.render_dem_map(0.5, shape=(3, 5))
+    snf = SuNeRFLoader.__new__(SuNeRFLoader)
+    snf.rendering, snf.device, snf.seconds_per_dt, snf.ref_time = mod, torch.device('cpu'), 86400., datetime.datetime(2022, 1, 1)
+    with pytest.raises(TypeError, match='density-temperature'):
+        snf.render_dem_image(0.1, 0.2, datetime.datetime(2022, 1, 2))
+    with pytest.raises(TypeError, match='density-temperature'):
+        snf.render_dem_map(datetime.datetime(2022, 1, 2), shape=(3, 5))
+    axis = torch.zeros(4, dtype=torch.float64)
+    with pytest.raises(TypeError, match='density-temperature'):
+        render_dem_frame(mod, axis, axis, torch.eye(4), 0.5)
+    with pytest.raises(TypeError, match='density-temperature'):
+        render_dem_columns(mod, axis, axis, 0.5)
+
+
+def test_render_dem_refuses_an_unknown_channel(tables):
+    from sunerf.model.model import NeRF_DT
+    from sunerf.rendering.density_temperature import DensityTemperatureRadiativeTransfer
+    g = load_golden('g6_dt_e2e')
+    mod = DensityTemperatureRadiativeTransfer(
+        Rs_per_ds=1.0, sampling_config={'type': 'stratified', 'n_samples': 8, 'perturb': False},
+        hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 8}, model_config={'d_filter': 64}, model=NeRF_DT,
+        device=torch.device('cpu'), pixel_intensity_factor=1.0, response_table=(g['aia_logte'].numpy(), g['aia_tresp'].numpy()))
+    rays = torch.zeros(4, 3)
+    for bad in (1600, 171.5, 'hot'):
+        with pytest.raises(ValueError, match='not a channel'):
+            mod.render_dem(rays, rays, torch.zeros(4, 1), attenuation_wavelength=bad)
+    assert mod.attenuation_scalar(None) is None and mod.attenuation_scalar(193).shape == (1,)
+    assert torch.equal(mod.dem_nodes(), mod.response_logte[0]) and mod.dem_nodes([5.0, 6.0, 7.0]).dtype == torch.float32
