@@ -1,0 +1,184 @@
+"""A field that is a plain array of values on a grid: rendered through the same line-of-sight
+integrals as the MLP and **fitted** through them -- classical rotational tomography as the non-ML baseline -- or baked from a
+trained model (``sample_volume`` -> :meth:`GridField.from_volume`) so that a frame skips the network.
+
+The reference has two grid interpolators, both forward-only and on the CPU: ``MHDModel``'s scipy
+``RegularGridInterpolator`` (sunerf/model/mhd_model.py:45-75) and the cube of ``evaluation/stash/voxel_volume.py:30-56``,
+which it only draws.  ``GridField`` is their device form for any grid of :mod:`sunerf_hip.volume` with the adjoint
+(``csrc/grid_field.hip``), ``GridFieldDT`` carries the density-temperature head exactly as ``MHDModel`` does.
+"""
+import math
+
+import numpy as np
+import torch
+from torch import nn
+
+from sunerf_hip import grid_field as _gf
+from sunerf_hip import ops
+
+EMPTY = -50.0                   # exp(-50) ~ 2e-22: "nothing here" for a channel that is exponentiated
+
+
+def default_fill(d_output: int):
+    """What a sample outside the grid answers when no ``fill`` is given: ``(-50, 0, 0, 0)[:d_output]``.
+
+    - emission (``d_output=2``: ln emission, absorption logit): ``exp(raw0) ~ 0``, ``relu(raw1) = 0`` -- empty space;
+    - white light (``d_output=1``: ln rho): ``exp(-50) ~ 0`` electrons;
+    - density / temperature: :class:`GridFieldDT` has its own default, ``MHDModel``'s."""
+    return (EMPTY, 0.0, 0.0, 0.0)[:d_output]
+
+
+class GridField(nn.Module):
+    """``values (n0, n1, n2, C)`` on the nodes of ``grid`` (a ``CartesianGrid`` or ``SphericalGrid`` of
+    :mod:`sunerf_hip.volume`; C order over its axes, the layout of ``sample_volume``'s ``inferences``), interpolated
+    trilinearly at points given in model units (``X = p * Rs_per_ds`` solar radii).  The field is static: times are ignored.
+
+    ``d_output``: channels per node, 1 to 4; ``d_input`` is accepted (the renderings force both into ``model_config``) and
+    must be 3 or 4.  ``init``: ``None`` (zeros), a number, ``d_output`` numbers, or a full array.  ``fill (C,)``: the answer
+    outside the grid (:func:`default_fill`).  ``periodic_lon``: how a ``SphericalGrid``'s longitude axis is read
+    (:func:`sunerf_hip.grid_field.longitude_mode`).  ``trainable=False`` freezes ``values``.
+
+    A model of a rendering: ``EmissionRadiativeTransfer(model=GridField, model_config={'grid': grid, ...})``; the rendering's
+    ``Rs_per_ds`` goes into ``model_config`` too."""
+
+    def __init__(self, grid, d_output=2, d_input=4, Rs_per_ds=1.0, init=None, fill=None, periodic_lon=None, trainable=True):
+        super().__init__()
+        _gf.check_grid(grid)
+        if int(d_output) != d_output or not 1 <= d_output <= _gf.MAX_CHANNELS:
+            raise ValueError(f'a grid field holds 1 to {_gf.MAX_CHANNELS} channels per node, got d_output={d_output!r}')
+        if d_input not in (3, 4):
+            raise ValueError(f'a grid field takes points (x, y, z[, t]): d_input must be 3 or 4, got {d_input!r}')
+        Rs_per_ds = float(Rs_per_ds)
+        if not (math.isfinite(Rs_per_ds) and Rs_per_ds > 0):
+            raise ValueError(f'Rs_per_ds must be finite and > 0, got {Rs_per_ds}')
+        self.grid, self.d_output, self.d_input, self.Rs_per_ds = grid, int(d_output), int(d_input), Rs_per_ds
+        self.lon_mode = _gf.longitude_mode(grid, periodic_lon)
+        shape = (*grid._shape3, self.d_output)
+        if init is None:
+            values = torch.zeros(shape, dtype=torch.float32)
+        else:
+            init = torch.as_tensor(np.asarray(init.detach().cpu() if isinstance(init, torch.Tensor) else init),
+                                   dtype=torch.float32)
+            if init.dim() <= 1 and init.numel() in (1, self.d_output):
+                values = init.reshape(-1).expand(shape).clone()
+            elif tuple(init.shape) == shape:
+                values = init.clone()
+            else:
+                raise ValueError(f'init has shape {tuple(init.shape)}; expected a number, {self.d_output} numbers or {shape}')
+        self.values = nn.Parameter(values.contiguous(), requires_grad=bool(trainable))
+        fill = self._default_fill() if fill is None else fill
+        fill = torch.as_tensor(np.asarray(fill, dtype=np.float32)).reshape(-1)
+        if fill.shape[0] != self.d_output:
+            raise ValueError(f'fill has {fill.shape[0]} values for {self.d_output} channels')
+        self.register_buffer('fill', fill)
+        self._descs = {}
+
+    def _default_fill(self):
+        return default_fill(self.d_output)
+
+    # ---- construction from a volume -----------------------------------------------------------------------------------------
+    @classmethod
+    def from_volume(cls, volume, trainable=False, **kwargs):
+        """The field whose values are ``volume['inferences']``, bit for bit, on ``volume['grid']`` with ``volume['Rs_per_ds']``:
+        the dict ``sample_volume`` / ``load_volume`` return (tensors or numpy arrays; one time)."""
+        grid, inf = volume['grid'], volume['inferences']
+        _gf.check_grid(grid)
+        device = inf.device if isinstance(inf, torch.Tensor) else torch.device('cpu')
+        inf = torch.as_tensor(np.asarray(inf.detach().cpu() if isinstance(inf, torch.Tensor) else inf))
+        if inf.dim() != 4 or tuple(inf.shape[:3]) != tuple(grid._shape3):
+            raise ValueError(f'from_volume: inferences of shape {tuple(inf.shape)} do not fit the grid {tuple(grid._shape3)} '
+                             '(one time, channels last)')
+        if inf.dtype != torch.float32:
+            raise ValueError(f'from_volume: inferences must be float32, got {inf.dtype}')
+        kwargs.setdefault('Rs_per_ds', volume.get('Rs_per_ds', 1.0))
+        field = cls(grid, d_output=inf.shape[-1], init=inf, trainable=trainable, **kwargs)
+        return field.to(device)
+
+    @classmethod
+    def bake(cls, field_or_rendering, grid, time, trainable=False, fill=None, periodic_lon=None, **sample_volume_kwargs):
+        """``sample_volume(field_or_rendering, grid, time, ...)`` turned into a field: a trained model's answer on ``grid`` at
+        the normalised ``time``, from which frames render without the network."""
+        from sunerf_hip.volume import sample_volume
+        if isinstance(time, (list, tuple, np.ndarray)) or (isinstance(time, torch.Tensor) and time.dim() > 0):
+            raise ValueError('bake: one time per field (the grid has no time axis)')
+        volume = sample_volume(field_or_rendering, grid, time, **sample_volume_kwargs)
+        return cls.from_volume(volume, trainable=trainable, fill=fill, periodic_lon=periodic_lon)
+
+    # ---- evaluation ---------------------------------------------------------------------------------------------------------
+    def descriptor(self, device=None) -> '_gf.GridDescriptor':
+        """The kernels' descriptor of this field on ``device`` (default: where ``values`` are), rebuilt when ``fill`` changed."""
+        device = self.values.device if device is None else torch.device(device)
+        key = (self.fill.data_ptr(), self.fill._version)
+        cached = self._descs.get(str(device))
+        if cached is None or cached[0] != key:
+            desc = _gf.GridDescriptor(self.grid, self.d_output, self.Rs_per_ds, self.fill.detach().cpu().tolist(), self.lon_mode,
+                                      device)
+            cached = self._descs[str(device)] = (key, desc)
+        return cached[1]
+
+    def field_parameters(self):
+        """The parameters :meth:`field_on_rays` carries gradients for."""
+        return [self.values]
+
+    def field_on_rays(self, rays_o, rays_d, z_vals):
+        """``raw (N, S, C)`` at the samples ``o + d z`` (``sunerf_grid_field_fwd``); differentiable w.r.t. ``values``."""
+        return _gf.field_on_rays(self.descriptor(), self.values, rays_o, rays_d, z_vals)
+
+    def inferences(self, query_points):
+        points = query_points.reshape(-1, query_points.shape[-1])
+        return _gf.field_on_points(self.descriptor(), self.values, points)
+
+    def forward(self, query_points):
+        """``(M, 3 | 4)`` query points -> ``{'inferences': (M, C)}``; a time column is ignored."""
+        return {'inferences': self.inferences(query_points)}
+
+    # ---- prior --------------------------------------------------------------------------------------------------------------
+    def smoothness(self):
+        """A discrete ``|grad v|^2``: per axis the mean over nodes and channels of ``((v[i + 1] - v[i]) / (a[i + 1] - a[i]))^2``
+        in the axis' own coordinate (solar radii, radians), then the mean over the three axes.  On a periodic longitude the
+        differences across the seam count too: last node -> first node + 2 pi on an open axis; on a closed axis the two seam
+        nodes are one place, and their difference is taken at the axis' mean step.  Plain torch ops, differentiable."""
+        v = self.values
+        total = 0.0
+        for k, axis in enumerate(self.grid.axes):
+            step = (axis[1:] - axis[:-1]).to(device=v.device, dtype=v.dtype)
+            shape = [1, 1, 1, 1]
+            shape[k] = -1
+            d = (v.narrow(k, 1, v.shape[k] - 1) - v.narrow(k, 0, v.shape[k] - 1)) / step.view(shape)
+            if k == 1 and self.lon_mode != _gf.LON_PATCH:
+                if self.lon_mode == _gf.LON_OPEN:
+                    seam = (axis[0] + _gf.TWO_PI - axis[-1]).item()
+                else:
+                    seam = ((axis[-1] - axis[0]) / (axis.shape[0] - 1)).item()
+                d = torch.cat([d, (v[:, :1] - v[:, -1:]) / seam], 1)
+            total = total + d.pow(2).mean()
+        return total / 3.0
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state['_descs'] = {}
+        return state
+
+
+class GridFieldDT(GridField):
+    """A grid of ``(ln rho, log10 T)`` with the density-temperature head exactly as ``MHDModel`` carries it (mhd_model.py:11-24):
+    the ``log_absortpion`` scalars over the AIA channels, ``volumetric_constant`` and zero base offsets, so that
+    ``DensityTemperatureRadiativeTransfer(model=GridFieldDT)`` renders and fits it.  Default ``fill``: ``(ln 1e-10, log10
+    1e-10)``, ``MHDModel``'s ``FILL_VALUE`` outside its cube."""
+
+    def __init__(self, grid, d_output=2, **kwargs):
+        if d_output != 2:
+            raise ValueError(f'a density-temperature grid holds (ln rho, log10 T): d_output must be 2, got {d_output!r}')
+        super().__init__(grid, d_output=2, **kwargs)
+        self.log_absortpion = nn.ParameterDict([[str(w), torch.tensor(v, dtype=torch.float32)] for w, v in
+                                                zip(ops.AIA_WAVELENGTHS, (20.4, 20.2, 20.0, 19.8, 19.6, 19.4, 19.2))])
+        self.volumetric_constant = nn.Parameter(torch.tensor(1.0, dtype=torch.float32, requires_grad=True))
+        self.base_log_density = 0.0
+        self.base_log_temperature = 0.0
+
+    def _default_fill(self):
+        return (math.log(1e-10), -10.0)
+
+    def forward(self, query_points):
+        """``{'inferences': (M, 2), 'log_abs', 'vol_c'}``, as ``NeRF_DT`` / ``MHDModel`` answer."""
+        return {'inferences': self.inferences(query_points), 'log_abs': self.log_absortpion, 'vol_c': self.volumetric_constant}

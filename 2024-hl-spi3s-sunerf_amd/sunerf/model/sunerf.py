@@ -11,6 +11,7 @@ import torch
 from torch import nn
 from torch.optim.lr_scheduler import ExponentialLR
 
+from sunerf.model.model import NeRF
 from sunerf.rendering.base_tracing import SuNeRFRendering
 from sunerf.rendering.emission import EmissionRadiativeTransfer
 from sunerf.rendering.density_temperature import DensityTemperatureRadiativeTransfer
@@ -65,6 +66,15 @@ class BaseSuNeRFModule(LightningModule):
         if gradient_clip_val and gradient_clip_algorithm == 'value':
             raise NotImplementedError("gradient_clip_algorithm='value' is not supported by the fused optimiser step: use 'norm'")
         optimizer.max_norm = float(gradient_clip_val) if gradient_clip_val else None
+
+    def _with_smoothness(self, loss):
+        """``loss + lambda_smoothness (coarse.smoothness() + fine.smoothness())`` for field models that have the prior
+        (``GridField``: tomography's regulariser); the loss itself with the default ``lambda_smoothness = 0``."""
+        lam = getattr(self, 'lambda_smoothness', 0.0)
+        models = (self.rendering.coarse_model, self.rendering.fine_model)
+        if not lam > 0 or not all(hasattr(m, 'smoothness') for m in models):
+            return loss
+        return loss + lam * (models[0].smoothness() + models[1].smoothness())
 
     def _step_nonfinite_count(self):
         """This step's non-finite output count (device scalar) for ``ClipAdam.step(closure)``."""
@@ -177,12 +187,14 @@ class EmissionSuNeRFModule(BaseSuNeRFModule):
     """sunerf.py:77-149."""
 
     def __init__(self, Rs_per_ds, seconds_per_dt, image_scaling_config, lambda_image=1.0, lambda_regularization=1.0,
-                 sampling_config=None, hierarchical_sampling_config=None, model_config=None, **kwargs):
+                 sampling_config=None, hierarchical_sampling_config=None, model_config=None, model=NeRF,
+                 lambda_smoothness=0.0, **kwargs):
         self.lambda_image = lambda_image
         self.lambda_regularization = lambda_regularization
+        self.lambda_smoothness = lambda_smoothness
         rendering = EmissionRadiativeTransfer(Rs_per_ds=Rs_per_ds, sampling_config=sampling_config,
                                               hierarchical_sampling_config=hierarchical_sampling_config,
-                                              model_config=model_config)
+                                              model_config=model_config, model=model)
         super().__init__(Rs_per_ds=Rs_per_ds, seconds_per_dt=seconds_per_dt, rendering=rendering, **kwargs)
         self.image_scaling = ImageAsinhScaling(**image_scaling_config)
         self.mse_loss = nn.MSELoss()
@@ -206,7 +218,7 @@ class EmissionSuNeRFModule(BaseSuNeRFModule):
                                     outputs['regularization'], self.lambda_image, self.lambda_regularization,
                                     asinh_scaling=self._asinh_constants(),
                                     finite_check=_other_outputs(outputs))
-        return self._finish_step(loss, stats)
+        return self._finish_step(self._with_smoothness(loss), stats)
 
     def _validation_images(self, fine, target):
         """TestImageCallback's ImageNormalize(vmin=0, vmax=1, stretch=AsinhStretch(0.005), clip=True) (callback.py:35, 46-48;
@@ -236,9 +248,10 @@ class DensityTemperatureSuNeRFModule(BaseSuNeRFModule):
 
     def __init__(self, Rs_per_ds, seconds_per_dt, image_scaling_config, model, loss=nn.MSELoss(), lambda_image=1.0,
                  lambda_regularization=1.0, sampling_config=None, hierarchical_sampling_config=None,
-                 pixel_intensity_factor=1e17, model_config=None, **kwargs):
+                 pixel_intensity_factor=1e17, model_config=None, lambda_smoothness=0.0, **kwargs):
         self.lambda_image = lambda_image
         self.lambda_regularization = lambda_regularization
+        self.lambda_smoothness = lambda_smoothness
         rendering_kwargs = {k: kwargs.pop(k) for k in ('response_table', 'response_path') if k in kwargs}
         rendering = DensityTemperatureRadiativeTransfer(Rs_per_ds=Rs_per_ds, sampling_config=sampling_config,
                                                         hierarchical_sampling_config=hierarchical_sampling_config,
@@ -258,7 +271,7 @@ class DensityTemperatureSuNeRFModule(BaseSuNeRFModule):
         loss, stats = training_loss(outputs['coarse_image'], outputs['fine_image'], target_image,
                                     outputs['regularization'], self.lambda_image, self.lambda_regularization,
                                     asinh_scaling=None, finite_check=_other_outputs(outputs))
-        return self._finish_step(loss, stats)
+        return self._finish_step(self._with_smoothness(loss), stats)
 
     def _training_step_generic_loss(self, outputs, target_image):
         """A user-supplied loss module other than nn.MSELoss (sunerf.py:159 takes any callable): torch ops."""

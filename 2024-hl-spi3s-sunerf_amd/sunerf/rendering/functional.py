@@ -196,8 +196,32 @@ class _EmissionPass(torch.autograd.Function):
             accumulate=accumulate, times=times))
 
 
+def _field_emission_pass(model, rays_o, rays_d, times, z_vals, reg_radius, want_epilogues, want_raw=False):
+    """:func:`emission_pass` for a field module with ``field_on_rays`` (``GridField``: no MLP): the field through its own node,
+    the integral of emission.py:14-54 on its ``raw`` (``_EmissionIntegral``) and the three epilogues in torch, as
+    ``SuNeRFRendering.forward`` forms them (base_tracing.py:99-110).  The fused pass' keys; ``image`` and ``regularization``
+    carry the gradient to whatever parameters ``field_on_rays`` is differentiable in, the rest is detached like the fused
+    pass' non-differentiable outputs."""
+    raw = _field_raw(model, rays_o, rays_d, z_vals, times)
+    if raw.shape[-1] != 2:
+        raise ValueError(f'an emission field answers (ln emission, absorption logit) per sample, got {raw.shape[-1]} channels')
+    image, weights, absorption = _EmissionIntegral.apply(raw, z_vals, rays_d)
+    out = {'image': image, 'weights': weights.detach(), 'absorption': absorption.detach()}
+    if want_raw:
+        out['raw'] = raw.detach()
+    if want_epilogues:
+        points = rays_o[:, None, :] + rays_d[:, None, :] * z_vals[..., None]
+        distance = points.pow(2).sum(-1).pow(0.5)
+        out['height_map'] = (out['weights'] * distance).sum(-1)
+        out['absorption_map'] = (1 - out['absorption']).sum(-1)
+        out['regularization'] = torch.relu(distance - reg_radius) * (1 - absorption)
+    return out
+
+
 def emission_pass(model, rays_o, rays_d, times, z_vals, reg_radius, want_epilogues):
     """Dict of one pass' outputs; goes through autograd when gradients are enabled and the model is trainable."""
+    if hasattr(model, 'field_on_rays'):
+        return _field_emission_pass(model, rays_o, rays_d, times, z_vals, reg_radius, want_epilogues)
     params = _mlp_params(model)
     if _differentiable(params):
         outs = _EmissionPass.apply(model, rays_o, rays_d, times, z_vals, reg_radius, want_epilogues, *params)
@@ -398,7 +422,8 @@ def dt_pass(model, tables, pixel_factor, rays_o, rays_d, times, z_vals, waveleng
         # analytic field (SimpleStar) or simulation cube (MHDModel) instead of an MLP: same integral (stellar_model.py,
         # mhd_model.py, image_render.py:244-269)
         sp = star_parameters(model) if hasattr(model, 'stellar_parameters') else []
-        if _differentiable(la + sp + [model.volumetric_constant]):
+        fp = list(model.field_parameters()) if hasattr(model, 'field_parameters') else []     # a GridFieldDT's values
+        if _differentiable(la + sp + fp + [model.volumetric_constant]):
             # a star's field through its own node, on the device-side parameters even when they are frozen
             raw = star_field(model, rays_o, rays_d, z_vals) if sp else _field_raw(model, rays_o, rays_d, z_vals, times)
             outs = _FieldDtPass.apply(model, tables, pixel_factor, raw, rays_o, rays_d, z_vals, wavelengths, reg_radius,

@@ -157,6 +157,12 @@ _SIGNATURES = {
     'sunerf_volume_metrics_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64]),
     'sunerf_volume_metrics': (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void,
                                               c_void, c_void, ctypes.c_size_t, c_void]),
+    'sunerf_grid_field_desc_bytes': (ctypes.c_size_t, []),
+    'sunerf_grid_field_fwd': (ctypes.c_int, [c_void, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, c_f32p,
+                                              ctypes.c_int, c_f32p, c_void, c_f32p, c_void]),
+    'sunerf_grid_field_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    'sunerf_grid_field_bwd': (ctypes.c_int, [c_void, c_f32p, c_void, c_f32p, c_void, c_void, ctypes.c_int64, c_void,
+                                              ctypes.c_size_t, c_f32p, ctypes.c_int, c_void]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

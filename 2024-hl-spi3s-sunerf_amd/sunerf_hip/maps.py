@@ -137,8 +137,11 @@ def _tile(rendering, rays_o, rays_d, times, z, wl, kind: str, profiles: bool) ->
     model = rendering.fine_model
     scale = float(rendering.Rs_per_ds)
     if kind == 'emission':
-        out = ops.emission_render_fwd(model.packed(), rays_o, rays_d, times, z, 1.2 / rendering.Rs_per_ds,
-                                      want_raw=True, want_epilogues=True)
+        if hasattr(model, 'field_on_rays'):                    # a grid field: its own gather, then the same integral
+            out = F._field_emission_pass(model, rays_o, rays_d, times, z, 1.2 / rendering.Rs_per_ds, True, want_raw=True)
+        else:
+            out = ops.emission_render_fwd(model.packed(), rays_o, rays_d, times, z, 1.2 / rendering.Rs_per_ds,
+                                          want_raw=True, want_epilogues=True)
         res = {'image': out['image'], 'height_map': out['height_map'] * scale, 'absorption_map': out['absorption_map']}
         res.update(column_stats(out['raw'], z[0], rays_d, scale, profiles))
         return res

@@ -588,6 +588,66 @@ int sunerf_volume_metrics(const float* a, const float* b, int n0, int n1, int n2
                           const double* w2, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Voxel-grid field: values [n0][n1][n2][C] fp32 on the nodes of a grid (C order over the grid's axes,
+ * the layout of sample_volume's `inferences`), 1 <= C <= 4, gathered trilinearly and fitted through the adjoint.
+ * Generalises the interpolators of MHDModel, sunerf/model/mhd_model.py:45-75 (RegularGridInterpolator(method='linear',
+ * bounds_error=False, fill_value=...)), to the grids of the volumes -- the cube of
+ * sunerf/evaluation/stash/voxel_volume.py:30-44 included -- and adds the gradient w.r.t. the values.
+ *
+ * One sample at the point p [model units, fp32]; X = p * Rs_per_ds [solar radii] and everything up to the weights in fp64:
+ *   SUNERF_GRID_AFFINE   : u = inverse (X - origin), u_m = (inverse[m][0] dx + inverse[m][1] dy) + inverse[m][2] dz;
+ *                          `inverse` is the inverse of the node map X = origin + u_0 e_0 + u_1 e_1 + u_2 e_2
+ *   SUNERF_GRID_SPHERICAL: the inverse of sunerf_grid_points' X = r (-cos b sin l, cos b cos l, -sin b):
+ *                          r = sqrt((X^2 + Y^2) + Z^2), u = (lat, lon, r) = (asin(clamp(-Z / r)), atan2(-X, Y), r), the
+ *                          longitude then reduced into [lon[0], lon[0] + 2 pi)
+ *   cell per axis : i = searchsorted(axis, u, 'left') - 1 clipped to [0, n - 2] (axes strictly increasing, n >= 2),
+ *                   t = (u - axis[i]) / (axis[i + 1] - axis[i]); the weights (float)(1 - t), (float)t; interpolation in fp32
+ *   inside        : lo[k] <= u_k <= hi[k] (the axis ends) on every axis that is not a periodic longitude.  Outside, or with
+ *                   a NaN coordinate (missed rays of SphericalSampler): raw = fill[c], no gradient
+ *   lon_mode      : SUNERF_GRID_LON_PATCH  a limited span: outside it the fill
+ *                   SUNERF_GRID_LON_CLOSED periodic, the axis spans 2 pi and its last node repeats the first
+ *                   SUNERF_GRID_LON_OPEN   periodic, endpoint left out: one more cell joins the last node to the first + 2 pi
+ *
+ * sunerf_grid_field_fwd: ray mode (points == NULL): the samples o + d z (multiply, then add, in fp32) of rays_o / rays_d
+ *   [N,3], z_vals [N,S] -> raw [N,S,C]; points mode: points [M, point_stride] (stride 3 or 4; a time column is ignored: the
+ *   field is static), n_rays = M, n_samples = 1 -> raw [M,C].  cells [N S] int32 and weights [N S][3][2] fp32 (both or
+ *   neither): the flattened cell id of every sample (outside: the number of cells) and its weights, for the backward.
+ * sunerf_grid_field_bwd: g_values[node][c] (+)= sum over samples of w(sample, node) g_raw[sample][c], the adjoint.
+ *   perm [n_total] int64: a stable ascending sort of `cells`; seg_start [number of cells + 1] int64: the first sorted
+ *   position of every cell id (searchsorted of the sorted ids).  No floating-point atomics: per node the segments of its
+ *   adjacent cells are added in a fixed order, segments longer than 64 samples through per-wave partial sums in `workspace`
+ *   (sunerf_grid_field_bwd_workspace_bytes): reruns are bit-identical.  accumulate != 0 adds onto g_values.
+ * Sizes and the descriptor are checked first (n[k] < 2, C < 1, a bad kind / lon_mode, Rs_per_ds <= 0: -1; C > 4 or 2^31
+ * cells: -2), then the empty batch (0), then null pointers (-1) and the workspace (-3).  `grid` is a HOST pointer; its
+ * axis pointers are device arrays (fp64).
+ * ---------------------------------------------------------------------------------------------------------- */
+#define SUNERF_GRID_FIELD_MAX_CHANNELS 4
+#define SUNERF_GRID_LON_PATCH  0
+#define SUNERF_GRID_LON_CLOSED 1
+#define SUNERF_GRID_LON_OPEN   2
+typedef struct SunerfGridFieldDesc {
+  const double* axis[3];    /* device, strictly increasing, n[k] nodes */
+  int n[3];
+  int n_channels;
+  int kind;                 /* SUNERF_GRID_AFFINE / SUNERF_GRID_SPHERICAL */
+  int lon_mode;             /* SUNERF_GRID_LON_*; PATCH for an affine grid */
+  double lo[3];             /* axis[k][0] */
+  double hi[3];             /* axis[k][n[k] - 1] */
+  double inverse[3][3];     /* affine grids */
+  double origin[3];
+  double Rs_per_ds;
+  float fill[4];
+} SunerfGridFieldDesc;
+size_t sunerf_grid_field_desc_bytes(void);
+int sunerf_grid_field_fwd(const SunerfGridFieldDesc* grid, const float* values, const float* rays_o, const float* rays_d,
+                          const float* z_vals, int64_t n_rays, int n_samples, const float* points, int point_stride,
+                          float* raw, int* cells, float* weights, void* stream);
+size_t sunerf_grid_field_bwd_workspace_bytes(int64_t n_total, int n_channels);
+int sunerf_grid_field_bwd(const SunerfGridFieldDesc* grid, const float* g_raw, const int* cells, const float* weights,
+                          const int64_t* perm, const int64_t* seg_start, int64_t n_total, void* workspace,
+                          size_t workspace_bytes, float* g_values, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Output side of the path: training loss and optimiser step without host synchronisation.
  *
  * sunerf_training_loss replaces EmissionSuNeRFModule.training_step's loss section, sunerf/model/sunerf.py:105-125

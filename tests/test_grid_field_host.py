@@ -1,0 +1,330 @@
+"""CPU-only checks of the voxel-grid field (no GPU): the float64 restatement the GPU tests check the kernels
+against (vs scipy, the spherical inverse map, the three longitude conventions), the Python side (refusals, from_volume,
+smoothness, pickling, module defaults) and the new entry points (declared, bound, exported; argument errors)."""
+import ctypes
+import io
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import grid_field_reference as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ('sunerf_grid_field_desc_bytes', 'sunerf_grid_field_fwd', 'sunerf_grid_field_bwd_workspace_bytes',
+               'sunerf_grid_field_bwd')
+
+
+@pytest.fixture(scope='session')
+def lib():
+    import sunerf_hip
+    if not os.path.exists(sunerf_hip.LIB_PATH):
+        import subprocess
+        subprocess.check_call(['bash', os.path.join(ROOT, '2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh')])
+    return sunerf_hip.load()
+
+
+def nonuniform_grid(**kwargs):
+    from sunerf_hip.volume import CartesianGrid
+    return CartesianGrid([-1.0, -0.4, 0.1, 0.3, 1.2], [-0.9, -0.2, 0.5, 0.8], [-1.1, 0.05, 0.7], **kwargs)
+
+
+def spherical_grid(kind):
+    from sunerf_hip.volume import SphericalGrid
+    lat, r = np.linspace(-1.2, 1.2, 7), np.array([1.0, 1.1, 1.25, 1.5, 2.0])
+    if kind == 'closed':
+        lon = np.linspace(-math.pi, math.pi, 12)
+    elif kind == 'open':
+        lon = np.linspace(-math.pi, math.pi, 12, endpoint=False)
+    else:
+        lon = np.linspace(-0.7, 1.1, 12)
+    return SphericalGrid(lat, lon, r)
+
+
+# ---- the restatement --------------------------------------------------------------------------------------------------------
+def test_restatement_agrees_with_scipy_on_a_nonuniform_grid():
+    from scipy.interpolate import RegularGridInterpolator
+    grid = nonuniform_grid()
+    gen = torch.Generator().manual_seed(11)
+    values = torch.randn(5, 4, 3, 2, generator=gen, dtype=torch.float64)
+    pts = (torch.rand(4000, 3, generator=gen) * 2.8 - 1.4).float()
+    nodes = torch.stack(torch.meshgrid(*grid.axes, indexing='ij'), -1).reshape(-1, 3).float()      # every node, the last ones too
+    pts = torch.cat([pts, nodes, torch.tensor([[float('nan'), 0., 0.], [9., 9., 9.]])])
+    fill = (-7.0, 3.0)
+    raw, _, inside = ref.field(grid, values, pts, fill)
+    assert 0.2 < inside.float().mean().item() < 0.8
+    for c in range(2):
+        rgi = RegularGridInterpolator(tuple(a.numpy() for a in grid.axes), values[..., c].numpy(), method='linear',
+                                      bounds_error=False, fill_value=fill[c])
+        want = rgi(pts.double().numpy())
+        want[np.isnan(pts.numpy()).any(1)] = fill[c]              # scipy answers NaN for a NaN coordinate; the field fills
+        assert np.abs(raw[:, c].numpy() - want).max() <= 1e-12
+
+
+def test_inverse_of_the_identity_basis_is_exact():
+    from sunerf_hip.grid_field import affine_inverse
+    grid = nonuniform_grid()
+    assert torch.equal(torch.linalg.inv(grid.basis.T.contiguous()), torch.eye(3, dtype=torch.float64))
+    assert torch.equal(affine_inverse(grid), torch.eye(3, dtype=torch.float64))
+    pts = torch.tensor([[1.2, 0.8, 0.7], [-1.0, -0.9, -1.1]])
+    u = ref.grid_coordinates(grid, pts)
+    assert torch.equal(u, pts.double())
+
+
+@pytest.mark.parametrize('kind', ['closed', 'open', 'patch'])
+def test_spherical_inverse_map_round_trips_at_the_nodes(kind):
+    grid = spherical_grid(kind)
+    nodes = grid.points_f64(1.0).reshape(-1, 3)
+    lat, lon, r = torch.meshgrid(*grid.axes, indexing='ij')
+    # (fp32 points would move the nodes by 1e-7: the round trip is made on the fp64 nodes, the map itself is what is checked)
+    X = nodes
+    rr = torch.sqrt((X[:, 0] ** 2 + X[:, 1] ** 2) + X[:, 2] ** 2)
+    got_lat, got_lon = torch.asin(-X[:, 2] / rr), torch.atan2(-X[:, 0], X[:, 1])
+    assert (got_lat - lat.reshape(-1)).abs().max() < 1e-14
+    assert (rr - r.reshape(-1)).abs().max() < 1e-14
+    dlon = torch.remainder(got_lon - lon.reshape(-1) + math.pi, ref.TWO_PI) - math.pi
+    assert dlon.abs().max() < 1e-14
+    # and through the restatement on fp32 points, to fp32 accuracy of the points
+    u = ref.grid_coordinates(grid, nodes.float(), 1.0, kind)
+    assert (u[:, 0] - lat.reshape(-1)).abs().max() < 1e-6 and (u[:, 2] - r.reshape(-1)).abs().max() < 1e-6
+    d = torch.remainder(u[:, 1] - lon.reshape(-1) + math.pi, ref.TWO_PI) - math.pi
+    assert d.abs().max() < 1e-6
+    lon0 = grid.axes[1][0]
+    assert bool((u[:, 1] >= lon0).all()) and bool((u[:, 1] < lon0 + ref.TWO_PI).all())
+
+
+def _sph_points(lat, lon, r):
+    lat, lon, r = (torch.as_tensor(v, dtype=torch.float64) for v in (lat, lon, r))
+    return torch.stack([-torch.cos(lat) * torch.sin(lon) * r, torch.cos(lat) * torch.cos(lon) * r, -torch.sin(lat) * r], -1).float()
+
+
+def test_the_three_longitude_conventions():
+    from sunerf_hip.grid_field import LON_CLOSED, LON_OPEN, LON_PATCH, longitude_mode
+    f = lambda lat, lon, r: torch.stack([torch.sin(lon) + 0.3 * torch.cos(2 * lon) + lat, r * torch.cos(lon)], -1)   # noqa: E731
+    fill = (-50.0, 0.0)
+    q_lon = torch.tensor([-3.1, -1.0, 0.3, 2.0, 3.05, 3.14, -3.14, 3.3, -4.0])
+    q = _sph_points(torch.full_like(q_lon, 0.2), q_lon, torch.full_like(q_lon, 1.3))
+    answers = {}
+    for kind, mode in (('closed', LON_CLOSED), ('open', LON_OPEN), ('patch', LON_PATCH)):
+        grid = spherical_grid(kind)
+        assert longitude_mode(grid) == mode, kind
+        lat, lon, r = torch.meshgrid(*grid.axes, indexing='ij')
+        values = f(lat, lon, r)
+        raw, _, inside = ref.field(grid, values, q, fill, 1.0, kind)
+        answers[kind] = (raw, inside)
+    # periodic axes answer everywhere, and the two agree with the smooth function to the grid's resolution
+    for kind in ('closed', 'open'):
+        raw, inside = answers[kind]
+        assert bool(inside.all())
+        want = f(torch.full_like(q_lon, 0.2).double(), q_lon.double(), torch.full_like(q_lon, 1.3).double())
+        assert (raw - want).abs().max() < 0.12
+    # 3.3 and -4.0 are 3.3 - 2 pi and 2 pi - 4: the reduction brings them home
+    raw, _ = answers['open']
+    again, _, _ = ref.field(spherical_grid('open'), f(*torch.meshgrid(*spherical_grid('open').axes, indexing='ij')),
+                            _sph_points([0.2, 0.2], [3.3 - ref.TWO_PI, ref.TWO_PI - 4.0], [1.3, 1.3]), fill, 1.0, 'open')
+    assert (raw[-2:] - again).abs().max() < 1e-6
+    # the wrap cell of the open axis: between the last node and the first + 2 pi the answer interpolates those two nodes
+    grid = spherical_grid('open')
+    lon_axis = grid.axes[1]
+    values = torch.zeros(7, 12, 5, 1, dtype=torch.float64)
+    values[:, -1], values[:, 0] = 1.0, 3.0
+    mid = 0.5 * (lon_axis[-1] + lon_axis[0] + ref.TWO_PI)
+    raw, _, inside = ref.field(grid, values, _sph_points([0.2], [mid], [1.3]), (-50.0,), 1.0, 'open')
+    assert bool(inside.all()) and abs(raw.item() - 2.0) < 1e-6
+    # the patch: outside its span the fill, exactly; inside, the same interpolation
+    raw, inside = answers['patch']
+    span = (q_lon >= -0.7) & (q_lon <= 1.1)
+    assert torch.equal(inside, span)
+    assert torch.equal(raw[~span], torch.tensor(fill, dtype=torch.float64).expand(int((~span).sum()), 2))
+    # explicit requests
+    assert longitude_mode(spherical_grid('patch'), True) == LON_OPEN and longitude_mode(spherical_grid('closed'), False) == LON_PATCH
+    assert longitude_mode(spherical_grid('open'), False) == LON_PATCH
+
+
+# ---- the Python side --------------------------------------------------------------------------------------------------------
+def test_refusals():
+    from sunerf.model.grid_model import GridField, GridFieldDT
+    from sunerf_hip.volume import CartesianGrid, Plane, SphericalGrid
+    ax = [0.0, 1.0, 2.0]
+    with pytest.raises(ValueError, match='at least two'):
+        GridField(CartesianGrid(ax, ax, [0.0]))
+    with pytest.raises(ValueError, match='Plane'):
+        GridField(Plane((0, 0, 0), (1, 0, 0), (0, 1, 0), ax, ax))
+    with pytest.raises(ValueError, match='strictly increasing'):
+        GridField(CartesianGrid(ax, [0.0, 1.0, 1.0], ax))
+    with pytest.raises(ValueError, match='strictly increasing'):
+        GridField(CartesianGrid(ax, ax, [2.0, 1.0, 0.0]))
+    with pytest.raises(ValueError, match='1 to 4'):
+        GridField(CartesianGrid(ax, ax, ax), d_output=5)
+    with pytest.raises(ValueError, match='1 to 4'):
+        GridField(CartesianGrid(ax, ax, ax), d_output=0)
+    with pytest.raises(ValueError, match='fill'):
+        GridField(CartesianGrid(ax, ax, ax), d_output=2, fill=(1.0, 2.0, 3.0))
+    with pytest.raises(ValueError, match='d_output must be 2'):
+        GridFieldDT(CartesianGrid(ax, ax, ax), d_output=1)
+    with pytest.raises(ValueError, match='2 pi'):
+        GridField(SphericalGrid([-1.0, 1.0], [0.0, 3.0, 7.0], [1.0, 2.0]))
+    grid = CartesianGrid(ax, ax, ax)
+    with pytest.raises(ValueError, match='do not fit'):
+        GridField.from_volume({'grid': grid, 'inferences': torch.zeros(3, 3, 2, 2), 'Rs_per_ds': 1.0})
+    with pytest.raises(ValueError, match='do not fit'):
+        GridField.from_volume({'grid': grid, 'inferences': torch.zeros(2, 3, 3, 3, 2), 'Rs_per_ds': 1.0})     # two times
+    with pytest.raises(ValueError, match='float32'):
+        GridField.from_volume({'grid': grid, 'inferences': torch.zeros(3, 3, 3, 2, dtype=torch.float64), 'Rs_per_ds': 1.0})
+    from sunerf_hip import SunerfHipError
+    field = GridField(grid)
+    with pytest.raises(SunerfHipError):                       # no CPU path
+        field.field_on_rays(torch.zeros(4, 3), torch.ones(4, 3), torch.ones(4, 8))
+    with pytest.raises(SunerfHipError):
+        field(torch.zeros(4, 4))
+
+
+def test_from_volume_keeps_the_bits(tmp_path):
+    from sunerf.model.grid_model import GridField
+    from sunerf_hip.volume import load_volume, save_volume
+    grid = nonuniform_grid(origin=(0.1, -0.2, 0.3))
+    inf = torch.randn(5, 4, 3, 2, generator=torch.Generator().manual_seed(3))
+    inf[0, 0, 0, 0] = float(np.float32(1e-42))                 # a subnormal survives too
+    volume = {'inferences': inf, 'radius': grid.radius_f64().float(), 'grid': grid, 'times': 0.25, 'Rs_per_ds': 0.5,
+              'kind': 'emission'}
+    field = GridField.from_volume(volume)
+    assert torch.equal(field.values.detach().view(torch.int32), inf.view(torch.int32))
+    assert field.Rs_per_ds == 0.5 and field.d_output == 2 and not field.values.requires_grad
+    assert field.values.data_ptr() != inf.data_ptr()
+    path = str(tmp_path / 'v.npz')
+    save_volume(path, volume)
+    again = GridField.from_volume(load_volume(path), trainable=True)
+    assert torch.equal(again.values.detach().view(torch.int32), inf.view(torch.int32)) and again.values.requires_grad
+    assert torch.equal(again.grid.axes[0], grid.axes[0]) and torch.equal(again.grid.origin, grid.origin)
+    assert torch.equal(field.fill, torch.tensor([-50.0, 0.0]))
+
+
+@pytest.mark.parametrize('kind', ['cartesian', 'closed', 'open', 'patch'])
+def test_smoothness_against_a_hand_computation(kind):
+    from sunerf.model.grid_model import GridField
+    grid = nonuniform_grid() if kind == 'cartesian' else spherical_grid(kind)
+    mode = 'patch' if kind == 'cartesian' else kind
+    field = GridField(grid, d_output=3, init=torch.randn(*grid.shape, 3, generator=torch.Generator().manual_seed(5)))
+    got = field.smoothness()
+    want = ref.smoothness(grid, field.values.detach(), mode)
+    assert abs(got.item() - want.item()) <= 1e-5 * abs(want.item())
+    got.backward()
+    assert field.values.grad is not None and bool(torch.isfinite(field.values.grad).all()) and field.values.grad.abs().max() > 0
+    if kind in ('closed', 'open'):                             # the wrap term is in: without it the value differs
+        plain = ref.smoothness(grid, field.values.detach(), 'patch')
+        assert abs(plain.item() - want.item()) > 1e-4 * abs(want.item())
+    const = GridField(grid, d_output=2, init=(1.5, -2.0))
+    assert const.smoothness().item() == 0.0
+
+
+def test_pickle_and_state_dict_round_trip():
+    from sunerf.model.grid_model import GridField, GridFieldDT
+    from sunerf.rendering.emission import EmissionRadiativeTransfer
+    grid = spherical_grid('open')
+    field = GridFieldDT(grid, init=torch.randn(*grid.shape, 2), fill=(1.0, 2.0), Rs_per_ds=2.0)
+    field._descs['stale'] = object()                           # stands for a device descriptor (ctypes: not picklable)
+    buf = io.BytesIO()
+    torch.save(field, buf)
+    buf.seek(0)
+    back = torch.load(buf, weights_only=False)
+    assert back._descs == {} and back.lon_mode == field.lon_mode and back.Rs_per_ds == 2.0
+    assert torch.equal(back.values, field.values) and torch.equal(back.fill, field.fill)
+    assert set(back.state_dict()) == set(field.state_dict())
+    assert {'values', 'fill', 'volumetric_constant', 'log_absortpion.171'} <= set(field.state_dict())
+    other = GridFieldDT(grid)
+    other.load_state_dict(field.state_dict())
+    assert torch.equal(other.values, field.values) and torch.equal(other.fill, field.fill)
+    # a rendering whose models are grid fields pickles whole (what save_state writes into a .snf)
+    mod = EmissionRadiativeTransfer(Rs_per_ds=1.0, sampling_config={'type': 'stratified', 'n_samples': 8, 'perturb': False},
+                                    hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 8},
+                                    model=GridField, model_config={'grid': nonuniform_grid()})
+    assert isinstance(mod.fine_model, GridField) and mod.fine_model.d_output == 2 and mod.fine_model.d_input == 4
+    buf = io.BytesIO()
+    torch.save({'rendering': mod}, buf)
+    buf.seek(0)
+    back = torch.load(buf, weights_only=False)['rendering']
+    assert torch.equal(back.fine_model.values, mod.fine_model.values)
+    assert not mod._hooks_replaced(EmissionRadiativeTransfer)
+
+
+def test_module_kwargs_default_to_todays_behaviour():
+    import inspect
+    from sunerf.model.model import NeRF
+    from sunerf.model.sunerf import DensityTemperatureSuNeRFModule, EmissionSuNeRFModule
+    sig = inspect.signature(EmissionSuNeRFModule.__init__)
+    assert sig.parameters['model'].default is NeRF and sig.parameters['lambda_smoothness'].default == 0.0
+    assert inspect.signature(DensityTemperatureSuNeRFModule.__init__).parameters['lambda_smoothness'].default == 0.0
+    m = EmissionSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={'vmax': 1, 'a': 0.005},
+                             sampling_config={'type': 'stratified', 'n_samples': 8, 'perturb': False},
+                             hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 8}, model_config={'d_filter': 64})
+    assert isinstance(m.rendering.fine_model, NeRF) and m.lambda_smoothness == 0.0
+    loss = torch.tensor(1.25)
+    assert m._with_smoothness(loss) is loss                    # nothing is added, not even a zero
+    m.lambda_smoothness = 0.5
+    assert m._with_smoothness(loss) is loss                    # a NeRF has no smoothness prior
+    from sunerf.model.grid_model import GridField
+    g = EmissionSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={'vmax': 1, 'a': 0.005},
+                             sampling_config={'type': 'stratified', 'n_samples': 8, 'perturb': False},
+                             hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 8}, model=GridField,
+                             model_config={'grid': nonuniform_grid(), 'init': torch.randn(5, 4, 3, 2)}, lambda_smoothness=0.5)
+    want = loss + 0.5 * (g.rendering.coarse_model.smoothness() + g.rendering.fine_model.smoothness())
+    assert torch.equal(g._with_smoothness(loss), want) and want.item() > 1.25
+    g.lambda_smoothness = 0.0
+    assert g._with_smoothness(loss) is loss
+
+
+# ---- the entry points -------------------------------------------------------------------------------------------------------
+def test_entry_points_are_declared_bound_and_exported(lib):
+    import sunerf_hip
+    from sunerf_hip.grid_field import GridFieldDesc
+    header = open(os.path.join(ROOT, 'include', 'sunerf_hip.h')).read()
+    declared = set(re.findall(r'\b(sunerf_\w+)\s*\(', header))
+    for name in NEW_SYMBOLS:
+        assert name in declared and name in sunerf_hip.EXPORTED_SYMBOLS and getattr(lib, name) is not None, name
+    assert 'mhd_model.py:45-75' in header and 'evaluation/stash/voxel_volume.py' in header
+    assert lib.sunerf_abi_version() == 9
+    assert lib.sunerf_grid_field_desc_bytes() == ctypes.sizeof(GridFieldDesc)
+    build = open(os.path.join(ROOT, '2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh')).read()
+    assert 'grid_field' in build
+
+
+def _desc(n=(5, 4, 3), c=2, kind=0, lon_mode=0, scale=1.0):
+    from sunerf_hip.grid_field import GridFieldDesc
+    d = GridFieldDesc()
+    for k in range(3):
+        d.n[k] = n[k]
+    d.n_channels, d.kind, d.lon_mode, d.Rs_per_ds = c, kind, lon_mode, scale
+    return d
+
+
+def test_argument_errors_without_gpu(lib):
+    """include/sunerf_hip.h: the descriptor and the sizes first, then the empty batch (0), then null pointers (-1) and the
+    workspace (-3); all before anything touches a device."""
+    def fwd(d, n_rays=4, n_samples=8, points=None, stride=0):
+        return lib.sunerf_grid_field_fwd(ctypes.byref(d) if d is not None else None, None, None, None, None, n_rays, n_samples,
+                                         points, stride, None, None, None, None)
+
+    def bwd(d, n_total=100, ws_bytes=0, g_values=None):
+        return lib.sunerf_grid_field_bwd(ctypes.byref(d) if d is not None else None, None, None, None, None, None, n_total, None,
+                                         ws_bytes, g_values, 0, None)
+    assert fwd(None) == -1 and bwd(None) == -1
+    assert fwd(_desc()) == -1                                                     # null pointers
+    assert fwd(_desc(), n_rays=0) == 0 and fwd(_desc(c=4), n_rays=0) == 0
+    assert fwd(_desc(), n_rays=-1) == -1 and fwd(_desc(), n_samples=0) == -1
+    for bad_n in ((1, 4, 3), (5, 1, 3), (5, 4, 1), (5, 4, 0)):
+        assert fwd(_desc(n=bad_n), n_rays=0) == -1 and bwd(_desc(n=bad_n), n_total=0) == -1
+    assert fwd(_desc(c=5), n_rays=0) == -2 and fwd(_desc(c=0), n_rays=0) == -1
+    assert bwd(_desc(c=5)) == -2
+    assert fwd(_desc(kind=2), n_rays=0) == -1 and fwd(_desc(lon_mode=3), n_rays=0) == -1
+    assert fwd(_desc(kind=0, lon_mode=1), n_rays=0) == -1                        # an affine grid has no longitude
+    assert fwd(_desc(kind=1, lon_mode=2), n_rays=0) == 0
+    assert fwd(_desc(scale=0.0), n_rays=0) == -1 and fwd(_desc(scale=float('nan')), n_rays=0) == -1
+    assert fwd(_desc(n=(2048, 2048, 2048)), n_rays=0) == -2                       # 2^33 cells: ids are int32
+    assert bwd(_desc()) == -1 and bwd(_desc(), n_total=-1) == -1
+    assert lib.sunerf_grid_field_bwd_workspace_bytes(0, 2) == 0
+    assert lib.sunerf_grid_field_bwd_workspace_bytes(64, 1) == 2 * 8 * 4
+    assert lib.sunerf_grid_field_bwd_workspace_bytes(65, 4) == 2 * 2 * 8 * 4 * 4
+    assert lib.sunerf_grid_field_bwd_workspace_bytes(257 * 67, 2) == ((257 * 67 + 63) // 64) * 2 * 8 * 2 * 4
