@@ -299,6 +299,25 @@ class SuNeRFLoader:
         return self._dem_map(time, lat_range, lon_range, shape, r_range, n_samples, batch_size, as_numpy, logt_nodes,
                              attenuation_wavelength, length_scale)
 
+    @torch.no_grad()
+    def invert_dem_image(self, images, wl=None, logt_nodes=None, errors=None, as_numpy: bool = True, **solver):
+        """The classical per-pixel DEM inversion (optically thin) of ``images`` (..., M) -- a frame of
+        :meth:`render_observer_image` of a density-temperature rendering, or observations in its units -- for the channels ``wl``
+        (default: all seven): ``DensityTemperatureRadiativeTransfer.invert_dem`` (``sunerf_hip.dem_inversion``), to set next to
+        :meth:`render_dem_image`'s ``dem`` / ``em`` / ``logt_mean`` of the same frame.  ``errors``, ``lam``, ``prior``,
+        ``chi2_target``, ... go through.  Raises ``TypeError`` for a rendering without a temperature."""
+        rendering = _dt_rendering(self.rendering, 'invert_dem_image')           # before any device work
+        if not isinstance(images, torch.Tensor):
+            images = torch.as_tensor(np.asarray(images), dtype=torch.float32)
+        if errors is not None and not isinstance(errors, torch.Tensor):
+            errors = torch.as_tensor(np.asarray(errors), dtype=torch.float32)
+        images = images.to(self.device)
+        out = rendering.invert_dem(images, None if wl is None else np.asarray(wl).reshape(-1).tolist(), logt_nodes,
+                                   None if errors is None else errors.to(self.device), **solver)
+        if not as_numpy:
+            return out
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
     def _volume(self, time: float, grid, wl, quantities, r_range, fill, batch_size, as_numpy):
         out = sample_volume(self.rendering, grid, float(time), None if wl is None else np.asarray(wl, dtype=np.float32),
                             quantities, r_range, fill, tile_points=None if batch_size is None else int(batch_size))

@@ -171,6 +171,49 @@ class DensityTemperatureRadiativeTransfer(SuNeRFRendering):
         out.update(logt_nodes=nodes, z_vals=z_comb)
         return out
 
+    # ---- per-pixel DEM inversion of images (sunerf_hip/dem_inversion.py) ------------------------------------------
+    def channel_indices(self, wavelengths=None):
+        """Rows of the response table for ``wavelengths`` (default: all of ``ops.AIA_WAVELENGTHS``); an unknown channel raises
+        like :meth:`attenuation_scalar`."""
+        rows = []
+        for w in (ops.AIA_WAVELENGTHS if wavelengths is None else wavelengths):
+            try:
+                ok = float(w) == int(w) and int(w) in ops.AIA_WAVELENGTHS
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f'wavelength {w!r} is not a channel of the model '
+                                 f'({", ".join(str(c) for c in ops.AIA_WAVELENGTHS)})')
+            rows.append(ops.AIA_WAVELENGTHS.index(int(w)))
+        return rows
+
+    @torch.no_grad()
+    def inversion_response(self, wavelengths=None, logt_nodes=None):
+        """``G`` (M, K) float64 of :meth:`invert_dem`: ``volumetric_constant * pixel_intensity_factor`` times the channels'
+        response rows on the nodes (``dem_inversion.response_on_nodes``), so that ``G @ dem`` is ``forward``'s optically thin
+        image of a line-of-sight DEM ``dem``."""
+        from sunerf_hip.dem_inversion import response_on_nodes
+        rows = self.channel_indices(wavelengths)
+        nodes = self.dem_nodes(logt_nodes)
+        resp = response_on_nodes(self.response_logte[rows], self.response_table[rows], nodes)
+        vol_c = self.fine_model.volumetric_constant.detach().to(device=resp.device, dtype=torch.float64)
+        return resp * (vol_c * float(self.pixel_intensity_factor))
+
+    @torch.no_grad()
+    def invert_dem(self, images, wavelengths=None, logt_nodes=None, errors=None, **solver):
+        """The classical per-pixel DEM inversion of ``images`` (..., M), the channels ``wavelengths`` (default: all seven of
+        ``ops.AIA_WAVELENGTHS``, in that order) of ``forward``'s image or of observations in its units:
+        ``sunerf_hip.dem_inversion.invert_dem`` with :meth:`inversion_response`; ``errors`` and ``**solver`` (``lam``, ``prior``,
+        ``chi2_target``, ``lam_range``, ...) go through.  This is the OPTICALLY THIN inversion: the model's ``log_absortpion`` is
+        not inverted, so compare with ``render_dem`` without ``attenuation_wavelength``.  On the default nodes
+        ``dem.fold(result['dem'], response rows) * constants`` is comparable with ``forward``'s image and ``result['dem']`` /
+        ``em`` / ``logt_mean`` with ``render_dem``'s, key for key."""
+        from sunerf_hip.dem_inversion import invert_dem
+        G = self.inversion_response(wavelengths, logt_nodes)
+        if not isinstance(images, torch.Tensor) or images.dim() < 1 or images.shape[-1] != G.shape[0]:
+            raise ValueError(f'images must be (..., {G.shape[0]}): one value per channel')
+        return invert_dem(images, G, self.dem_nodes(logt_nodes), errors, **solver)
+
     def _render(self, model, query_points, rays_d, rays_o, z_vals, wavelengths):
         """density_temperature.py:148-190: ``model.forward`` at the query points -- inferences with the base offsets, the
         absorption scalars, the volumetric constant -- plus ``z_vals`` / ``rays_d`` / ``wavelengths`` into ``raw2outputs``."""

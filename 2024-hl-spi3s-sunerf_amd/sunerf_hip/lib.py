@@ -89,6 +89,10 @@ _SIGNATURES = {
     'sunerf_dem_integral': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                             c_f32p, ctypes.c_float, ctypes.c_float, ctypes.c_int64, ctypes.c_int, c_f32p, c_f32p,
                                             c_f32p, c_f32p, c_void]),
+    'sunerf_dem_invert': (ctypes.c_int, [c_f32p, c_f32p, c_void, c_void, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double,
+                                          ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, c_f32p,
+                                          c_f32p, c_f32p, c_void, c_void]),
     'sunerf_hier_resample': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
                                              ctypes.c_int, c_f32p, c_f32p, c_void]),
     'sunerf_mlp_points_fwd': (ctypes.c_int, [c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int64, c_f32p,

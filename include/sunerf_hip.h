@@ -588,6 +588,38 @@ int sunerf_volume_metrics(const float* a, const float* b, int n0, int n1, int n2
                           const double* w2, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Per-pixel DEM inversion: channel images -> DEM(log T) per pixel.  Nothing in the reference inverts; the
+ * result is comparable, key for key, with sunerf_dem_integral's -- the line-of-sight DEM of the model behind
+ * density_temperature.py:237-265 -- and, folded with the response, with that render's image.
+ *
+ * For every pixel i, with y [N][M] the channel values, sigma [N][M] > 0 their errors (fp32), response [M][K] >= 0 the
+ * channels' response on the K log T nodes times the render's constant, prior [K] > 0 a scale per node (fp64) and lam > 0:
+ *   x* = argmin over x >= 0 of  1/2 sum_w ((response x - y)_w / sigma_w)^2 + lam/2 sum_k (x_k / prior_k)^2
+ * (strictly convex: unique; what scipy.optimize.nnls returns for the stacked system), by semismooth Newton on the dual in
+ * fp64, one lane per pixel: stops at max |F| <= tol max |y / sigma| or after max_iter Newton steps.
+ *   A channel whose y is not finite, or whose sigma is not finite or <= 0, is left out for that pixel.
+ *   discrepancy == 0: lam [N] (lam_per_pixel != 0) or [1] fp32 device, each > 0 and finite.
+ *   discrepancy != 0: lam is not read; per pixel log10 lam is bisected n_bisect times on [lam_min, lam_max] for
+ *     chi2(lam) = sum_w ((response x* - y)_w / sigma_w)^2 = chi2_target (< 0: the number of channels the pixel uses); each
+ *     solve starts from the previous one; the solve at the middle of the last bracket is returned.  chi2(lam_min) > target
+ *     returns the solve at lam_min and sets status bit 4, chi2(lam_max) < target the solve at lam_max and bit 8.  Every lam
+ *     of a solve is an fp32 number (lam_min and lam_max are rounded first): lam_out is the lam of the returned x*.
+ *   dem [N][K] = x*, em [N] = sum_k x*_k, logt_mean [N] = sum_k x*_k logt_nodes[k] / em (NaN where em = 0), chi2 [N],
+ *   lam_out [N] (fp32; the sums in fp64); each may be NULL.  status [N] int32, required: bit 0 a solve stopped before it
+ *   met tol (max_iter, or 30 line-search trials of one step), 2 no channel left (dem = em = 0, logt_mean = lam_out = NaN), 4 / 8 the
+ *   bracket ends, 16 a lam that is not > 0 and finite (outputs as for 2); bits 8.. the Newton steps of all solves.
+ * No atomics; a pixel's outputs depend on its own inputs only: reruns, batches and tilings give the same bits.
+ * Sizes are checked first (n_nodes < 2, n_channels < 1, n_bisect < 0, max_iter < 1, n_pixels < 0: -1; n_nodes > 128,
+ * n_channels > 8, n_bisect > 60 or max_iter > 4096: -2), then the empty batch (0), then values and null pointers (tol < 0,
+ * in discrepancy mode a [lam_min, lam_max] that is not 0 < lam_min <= lam_max < inf, a NULL input or status: -1).
+ * ---------------------------------------------------------------------------------------------------------- */
+int sunerf_dem_invert(const float* y, const float* sigma, const double* response, const double* prior,
+                      const float* logt_nodes, const float* lam, int lam_per_pixel, int discrepancy, double chi2_target,
+                      double lam_min, double lam_max, int n_bisect, double tol, int max_iter, int64_t n_pixels,
+                      int n_channels, int n_nodes, float* dem, float* em, float* logt_mean, float* chi2, float* lam_out,
+                      int* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Voxel-grid field: values [n0][n1][n2][C] fp32 on the nodes of a grid (C order over the grid's axes,
  * the layout of sample_volume's `inferences`), 1 <= C <= 4, gathered trilinearly and fitted through the adjoint.
  * Generalises the interpolators of MHDModel, sunerf/model/mhd_model.py:45-75 (RegularGridInterpolator(method='linear',
