@@ -148,9 +148,11 @@ extern "C" int sunerf_pack_mlp(const float* const* weights_host, const float* co
   const int threads = 256;
   const unsigned blocks = (unsigned)((total + threads - 1) / threads);
   SUNERF_CLEAR_ERROR();
+  // the 128-byte scale block is part of the image in every mode (FAST fills it below): a packed buffer is the same bytes
+  // whatever it held before
+  hipError_t e = hipMemsetAsync(a.packed + L.scale_off(), 0, 128, (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
   if (a.fp8c) {
-    hipError_t e = hipMemsetAsync(a.packed + L.scale_off(), 0, 128, (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(pack_absmax_kernel, dim3(64, n_linear - 1), dim3(256), 0, (hipStream_t)stream, a);
     SUNERF_CHECK_LAUNCH();
   }

@@ -575,6 +575,10 @@ __global__ __launch_bounds__(1024) void layer_sumsq_kernel(PackTArgs a) {
     for (int i = 0; i < 16; ++i) t += part[i];
     a.sumsq[l] = t;
   }
+  // the slots no layer owns (the in layer's, and those beyond n_linear) are part of the image too: a packed buffer is the same
+  // bytes whatever it held before
+  if (blockIdx.x == 0 && threadIdx.x < SUNERF_MAX_LAYERS && (threadIdx.x == 0 || (int)threadIdx.x >= a.n_linear))
+    a.sumsq[threadIdx.x] = 0.f;
 }
 
 __global__ void pack_mlp_t_kernel(PackTArgs a) {

@@ -16,6 +16,24 @@
  *     failed.  The Python side turns non-zero into RuntimeError / ValueError.
  *   - thread-safe / re-entrant: no global mutable state (evaluation/loader.py:226-229 calls the renderer from
  *     a ThreadPoolExecutor).
+ *   - a kernel reads and writes exactly the extents given per argument, whatever the launch is rounded up to, and no
+ *     result depends on what an output or a workspace held before the call (unless the argument is documented as
+ *     accumulated into, updated in place or zeroed by the caller); a workspace of the size its *_bytes() query returns
+ *     is enough, a smaller one is refused with SUNERF_E_WORKSPACE before anything is queued
+ *     (tests/test_gpu_abi_extents.py holds every entry point to this between guard words).
+ *   - an empty batch (a count of zero rays, points, pixels, columns, voxels, slots, rows or images) is handled per entry
+ *     point, in one of three ways (each checked by tests/test_gpu_abi_extents.py):
+ *       returns 0 and touches no buffer: sunerf_sample_z, _hier_resample, _sample_pdf, _emission_render_fwd, _mlp_points_fwd,
+ *         _emission_integral_fwd, _mlp_dgrad, _dt_integral_fwd, _thomson_integral_fwd, _dem_integral, _column_stats,
+ *         _simple_star_field(_dev), _mhd_field(_points), _grid_field_fwd, _observer_rays, _column_rays, _build_ray_pool,
+ *         _synchronic_map (n_rows == 0), _grid_points, _field_quantities, _image_metrics, _dem_invert, _clip_adam_step;
+ *       returns 0 and writes the gradient of nothing: sunerf_emission_integral_bwd / _thomson_integral_bwd clear g_absmax,
+ *         sunerf_dt_integral_bwd(_full) clear g_log_abs, g_vol_c and g_absmax, and with accumulate == 0 sunerf_mlp_wgrad
+ *         zeroes every grad_weights / grad_biases tensor, sunerf_grid_field_bwd g_values and sunerf_simple_star_bwd g_params
+ *         (accumulate != 0: left as they are);
+ *       is SUNERF_E_BADARG, nothing written: sunerf_mlp_backward_pipe, _mlp_backward_exact, _mlp_backward_exact_chunked and
+ *         _mlp_input_grad_exact (n_rays >= 1), sunerf_training_loss (n >= 1), sunerf_map_fill and sunerf_reproject_views
+ *         (n_pixels >= 1), sunerf_volume_metrics (every n >= 1).
  */
 #ifndef SUNERF_HIP_H
 #define SUNERF_HIP_H
@@ -65,7 +83,8 @@ int sunerf_abi_version(void);
  *   weights_host[i] -> device fp32 W_i [out_i, in_i] row-major (nn.Linear layout), i = 0..n_linear-1
  *   biases_host[i]  -> device fp32 b_i [out_i]
  *   n_linear = n_layers + 1 : in_layer (84 -> d_filter), n_layers-1 hidden (d_filter -> d_filter), out_layer
- *   packed: device buffer of sunerf_packed_mlp_bytes() bytes, 16-byte aligned
+ *   packed: device buffer of sunerf_packed_mlp_bytes() bytes, 16-byte aligned; every byte of it is written in every mode (the
+ *           scale block that only FAST uses is zero otherwise), so two packs of one model are the same bytes
  *   precision: SUNERF_PRECISION_FAST / _EXACT (above); selects the stream format of the hidden and out layers
  * ---------------------------------------------------------------------------------------------------------- */
 size_t sunerf_packed_mlp_bytes(int d_filter, int n_linear);
@@ -107,6 +126,9 @@ int sunerf_sample_z(int sampler_kind, const float* rays_o, const float* rays_d, 
  *                sunerf_mlp_dgrad / sunerf_mlp_wgrad read -- or SUNERF_STASH_PHASE -- the 16-bit phase of every pre-activation
  *                (4.1 KB per sample; sin and cos to 4.8e-5 from it): what sunerf_mlp_backward_pipe reads; d_filter = 256 only
  *   workspace  : sunerf_render_workspace_bytes(d_filter) bytes of device scratch (may be NULL when that is 0)
+ *   n_samples >= 2 (the first interval of emission.py:19-26 is the second one, duplicated): a single sample is
+ *   SUNERF_E_BADARG, here and in sunerf_emission_integral_fwd / _bwd, sunerf_mlp_dgrad, sunerf_mlp_wgrad and
+ *   sunerf_mlp_backward_pipe
  * ---------------------------------------------------------------------------------------------------------- */
 #define SUNERF_STASH_FP16  0
 #define SUNERF_STASH_PHASE 1
@@ -144,7 +166,9 @@ int sunerf_mlp_points_fwd(const void* packed, int d_filter, int n_linear, int pr
  *
  *   packedT  : sunerf_pack_mlp_t output (transposed fp16 weight image, each layer times a power of two chosen from the layer's
  *              own weights so that the data gradient keeps the scale of g_raw from layer to layer; the same buffer goes to
- *              sunerf_mlp_dgrad and sunerf_mlp_wgrad), re-pack after every optimiser step
+ *              sunerf_mlp_dgrad and sunerf_mlp_wgrad), re-pack after every optimiser step; sunerf_packed_mlp_t_bytes() bytes,
+ *              every one of them written (the tail holds SUNERF_MAX_LAYERS floats: the sum of squares of every layer's weights
+ *              behind the first, 0 in the slots no layer owns)
  *   g_reg    : (N,S) gradient w.r.t. the 'regularization' output, or NULL with g_reg_const (the usual
  *              lambda / (N*S) of regularization.mean(), sunerf.py:118-119)
  *   g_absmax : 4-byte device scratch (bit pattern of max |g_raw|; selects the fp16 gradient scale on the device)
@@ -160,12 +184,13 @@ size_t sunerf_wgrad_workspace_bytes(int d_filter, int n_linear, int split);
 /* EmissionRadiativeTransfer.raw2outputs (sunerf/rendering/emission.py:14-54, cumprod_exclusive base_tracing.py:135-156) on a
  * GIVEN raw tensor -- the subclass hook SuNeRFRendering._render calls (base_tracing.py:128): raw (N,S,2), z_vals (N,S),
  * rays_d (N,3) -> image (N), weights (N,S), absorption (N,S) = the 'regularizing_quantity'.  (Inside
- * sunerf_emission_render_fwd the same arithmetic is fused behind the MLP.) */
+ * sunerf_emission_render_fwd the same arithmetic is fused behind the MLP.)  n_samples >= 2. */
 int sunerf_emission_integral_fwd(const float* raw, const float* z_vals, const float* rays_d, int64_t n_rays, int n_samples,
                                  float* image, float* weights, float* absorption, void* stream);
 
 /* g_weights / g_absorption: optional (N,S) gradients w.r.t. the 'weights' and 'regularizing_quantity' outputs of
- * raw2outputs (NULL on the training path, whose loss only reads image and regularization) */
+ * raw2outputs (NULL on the training path, whose loss only reads image and regularization).  g_raw (N,S,2) is overwritten;
+ * g_absmax (4 bytes, required) is cleared by every call, an empty batch (n_rays == 0) included, and then raised to max |g_raw| */
 int sunerf_emission_integral_bwd(const float* raw, const float* z_vals, const float* rays_o, const float* rays_d,
                                  const float* g_image, const float* g_reg, const float* g_weights, const float* g_absorption,
                                  float g_reg_const, float reg_radius, int64_t n_rays, int n_samples, float* g_raw,
@@ -289,7 +314,11 @@ int sunerf_mlp_input_grad_exact(const float* const* weights_host, const float* c
  *   image (N,W); weights (N,S) = relu(inf0)/(sum+1e-10); reg_q (N,S) = relu(inf0);
  *   height_map / absorption_map (N) and regularization (N,S) optional; reg_radius = 1.25 / Rs_per_ds
  *   backward: g_image (N,W), g_reg (N,S) or NULL -> g_raw (N,S,2) (feed sunerf_mlp_dgrad / sunerf_mlp_wgrad),
- *   g_log_abs (7), g_vol_c (1) (overwritten), g_absmax as in sunerf_emission_integral_bwd
+ *   g_log_abs (7), g_vol_c (1) (overwritten: cleared by the call, then summed with float atomics -- every ray adds its term
+ *   to its workgroup's sum and every workgroup its sum to the output, so from three rays on the order of the adds is free and
+ *   reruns agree to rounding, not by bits; g_raw and g_absmax do not depend on it), g_absmax as in
+ *   sunerf_emission_integral_bwd; all three required; an empty batch (n_rays == 0) clears them and touches nothing else
+ *   n_samples >= 3 (forward and backward; fewer: SUNERF_E_BADARG), at most 705 in the backward (its LDS: SUNERF_E_UNSUPPORTED)
  * ---------------------------------------------------------------------------------------------------------- */
 int sunerf_dt_integral_fwd(const float* raw, const float* z_vals, const float* rays_o, const float* rays_d,
                            const float* wavelengths, int n_wavelengths, const float* table_logt, const float* table_resp,
@@ -365,7 +394,8 @@ int sunerf_dem_integral(const float* raw, const float* z_vals, const float* rays
  *   ds_j = (z_j - z_{j-1}) |d|, ds_0 = ds_1 (:25-31); for S = 1 there is no ds and pixel_b = pixel_density = 0.
  *   backward: any subset of g_pixel_b (N,2), g_pixel_density, g_distance_from_sun, g_distance_from_obs (N),
  *   g_weights (N,S) (NULL = absent) -> g_raw (N,S,C) (channel 1 written 0); g_absmax (4 bytes, may be NULL) receives
- *   the bit pattern of max |g_raw|, as in sunerf_emission_integral_bwd (the scale sunerf_mlp_dgrad takes).
+ *   the bit pattern of max |g_raw|, as in sunerf_emission_integral_bwd (the scale sunerf_mlp_dgrad takes); given, it is
+ *   cleared by every call, an empty batch (n_rays == 0) included.
  *   n_samples >= 1; no float atomics: reruns are bit-identical.
  * ---------------------------------------------------------------------------------------------------------- */
 int sunerf_thomson_integral_fwd(const float* raw, int n_channels, float kappa, const float* z_vals, const float* rays_o,
@@ -518,6 +548,7 @@ int sunerf_column_rays(const double* lat, const double* lon, int per_column, int
  *   emission_height [N] = height_scale * sum r_j e_j / sum e_j            topographical_profile.py:57
  *   emission_column [N] = sum e_j dr_j  (optically thin column)          topographical_slice.py:131-140 (there without dr)
  *   emission [N,S] = e_j, absorption [N,S] = 1 - exp(-relu(raw_j1) dr_j) eruption_profile.py:89-94 (both NULL or both set)
+ *   n_samples >= 2 (SUNERF_E_BADARG otherwise: dr needs an interval)
  * ---------------------------------------------------------------------------------------------------------- */
 int sunerf_column_stats(const float* raw, const float* z_row, const float* rays_d, int64_t n_cols, int n_samples,
                         float height_scale, float* emission_height, float* emission_column, float* emission,
@@ -648,7 +679,9 @@ int sunerf_dem_invert(const float* y, const float* sigma, const double* response
  *   perm [n_total] int64: a stable ascending sort of `cells`; seg_start [number of cells + 1] int64: the first sorted
  *   position of every cell id (searchsorted of the sorted ids).  No floating-point atomics: per node the segments of its
  *   adjacent cells are added in a fixed order, segments longer than 64 samples through per-wave partial sums in `workspace`
- *   (sunerf_grid_field_bwd_workspace_bytes): reruns are bit-identical.  accumulate != 0 adds onto g_values.
+ *   (sunerf_grid_field_bwd_workspace_bytes): reruns are bit-identical.  accumulate != 0 adds onto g_values.  g_values
+ *   [n0][n1][n2][C] fp32; g_raw [n_total][C].  n_total == 0: g_values is zeroed (accumulate == 0) or left alone, and no other
+ *   pointer is read.
  * Sizes and the descriptor are checked first (n[k] < 2, C < 1, a bad kind / lon_mode, Rs_per_ds <= 0: -1; C > 4 or 2^31
  * cells: -2), then the empty batch (0), then null pointers (-1) and the workspace (-3).  `grid` is a HOST pointer; its
  * axis pointers are device arrays (fp64).
@@ -814,7 +847,7 @@ int sunerf_mhd_field_points(const float* points, int64_t n_points, const SunerfM
  * passed in as the tensor `u` [S_f] so that torch.linspace's own fp32 values are used; or a per-ray u [N,S_f]
  * with u_per_ray != 0 for perturb=True).
  *
- *   z_vals [N,S_c], weights [N,S_c] -> new_z [N,S_f], z_comb [N,S_c+S_f] (sorted)
+ *   z_vals [N,S_c], weights [N,S_c] -> new_z [N,S_f], z_comb [N,S_c+S_f] (sorted);  S_c >= 3 (the pdf is weights[1:-1]), S_f >= 1
  * ---------------------------------------------------------------------------------------------------------- */
 int sunerf_hier_resample(const float* z_vals, const float* weights, const float* u, int u_per_ray,
                          int64_t n_rays, int n_coarse, int n_fine, float* new_z, float* z_comb, void* stream);
@@ -825,7 +858,7 @@ int sunerf_hier_resample(const float* z_vals, const float* weights, const float*
  * cdf = [0, cumsum(pdf)], searchsorted(cdf, u, right=True), linear interpolation between the neighbouring bins with the
  * reference's `denom < 1e-5 -> 1` rule.  `u` as in sunerf_hier_resample.
  *
- *   bins [N,B], weights [N,B-1] -> samples [N,S_f]
+ *   bins [N,B], weights [N,B-1] -> samples [N,S_f];  B >= 2, S_f >= 1
  * ---------------------------------------------------------------------------------------------------------- */
 int sunerf_sample_pdf(const float* bins, const float* weights, const float* u, int u_per_ray, int64_t n_rays,
                       int n_bins, int n_fine, float* samples, void* stream);

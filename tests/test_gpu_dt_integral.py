@@ -46,6 +46,7 @@ PIXEL = {'generic': float(torch.tensor(1e26)), 'nerf_dt': float(torch.tensor(1e1
 # optical depth along a ray per channel (94 ... 335); None: log_abs < 0, kappa = relu(log_abs) = 0 and no gradient
 TAUS = (1e-3, 0.03, 0.3, 3.0, None, 30.0, 100.0)
 REG_RADIUS = 1.25
+SCALAR_GRADIENT_REL = 1e-4      # g_log_abs / g_vol_c against fp64 (float atomics: the order of the adds is free)
 CHUNK = 1024            # oracle rays per evaluation: the scalar gradients are sums over rays, added over chunks in fp64
 
 
@@ -279,7 +280,7 @@ def check_case(ops, c):
     assert m['weights'] <= 1e-5 and m['height_map'] <= 1e-5 and m['absorption_map'] <= 1e-5, m
     assert m['g_raw'] <= 1.0 and m['g_raw_full'] <= 1.0, m
     for k in ('g_log_abs', 'g_vol_c', 'g_log_abs_full', 'g_vol_c_full'):
-        assert m[k] <= 1e-4, (k, m)
+        assert m[k] <= SCALAR_GRADIENT_REL, (k, m)
 
 
 S_VALUES = (3, 31, 32, 33, 34, 63, 64, 65, 129, 256, 257, 300, 705)
