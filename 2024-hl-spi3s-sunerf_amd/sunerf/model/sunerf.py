@@ -72,9 +72,13 @@ class BaseSuNeRFModule(LightningModule):
         (``GridField``: tomography's regulariser); the loss itself with the default ``lambda_smoothness = 0``."""
         lam = getattr(self, 'lambda_smoothness', 0.0)
         models = (self.rendering.coarse_model, self.rendering.fine_model)
-        if not lam > 0 or not all(hasattr(m, 'smoothness') for m in models):
-            return loss
-        return loss + lam * (models[0].smoothness() + models[1].smoothness())
+        if lam > 0 and all(hasattr(m, 'smoothness') for m in models):
+            loss = loss + lam * (models[0].smoothness() + models[1].smoothness())
+        # the temporal prior of a grid with a time axis (``DynamicGridField``), likewise only when asked for
+        lam_t = getattr(self, 'lambda_temporal', 0.0)
+        if lam_t > 0 and all(hasattr(m, 'temporal_smoothness') for m in models):
+            loss = loss + lam_t * (models[0].temporal_smoothness() + models[1].temporal_smoothness())
+        return loss
 
     def _step_nonfinite_count(self):
         """This step's non-finite output count (device scalar) for ``ClipAdam.step(closure)``."""
@@ -188,10 +192,11 @@ class EmissionSuNeRFModule(BaseSuNeRFModule):
 
     def __init__(self, Rs_per_ds, seconds_per_dt, image_scaling_config, lambda_image=1.0, lambda_regularization=1.0,
                  sampling_config=None, hierarchical_sampling_config=None, model_config=None, model=NeRF,
-                 lambda_smoothness=0.0, **kwargs):
+                 lambda_smoothness=0.0, lambda_temporal=0.0, **kwargs):
         self.lambda_image = lambda_image
         self.lambda_regularization = lambda_regularization
         self.lambda_smoothness = lambda_smoothness
+        self.lambda_temporal = lambda_temporal
         rendering = EmissionRadiativeTransfer(Rs_per_ds=Rs_per_ds, sampling_config=sampling_config,
                                               hierarchical_sampling_config=hierarchical_sampling_config,
                                               model_config=model_config, model=model)
@@ -248,10 +253,11 @@ class DensityTemperatureSuNeRFModule(BaseSuNeRFModule):
 
     def __init__(self, Rs_per_ds, seconds_per_dt, image_scaling_config, model, loss=nn.MSELoss(), lambda_image=1.0,
                  lambda_regularization=1.0, sampling_config=None, hierarchical_sampling_config=None,
-                 pixel_intensity_factor=1e17, model_config=None, lambda_smoothness=0.0, **kwargs):
+                 pixel_intensity_factor=1e17, model_config=None, lambda_smoothness=0.0, lambda_temporal=0.0, **kwargs):
         self.lambda_image = lambda_image
         self.lambda_regularization = lambda_regularization
         self.lambda_smoothness = lambda_smoothness
+        self.lambda_temporal = lambda_temporal
         rendering_kwargs = {k: kwargs.pop(k) for k in ('response_table', 'response_path') if k in kwargs}
         rendering = DensityTemperatureRadiativeTransfer(Rs_per_ds=Rs_per_ds, sampling_config=sampling_config,
                                                         hierarchical_sampling_config=hierarchical_sampling_config,

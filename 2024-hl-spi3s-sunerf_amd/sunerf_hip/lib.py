@@ -171,6 +171,21 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# The extension table (include/sunerf_hip_ext.h): entry points added beside the table above, which stays as it is and keeps
+# its version.  The same library holds both.
+_EXT_SIGNATURES = {
+    'sunerf_ext_abi_version': (ctypes.c_int, []),
+    'sunerf_dynamic_grid_fwd': (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                                ctypes.c_int64, ctypes.c_int, c_f32p, ctypes.c_int, c_f32p, c_void, c_f32p,
+                                                c_void]),
+    'sunerf_dynamic_grid_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    'sunerf_dynamic_grid_bwd': (ctypes.c_int, [c_void, ctypes.c_int, c_f32p, c_void, c_f32p, c_void, c_void, ctypes.c_int64,
+                                                c_void, ctypes.c_size_t, c_f32p, ctypes.c_int, c_void]),
+}
+
+EXTENSION_SYMBOLS = tuple(_EXT_SIGNATURES)
+EXT_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -191,6 +206,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_abi_version() != 9:
             raise SunerfHipError('libsunerf_hip.so ABI version mismatch')
+        for name, (res, args) in _EXT_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_ext_abi_version() != EXT_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so extension ABI version mismatch')
         _lib = lib
     return _lib
 
