@@ -12,15 +12,19 @@
 //   sin^2(chi) = |o x d|^2 / (l^2 r^2),   u = limb_darkening_coeff
 //   I_T = (1-u) C + u D,   I_P = sin^2(chi) ((1-u) A + u B),   I_tot = 2 I_T - I_P
 //   |I_tot|, |I_P|, both 0 where r <= R or a value is not finite (nan_to_num, thompson.py:76-80)
+//   Seams: the limb is inside (r == R by bits gives 0, as does one fp32 step of z further in; one step out gives the limb
+//   values); d = 0 makes sin^2(chi) = 0 / 0, so both intensities are 0, as are all line elements; a ray through the centre has
+//   |o x d| = 0 and I_P = 0 exactly; a sample at the origin (R / r = inf) is inside; repeated z give D_j = 0.
 //
 //   pixel_B = C_0 (sum rho |I_tot| D, sum rho |I_P| D),  pixel_density = sum rho D,  M = sum rho
 //   distance_from_sun = sum rho r / (M + 1e-10),  distance_from_obs = sum rho z l / (M + 1e-10),  weights = rho / (M + 1e-10)
 //
 // Numerics: A..D are differences that cancel to O(s^2) far from the Sun (C ~ s^2, B ~ D ~ 2/3 s^2), so in fp32 the relative
 // error grows as 2^-24 / s^2 (8 % at 215 solar radii).  The sample point, its radius and A..D are evaluated in fp64 from the
-// fp32 inputs (C in the cancellation-free form (1 - c)(4 + c + c^2) / 3 with 1 - c = s^2 / (1 + c), L as log1p): the
-// residual relative error is ~1e-16 / s^2.  The sums stay fp32 (positive terms).  -DSUNERF_THOMSON_GEOMETRY_FP32 builds the
-// same arithmetic in fp32: a measurement variant (tools/thomson_render_time.py), not a product configuration.
+// fp32 inputs (C in the cancellation-free form (1 - c)(4 + c + c^2) / 3 with 1 - c = s^2 / (1 + c), L as log1p, c^2 as
+// (r^2 - R^2) / r^2): the residual relative error is ~1e-16 / s^2.  The sums stay fp32 (positive terms).
+// -DSUNERF_THOMSON_GEOMETRY_FP32 builds the same arithmetic in fp32: a measurement variant (tools/thomson_render_time.py), not
+// a product configuration.
 //
 // Layout as dt.hip: 32 lanes per ray, one sample per lane and 32-sample chunk (coalesced reads of raw / z, coalesced writes),
 // per-ray sums over the ray's own lanes (butterfly), no float atomics: reruns are bit-identical.  The backward also writes
@@ -104,9 +108,13 @@ __device__ __forceinline__ Sample sample_geometry(const Ray& ry, float z, geo_t 
   Sample o;
   o.r = (float)r;
   o.i_tot = o.i_p = 0.f;
-  if (!WANT_I || !(r > R)) return o;           // inside / on the Sun, or a NaN point
+  // inside / on the Sun, or a NaN point.  (On the limb itself c = 0 and (c^2 / s) L below is 0 * inf: the finite check at the
+  // end would zero r == R as well, so `>` and `>=` compute the same here; the comparison states the contract.)
+  if (!WANT_I || !(r > R)) return o;
   const geo_t s = R / r, s2 = s * s;
-  const geo_t c2 = geo_t(1) - s2, c = sqrt(c2);
+  // cos^2 from the squares: r^2 - R^2 is exact next to the limb, where 1 - s^2 keeps only the rounding of r (1e-3 of c one
+  // fp32 step of z outside a limb at R = 1 / 0.7, and with it of I_P = c s^2 sin^2(chi) at u = 0).  r > R gives r^2 > R^2.
+  const geo_t c2 = (r2 - R * R) / r2, c = sqrt(c2);
   const geo_t L = geo_t(0.5) * log1p(geo_t(2) * s / (geo_t(1) - s));       // ln((1 + s) / c)
   const geo_t k = c2 * r / R * L;                                          // (c^2 / s) L
   const geo_t A = c * s2;

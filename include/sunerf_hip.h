@@ -392,6 +392,13 @@ int sunerf_dem_integral(const float* raw, const float* z_vals, const float* rays
  *   pixel_density (N) = sum rho ds;  distance_from_sun / _obs (N) = sum rho r / (M + 1e-10), sum rho z |d| / (M + 1e-10);
  *   weights (N,S) = rho / (M + 1e-10), M = sum rho                   (:94-101)
  *   ds_j = (z_j - z_{j-1}) |d|, ds_0 = ds_1 (:25-31); for S = 1 there is no ds and pixel_b = pixel_density = 0.
+ *   On the limb and on degenerate rays (both entry points; tests/test_gpu_thomson_seams.py):
+ *     |x_j| == solar_radius by bits, or less: the sample is inside the Sun, I_tot = I_P = 0 for it (and no gradient through
+ *     pixel_b); it still counts in pixel_density, the two distances and weights.  |x_j| > solar_radius by any amount: the
+ *     limb values (I_P -> u / 4 sin^2 chi, I_tot -> 2 ((1 - u) 4/3 + u 3/4) - I_P).  A sample at the origin is inside.
+ *     rays_d = (0, 0, 0): sin^2 chi = 0 / 0, every intensity and every ds is 0: pixel_b = pixel_density = distance_from_obs
+ *     = 0, distance_from_sun = |rays_o| (M > 0), weights as ever.  rays_o x rays_d = 0 (a ray through the centre): pB = 0.
+ *     z_j == z_{j-1}: ds_j = 0, the sample adds nothing to pixel_b / pixel_density.
  *   backward: any subset of g_pixel_b (N,2), g_pixel_density, g_distance_from_sun, g_distance_from_obs (N),
  *   g_weights (N,S) (NULL = absent) -> g_raw (N,S,C) (channel 1 written 0); g_absmax (4 bytes, may be NULL) receives
  *   the bit pattern of max |g_raw|, as in sunerf_emission_integral_bwd (the scale sunerf_mlp_dgrad takes); given, it is

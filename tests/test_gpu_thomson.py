@@ -157,10 +157,10 @@ def test_non_finite_inputs_propagate(ops):
 
 
 # ---- the fused NeRF pass --------------------------------------------------------------------------------------------------
-def _nerf_module(d_filter, n_coarse=48, n_fine=48, seed=0, cls=None):
+def _nerf_module(d_filter, n_coarse=48, n_fine=48, seed=0, cls=None, Rs_per_ds=1.0):
     from sunerf.rendering.thompson import ThompsonScattering
     torch.manual_seed(seed)
-    return (cls or ThompsonScattering)(Rs_per_ds=1.0, sampling_config={'type': 'stratified', 'n_samples': n_coarse, 'perturb': False},
+    return (cls or ThompsonScattering)(Rs_per_ds=Rs_per_ds, sampling_config={'type': 'stratified', 'n_samples': n_coarse, 'perturb': False},
                               hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': n_fine},
                               model_config={'d_filter': d_filter}).cuda()
 
@@ -173,12 +173,12 @@ def _rays(n, seed=0):
     return o, (d / d.norm(dim=1, keepdim=True)).contiguous(), torch.rand(n, 1, generator=gen)
 
 
-def _oracle_pass(params64, o, d, t, z):
+def _oracle_pass(params64, o, d, t, z, **constants):
     import sunerf_oracle as orc
     pts = orc.points_on_rays(o, d, z)
     q = torch.cat([pts, t.reshape(-1, 1, 1).expand(-1, z.shape[1], 1)], -1).double()
     raw = orc.mlp_forward(params64, q.reshape(-1, 4)).reshape(*z.shape, -1)
-    return tr.thomson_integral(raw, z, o, d, LN10)
+    return tr.thomson_integral(raw, z, o, d, LN10, **constants)
 
 
 def _params(model, requires_grad=False):
@@ -287,10 +287,10 @@ def test_fused_forward_equals_generic_path():
 
 
 # ---- field modules --------------------------------------------------------------------------------------------------------
-def _star_module():
+def _star_module(Rs_per_ds=1.0):
     from sunerf.model.stellar_model import SimpleStar
     from sunerf.rendering.thompson import ThompsonScattering
-    return ThompsonScattering(Rs_per_ds=1.0, model=SimpleStar, model_config={},
+    return ThompsonScattering(Rs_per_ds=Rs_per_ds, model=SimpleStar, model_config={},
                               sampling_config={'type': 'stratified', 'n_samples': 40, 'perturb': False},
                               hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 40}).cuda()
 
