@@ -61,6 +61,35 @@ def field(grid, frame_times, values, points, fill, Rs_per_ds=1.0, lon_mode='patc
     return raw, abs_sum, inside
 
 
+def node_terms(grid, frame_times, points, g_raw, Rs_per_ds=1.0, lon_mode='patch', time_mode='clamp'):
+    """What bounds one (frame, node) of the adjoint on its own, from this restatement's cells, intervals and weights: ``(A (T,
+    n0, n1, n2, C), n (T, n0, n1, n2) long)`` with ``A = sum_s |w_s| |g_s|`` over the inside samples whose (interval, cell)
+    touches the frame's node (``w_s``: the sample's float64 weight at that corner of its 16) and ``n`` their number.
+    ``points (M, 4)`` fp32, ``g_raw (M, C)``."""
+    u = grid_coordinates(grid, points, Rs_per_ds, lon_mode)
+    i0, i1, t, inside = locate(grid, u, lon_mode)
+    j, s, inside_t = locate_time(frame_times, points[:, 3], time_mode)
+    inside = inside & inside_t
+    n_frames = len(frame_times)
+    n0, n1, n2 = (int(a.shape[0]) for a in grid.axes)
+    g = g_raw.reshape(points.shape[0], -1).double().abs()
+    terms = torch.zeros(n_frames * n0 * n1 * n2, g.shape[1], dtype=torch.float64)
+    count = torch.zeros(n_frames * n0 * n1 * n2, dtype=torch.long)
+    for dt in (0, 1):
+        wt = s if dt else 1 - s
+        for d0 in (0, 1):
+            for d1 in (0, 1):
+                for d2 in (0, 1):
+                    idx = [(i1 if d else i0)[:, k] for k, d in enumerate((d0, d1, d2))]
+                    w = wt.clone()
+                    for k, d in enumerate((d0, d1, d2)):
+                        w = w * (t[:, k] if d else 1 - t[:, k])
+                    flat = ((((j + dt) * n0 + idx[0]) * n1 + idx[1]) * n2 + idx[2])[inside]
+                    terms.index_add_(0, flat, (w.abs()[:, None] * g)[inside])
+                    count.index_add_(0, flat, torch.ones_like(flat))
+    return terms.reshape(n_frames, n0, n1, n2, -1), count.reshape(n_frames, n0, n1, n2)
+
+
 def field_on_rays(grid, frame_times, values, rays_o, rays_d, z_vals, times, fill, Rs_per_ds=1.0, lon_mode='patch',
                   time_mode='clamp'):
     """:func:`field` at the samples of a ray batch at the rays' fp32 ``times (N, 1) | (N,)``: ``(raw (N, S, C), abs_sum (N, S, C),

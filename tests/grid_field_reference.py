@@ -118,6 +118,29 @@ def boundary_distance(grid, points, Rs_per_ds=1.0, lon_mode='patch'):
     return dist
 
 
+def node_terms(grid, points, g_raw, Rs_per_ds=1.0, lon_mode='patch'):
+    """What bounds one node of the adjoint on its own, from this restatement's cells and weights: ``(A (n0, n1, n2, C), n (n0,
+    n1, n2) long)`` with ``A = sum_s |w_s| |g_s|`` over the inside samples whose cell touches the node (``w_s``: the sample's
+    float64 corner weight at the node) and ``n`` their number.  ``points (M, >= 3)`` fp32, ``g_raw (M, C)``."""
+    u = grid_coordinates(grid, points, Rs_per_ds, lon_mode)
+    i0, i1, t, inside = locate(grid, u, lon_mode)
+    n0, n1, n2 = (int(a.shape[0]) for a in grid.axes)
+    g = g_raw.reshape(points.shape[0], -1).double().abs()
+    terms = torch.zeros(n0 * n1 * n2, g.shape[1], dtype=torch.float64)
+    count = torch.zeros(n0 * n1 * n2, dtype=torch.long)
+    for d0 in (0, 1):
+        for d1 in (0, 1):
+            for d2 in (0, 1):
+                idx = [(i1 if d else i0)[:, k] for k, d in enumerate((d0, d1, d2))]
+                w = torch.ones(points.shape[0], dtype=torch.float64)
+                for k, d in enumerate((d0, d1, d2)):
+                    w = w * (t[:, k] if d else 1 - t[:, k])
+                flat = ((idx[0] * n1 + idx[1]) * n2 + idx[2])[inside]
+                terms.index_add_(0, flat, (w.abs()[:, None] * g)[inside])
+                count.index_add_(0, flat, torch.ones_like(flat))
+    return terms.reshape(n0, n1, n2, -1), count.reshape(n0, n1, n2)
+
+
 def smoothness(grid, values, lon_mode='patch'):
     """Hand computation of ``GridField.smoothness()`` with Python loops over the axes' differences (float64)."""
     v = values.double()
