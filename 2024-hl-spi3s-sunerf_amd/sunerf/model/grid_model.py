@@ -17,6 +17,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from sunerf.model.model import absorption_scalars
 from sunerf_hip import dynamic_grid as _dg
 from sunerf_hip import grid_field as _gf
 from sunerf_hip import ops
@@ -46,10 +47,10 @@ def _initial_values(init, shape, d_output):
     raise ValueError(f'init has shape {tuple(init.shape)}; expected a number, {d_output} numbers or {tuple(shape)}')
 
 
-def _add_dt_head(field):
-    """The density-temperature head of ``MHDModel`` (mhd_model.py:11-24) on a grid field."""
-    field.log_absortpion = nn.ParameterDict([[str(w), torch.tensor(v, dtype=torch.float32)] for w, v in
-                                             zip(ops.AIA_WAVELENGTHS, (20.4, 20.2, 20.0, 19.8, 19.6, 19.4, 19.2))])
+def _add_dt_head(field, channels=None):
+    """The density-temperature head of ``MHDModel`` (mhd_model.py:11-24) on a grid field; ``channels``: see
+    ``sunerf.model.model.absorption_scalars``."""
+    field.log_absortpion = absorption_scalars(channels)
     field.volumetric_constant = nn.Parameter(torch.tensor(1.0, dtype=torch.float32, requires_grad=True))
     field.base_log_density = 0.0
     field.base_log_temperature = 0.0
@@ -188,11 +189,11 @@ class GridFieldDT(GridField):
     ``DensityTemperatureRadiativeTransfer(model=GridFieldDT)`` renders and fits it.  Default ``fill``: ``(ln 1e-10, log10
     1e-10)``, ``MHDModel``'s ``FILL_VALUE`` outside its cube."""
 
-    def __init__(self, grid, d_output=2, **kwargs):
+    def __init__(self, grid, d_output=2, channels=None, **kwargs):
         if d_output != 2:
             raise ValueError(f'a density-temperature grid holds (ln rho, log10 T): d_output must be 2, got {d_output!r}')
         super().__init__(grid, d_output=2, **kwargs)
-        _add_dt_head(self)
+        _add_dt_head(self, channels)
 
     def _default_fill(self):
         return (math.log(1e-10), -10.0)
@@ -306,11 +307,11 @@ class DynamicGridFieldDT(DynamicGridField):
     """:class:`DynamicGridField` of ``(ln rho, log10 T)`` with the density-temperature head exactly as :class:`GridFieldDT`
     carries it, so that ``DensityTemperatureRadiativeTransfer(model=DynamicGridFieldDT)`` renders and fits it."""
 
-    def __init__(self, grid, d_output=2, **kwargs):
+    def __init__(self, grid, d_output=2, channels=None, **kwargs):
         if d_output != 2:
             raise ValueError(f'a density-temperature grid holds (ln rho, log10 T): d_output must be 2, got {d_output!r}')
         super().__init__(grid, d_output=2, **kwargs)
-        _add_dt_head(self)
+        _add_dt_head(self, channels)
 
     def _default_fill(self):
         return (math.log(1e-10), -10.0)

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from sunerf.model.model import absorption_scalars
 from sunerf_hip import ops
 
 FILL_VALUE = 1e-10              # mhd_model.py:45 / :108: outside the grid, and the clamp of negative data (:64)
@@ -144,7 +145,7 @@ class MHDModel(nn.Module):
 
     time_dependent = True       # functional.dt_pass hands the rays' times to field_on_rays
 
-    def __init__(self, data_path, device=None, reader=None, max_frames=4):
+    def __init__(self, data_path, device=None, reader=None, max_frames=4, channels=None):
         super().__init__()
         device = torch.device("cuda" if torch.cuda.is_available() else "cpu") if device is None else device
         self.device = device
@@ -155,8 +156,7 @@ class MHDModel(nn.Module):
             raise FileNotFoundError(f'no MHD density frames: {os.path.join(data_path, "rho", "*.h5")} matches nothing')
         self.ffirst = frame_number(self.density_files[0])
         self.flast = frame_number(self.density_files[-1])
-        self.log_absortpion = nn.ParameterDict([[str(w), torch.tensor(v, dtype=torch.float32)] for w, v in
-                                                zip(ops.AIA_WAVELENGTHS, (20.4, 20.2, 20.0, 19.8, 19.6, 19.4, 19.2))])
+        self.log_absortpion = absorption_scalars(channels)
         self.volumetric_constant = nn.Parameter(torch.tensor(1.0, dtype=torch.float32, requires_grad=True))
         # NeRF_DT adds these to its raw output (model.py:182-183); the simulation is already physical
         self.base_log_density = 0.0

@@ -140,6 +140,24 @@ class EmissionModel(NeRF):
         super().__init__(d_input=4, d_output=2, **kwargs)
 
 
+FIELD_ABSORPTION = dict(zip(ops.AIA_WAVELENGTHS, (20.4, 20.2, 20.0, 19.8, 19.6, 19.4, 19.2)))     # mhd_model.py:11-24
+
+
+def absorption_scalars(channels=None, field=True):
+    """The ``log_absortpion`` ParameterDict of a density-temperature model: one scalar per channel, named ``str(code)``.
+
+    ``channels=None``: the seven AIA channels.  Otherwise a sequence of channel codes or a ``sunerf_hip.response.ResponseSet``
+    (one scalar per code, in that order).  Initial values: ``field=True`` (``SimpleStar``, ``MHDModel``, the grid fields) the
+    reference's per-AIA-channel values for an AIA code and 20.0 for any other; ``field=False`` (``NeRF_DT``) 1e-6 throughout."""
+    if channels is None:
+        codes = ops.AIA_WAVELENGTHS
+    else:
+        from sunerf_hip.response import as_response_set
+        codes = as_response_set(channels)[0]
+    return nn.ParameterDict([[str(c), torch.tensor(FIELD_ABSORPTION.get(c, 20.0) if field else 1.0e-6, dtype=torch.float32)]
+                             for c in codes])
+
+
 class NeRF_DT(NeRF):
     """model.py:136-187: the same MLP read as (log density, log temperature) with base offsets, plus the 7 per-channel
     absorption scalars and the volumetric constant (same parameter names: ``log_absortpion.<wl>``, ``volumetric_constant``).
@@ -147,17 +165,16 @@ class NeRF_DT(NeRF):
 
     def __init__(self, d_input: int = 4, d_output: int = 2, n_layers: int = 8, d_filter: int = 512,
                  skip: Tuple[int] = (), encoding='positional', base_log_temperature: float = 5.0,
-                 base_log_density: float = 10.0):
+                 base_log_density: float = 10.0, channels=None):
         super().__init__(d_input=d_input, d_output=d_output, n_layers=n_layers, d_filter=d_filter, skip=skip,
                          encoding=encoding)
         self.base_log_temperature = base_log_temperature
         self.base_log_density = base_log_density
-        self.log_absortpion = nn.ParameterDict([[str(w), torch.tensor(1.0e-6, dtype=torch.float32)]
-                                                for w in ops.AIA_WAVELENGTHS])
+        self.log_absortpion = absorption_scalars(channels, field=False)
         self.volumetric_constant = nn.Parameter(torch.tensor(1.0, dtype=torch.float32, requires_grad=True))
 
     def log_abs_vector(self) -> torch.Tensor:
-        return torch.stack([self.log_absortpion[str(w)] for w in ops.AIA_WAVELENGTHS])
+        return torch.stack(list(self.log_absortpion.values()))
 
     def forward(self, x: torch.Tensor):
         from sunerf.rendering.functional import mlp_points

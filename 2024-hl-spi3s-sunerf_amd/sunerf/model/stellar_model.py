@@ -8,6 +8,7 @@ units (h0 [Mm], T0 [K], R_s [solar radii], t_photosphere [K], rho_0 [cm^-3])."""
 import torch
 from torch import nn
 
+from sunerf.model.model import absorption_scalars
 from sunerf_hip import ops
 
 MM_PER_SOLAR_RADIUS = 695.7     # IAU 2015 nominal solar radius, astropy's u.solRad
@@ -24,15 +25,14 @@ def _value(q, unit_name, default_scale=1.0):
 class SimpleStar(nn.Module):
     """stellar_model.py:5-102."""
 
-    def __init__(self, h0=60., T0=1.4e6, R_s=1.02, t_photosphere=5777., rho_0=3.0e8):
+    def __init__(self, h0=60., T0=1.4e6, R_s=1.02, t_photosphere=5777., rho_0=3.0e8, channels=None):
         super().__init__()
         self.h0 = _value(h0, 'solRad', 1. / MM_PER_SOLAR_RADIUS)      # plain number: megametres, like the default 60*u.Mm
         self.T0 = _value(T0, 'K')
         self.R_s = _value(R_s, 'solRad')
         self.t_photosphere = _value(t_photosphere, 'K')
         self.rho_0 = _value(rho_0, 'cm-3')
-        self.log_absortpion = nn.ParameterDict([[str(w), torch.tensor(v, dtype=torch.float32)] for w, v in
-                                                zip(ops.AIA_WAVELENGTHS, (20.4, 20.2, 20.0, 19.8, 19.6, 19.4, 19.2))])
+        self.log_absortpion = absorption_scalars(channels)
         self.stellar_parameters = nn.ParameterDict([['Rs', torch.tensor(self.R_s, dtype=torch.float32)],
                                                     ['h0', torch.tensor(self.h0, dtype=torch.float32)],
                                                     ['T0', torch.tensor(self.T0, dtype=torch.float32)],

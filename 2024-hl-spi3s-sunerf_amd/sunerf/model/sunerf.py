@@ -258,7 +258,7 @@ class DensityTemperatureSuNeRFModule(BaseSuNeRFModule):
         self.lambda_regularization = lambda_regularization
         self.lambda_smoothness = lambda_smoothness
         self.lambda_temporal = lambda_temporal
-        rendering_kwargs = {k: kwargs.pop(k) for k in ('response_table', 'response_path') if k in kwargs}
+        rendering_kwargs = {k: kwargs.pop(k) for k in ('response_table', 'response_path', 'response_set') if k in kwargs}
         rendering = DensityTemperatureRadiativeTransfer(Rs_per_ds=Rs_per_ds, sampling_config=sampling_config,
                                                         hierarchical_sampling_config=hierarchical_sampling_config,
                                                         model_config=model_config, model=model,

@@ -6,6 +6,7 @@ from sunerf.rendering.base_tracing import SuNeRFRendering, field_on_query_points
 from sunerf.rendering.functional import _field_raw, dt_pass, dt_raw2outputs
 from sunerf_hip import ops
 from sunerf_hip.genx import CHANNELS, read_aia_temp_resp
+from sunerf_hip.response import ResponseSet
 
 
 def _tensors_inside(obj, depth=3):
@@ -44,16 +45,26 @@ def _tables_from_interpolators(response):
 class DensityTemperatureRadiativeTransfer(SuNeRFRendering):
     """density_temperature.py:78-274.  Same constructor; the AIA response table is read from
     ``sunerf/data/aia_temp_resp.genx`` relative to the working directory exactly like the reference (:131) unless
-    ``response_table=(logte [7,101], tresp [7,101])`` is passed."""
+    ``response_table=(logte [7,101], tresp [7,101])`` is passed.
+
+    ``response_set`` (a ``sunerf_hip.response.ResponseSet``): render against that set's channels instead of the AIA table --
+    any instrument, any number of channels up to 64, each on its own log T grid.  The rays' ``wavelengths`` rows then carry the
+    set's codes, and the models need one ``log_absortpion`` scalar per code (``model_config={'channels': response_set}``).  The
+    AIA table is neither read nor held then.  Without it every call is what it was."""
 
     def __init__(self, model_config=None, device=None, aia_exp_time=2.9, pixel_intensity_factor=1e10,
-                 response_table=None, response_path="sunerf/data/aia_temp_resp.genx", **kwargs):
+                 response_table=None, response_path="sunerf/data/aia_temp_resp.genx", response_set=None, **kwargs):
         model_config = {} if model_config is None else model_config
+        if response_set is not None and not isinstance(response_set, ResponseSet):
+            raise TypeError('response_set must be a sunerf_hip.response.ResponseSet')
         kwargs.setdefault('model', NeRF_DT)
         super().__init__(model_config=model_config, **kwargs)
+        self.response_set = response_set
         device = torch.device("cuda" if torch.cuda.is_available() else "cpu") if device is None else device
         self.device = device
         self.pixel_intensity_factor = pixel_intensity_factor
+        if response_set is not None:
+            return
         logte, tresp = read_aia_temp_resp(response_path) if response_table is None else response_table
         # density_temperature.py:137-146: response x exposure time, cast to fp32
         self.register_buffer('response_logte', torch.as_tensor(logte).float(), persistent=False)
@@ -66,6 +77,8 @@ class DensityTemperatureRadiativeTransfer(SuNeRFRendering):
         reference -- they are built through its public constructor exactly as the reference builds them, so that a state
         written here renders in the reference; elsewhere the file simply lacks them (and still loads here)."""
         st = self.__dict__.copy()
+        if st.get('response_set') is not None:      # no AIA interpolators to offer: such a state renders here only
+            return st
         try:
             from xitorch.interpolate import Interp1D
         except ImportError:
@@ -78,6 +91,9 @@ class DensityTemperatureRadiativeTransfer(SuNeRFRendering):
         """A state written by the REFERENCE has the interpolators but not this class's table buffers: take the table out of
         them, or read the file again like the constructor."""
         self.__dict__.update(state)
+        self.__dict__.setdefault('response_set', None)      # states written before response sets existed
+        if self.response_set is not None:
+            return
         if 'response_logte' in self._buffers and 'response_table' in self._buffers:
             return
         tables = _tables_from_interpolators(state['response']) if isinstance(state.get('response'), dict) else None
@@ -88,6 +104,17 @@ class DensityTemperatureRadiativeTransfer(SuNeRFRendering):
         self.register_buffer('response_logte', tables[0].to(where), persistent=False)
         self.register_buffer('response_table', tables[1].to(where), persistent=False)
 
+    def _tables(self):
+        """What the DT passes interpolate in: the response set, or the AIA pair of buffers."""
+        if self.response_set is not None:
+            return self.response_set
+        return (self.response_logte, self.response_table)
+
+    def _table_device(self):
+        if self.response_set is None:
+            return self.response_logte.device
+        return next((p.device for p in self.parameters()), torch.device('cpu'))
+
     def regularization(self, distance, regularizing_quantity):
         return torch.relu(distance[:, :] - 1.25 / self.Rs_per_ds) * torch.relu(regularizing_quantity)
 
@@ -97,7 +124,7 @@ class DensityTemperatureRadiativeTransfer(SuNeRFRendering):
             raise ValueError('DensityTemperatureRadiativeTransfer needs the wavelengths of every ray')
         if self._hooks_replaced(DensityTemperatureRadiativeTransfer):   # a subclass with its own raw2outputs / _render / regularization
             return SuNeRFRendering.forward(self, rays_o, rays_d, times, wavelengths)
-        tables = (self.response_logte, self.response_table)
+        tables = self._tables()
         reg_radius = 1.25 / self.Rs_per_ds
         z_vals = self.sampler.z_vals(rays_o, rays_d)
         coarse = dt_pass(self.coarse_model, tables, self.pixel_intensity_factor, rays_o, rays_d, times, z_vals, wavelengths,
@@ -113,8 +140,13 @@ class DensityTemperatureRadiativeTransfer(SuNeRFRendering):
     def dem_nodes(self, logt_nodes=None):
         """The log T nodes of a DEM as a float32 device vector: ``logt_nodes``, or the response table's own grid."""
         if logt_nodes is None:
-            return self.response_logte[0].contiguous()
-        return torch.as_tensor(logt_nodes, dtype=torch.float32).to(self.response_logte.device).contiguous()
+            if self.response_set is None:
+                return self.response_logte[0].contiguous()
+            grid = self.response_set.shared_grid()
+            if grid is None:
+                raise ValueError('the channels of the response set have different log T grids: pass logt_nodes')
+            logt_nodes = grid
+        return torch.as_tensor(logt_nodes, dtype=torch.float32).to(self._table_device()).contiguous()
 
     def attenuation_scalar(self, attenuation_wavelength=None):
         """The fine model's ``log_absortpion`` scalar of channel ``attenuation_wavelength`` as a one-element device tensor
@@ -157,10 +189,11 @@ class DensityTemperatureRadiativeTransfer(SuNeRFRendering):
             raise TypeError('render_dem needs the built-in density-temperature hooks and a NeRF_DT or field model')
         nodes = self.dem_nodes(logt_nodes)
         log_abs = self.attenuation_scalar(attenuation_wavelength)
-        tables = (self.response_logte, self.response_table)
+        tables = self._tables()
         z_vals = self.sampler.z_vals(rays_o, rays_d)
         # the coarse weights = relu(inf0) / sum do not depend on the channel: one present channel keeps the pass cheap
-        wl = torch.full((z_vals.shape[0], 1), float(ops.AIA_WAVELENGTHS[2]), dtype=torch.float32, device=z_vals.device)
+        cheap = ops.AIA_WAVELENGTHS[2] if self.response_set is None else self.response_set.codes[0]
+        wl = torch.full((z_vals.shape[0], 1), float(cheap), dtype=torch.float32, device=z_vals.device)
         coarse = dt_pass(self.coarse_model, tables, self.pixel_intensity_factor, rays_o, rays_d, times, z_vals, wl,
                          1.25 / self.Rs_per_ds, want_epilogues=False)
         _, z_comb = self.sampler_hierarchical.resample(z_vals, coarse['weights'])
@@ -175,6 +208,8 @@ class DensityTemperatureRadiativeTransfer(SuNeRFRendering):
     def channel_indices(self, wavelengths=None):
         """Rows of the response table for ``wavelengths`` (default: all of ``ops.AIA_WAVELENGTHS``); an unknown channel raises
         like :meth:`attenuation_scalar`."""
+        if self.response_set is not None:      # by code
+            return self.response_set.index_of(self.response_set.codes if wavelengths is None else list(wavelengths))
         rows = []
         for w in (ops.AIA_WAVELENGTHS if wavelengths is None else wavelengths):
             try:
@@ -195,7 +230,10 @@ class DensityTemperatureRadiativeTransfer(SuNeRFRendering):
         from sunerf_hip.dem_inversion import response_on_nodes
         rows = self.channel_indices(wavelengths)
         nodes = self.dem_nodes(logt_nodes)
-        resp = response_on_nodes(self.response_logte[rows], self.response_table[rows], nodes)
+        if self.response_set is not None:
+            resp = self.response_set.on_nodes(nodes)[rows].to(nodes.device)
+        else:
+            resp = response_on_nodes(self.response_logte[rows], self.response_table[rows], nodes)
         vol_c = self.fine_model.volumetric_constant.detach().to(device=resp.device, dtype=torch.float64)
         return resp * (vol_c * float(self.pixel_intensity_factor))
 
@@ -224,5 +262,5 @@ class DensityTemperatureRadiativeTransfer(SuNeRFRendering):
         """density_temperature.py:192-271 on the state ``NeRF_DT.forward`` returns (``inferences`` (N, S, 2) with the base
         offsets added, the ``log_absortpion`` ParameterDict, ``volumetric_constant``): ``{'image' (N,W), 'weights',
         'regularizing_quantity'}``; differentiable through ``image`` (sunerf_dt_integral_fwd / _bwd)."""
-        return dt_raw2outputs((self.response_logte, self.response_table), self.pixel_intensity_factor, inferences, log_abs,
+        return dt_raw2outputs(self._tables(), self.pixel_intensity_factor, inferences, log_abs,
                               vol_c, z_vals, rays_d, wavelengths)

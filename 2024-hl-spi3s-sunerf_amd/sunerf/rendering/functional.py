@@ -2,6 +2,7 @@
 import torch
 
 from sunerf_hip import ops
+from sunerf_hip.response import ResponseSet
 from sunerf_hip.train import bucket_of
 
 
@@ -306,6 +307,19 @@ def emission_raw2outputs(raw, z_vals, rays_d):
     return {'image': image, 'weights': weights, 'regularizing_quantity': absorption}
 
 
+def _absorption_scalars(log_abs, tables):
+    """The ``log_absortpion`` scalars the integral takes, in its channel order.  ``tables`` is the AIA pair ``(logte [7,101],
+    response [7,101])`` -- the seven AIA names, the kernels of sunerf_hip.h -- or a ``ResponseSet``: one scalar per channel of the
+    set, by its code, for the kernels of sunerf_hip_response.h."""
+    if isinstance(tables, ResponseSet):
+        missing = [k for k in tables.keys if k not in log_abs]
+        if missing:
+            raise ValueError(f'the model has no log_absortpion scalar for the response set\'s channels {", ".join(missing)} '
+                           f'(it has {", ".join(log_abs.keys())}): build it with channels=<the set or its codes>')
+        return [log_abs[k] for k in tables.keys]
+    return [log_abs[str(w)] for w in ops.AIA_WAVELENGTHS]
+
+
 class _DtIntegral(torch.autograd.Function):
     """``DensityTemperatureRadiativeTransfer.raw2outputs`` (density_temperature.py:192-271) on given inferences (base offsets
     already added, as ``NeRF_DT.forward`` returns them).  Differentiable through all three outputs -- ``image``, ``weights``
@@ -317,8 +331,12 @@ class _DtIntegral(torch.autograd.Function):
     def forward(ctx, tables, pixel_factor, inferences, z_vals, rays_d, wavelengths, vol_c, *la):
         la_vec = torch.stack([p.detach() for p in la])
         zeros = torch.zeros_like(rays_d)
-        out = ops.dt_integral_fwd(inferences.detach(), z_vals, zeros, rays_d, wavelengths, tables[0], tables[1], la_vec, vol_c, 0.0, 0.0,
-                                  pixel_factor, 0.0)
+        if isinstance(tables, ResponseSet):
+            out = ops.dt_response_fwd(inferences.detach(), z_vals, zeros, rays_d, wavelengths, tables, la_vec, vol_c, 0.0, 0.0,
+                                      pixel_factor, 0.0)
+        else:
+            out = ops.dt_integral_fwd(inferences.detach(), z_vals, zeros, rays_d, wavelengths, tables[0], tables[1], la_vec, vol_c,
+                                      0.0, 0.0, pixel_factor, 0.0)
         ctx.tables, ctx.pixel_factor = tables, pixel_factor
         ctx.save_for_backward(inferences.detach(), z_vals, rays_d, wavelengths, la_vec, vol_c.detach())
         ctx.set_materialize_grads(False)
@@ -331,20 +349,25 @@ class _DtIntegral(torch.autograd.Function):
             return (None,) * (7 + la_vec.shape[0])
         if g_image is None:
             g_image = torch.zeros(z_vals.shape[0], wavelengths.shape[1], dtype=torch.float32, device=z_vals.device)
-        g_raw, g_la, g_vc, _ = ops.dt_integral_bwd_full(inferences, z_vals, torch.zeros_like(rays_d), rays_d, wavelengths,
-                                                        ctx.tables[0], ctx.tables[1], la_vec, vol_c, 0.0, 0.0, ctx.pixel_factor,
-                                                        0.0, g_image.contiguous(), None,
-                                                        None if g_weights is None else g_weights.contiguous(),
-                                                        None if g_q is None else g_q.contiguous())
+        entry, tables = ((ops.dt_response_bwd_full, (ctx.tables,)) if isinstance(ctx.tables, ResponseSet) else
+                         (ops.dt_integral_bwd_full, (ctx.tables[0], ctx.tables[1])))
+        g_raw, g_la, g_vc, _ = entry(inferences, z_vals, torch.zeros_like(rays_d), rays_d, wavelengths, *tables, la_vec, vol_c,
+                                     0.0, 0.0, ctx.pixel_factor, 0.0, g_image.contiguous(), None,
+                                     None if g_weights is None else g_weights.contiguous(),
+                                     None if g_q is None else g_q.contiguous())
         return (None, None, g_raw, None, None, None, g_vc.reshape(())) + tuple(g_la[i] for i in range(g_la.shape[0]))
 
 
 def dt_raw2outputs(tables, pixel_factor, inferences, log_abs, vol_c, z_vals, rays_d, wavelengths):
-    la = [log_abs[str(w)] for w in ops.AIA_WAVELENGTHS]
+    la = _absorption_scalars(log_abs, tables)
     if not torch.is_grad_enabled() or not any(t.requires_grad for t in [inferences, vol_c] + la):
         la_vec = torch.stack([p.detach() for p in la])
-        out = ops.dt_integral_fwd(inferences.detach(), z_vals, torch.zeros_like(rays_d), rays_d, wavelengths, tables[0], tables[1],
-                                  la_vec, vol_c, 0.0, 0.0, pixel_factor, 0.0)
+        if isinstance(tables, ResponseSet):
+            out = ops.dt_response_fwd(inferences.detach(), z_vals, torch.zeros_like(rays_d), rays_d, wavelengths, tables, la_vec,
+                                      vol_c, 0.0, 0.0, pixel_factor, 0.0)
+        else:
+            out = ops.dt_integral_fwd(inferences.detach(), z_vals, torch.zeros_like(rays_d), rays_d, wavelengths, tables[0],
+                                      tables[1], la_vec, vol_c, 0.0, 0.0, pixel_factor, 0.0)
         return {'image': out['image'], 'weights': out['weights'], 'regularizing_quantity': out['reg_q']}
     image, weights, reg_q = _DtIntegral.apply(tables, pixel_factor, inferences, z_vals, rays_d, wavelengths, vol_c, *la)
     return {'image': image, 'weights': weights, 'regularizing_quantity': reg_q}
@@ -352,7 +375,10 @@ def dt_raw2outputs(tables, pixel_factor, inferences, log_abs, vol_c, z_vals, ray
 
 def _dt_forward(model, tables, pixel_factor, raw, rays_o, rays_d, z_vals, wavelengths, reg_radius, want_epilogues, la, vol_c):
     """The DT integral of ``raw`` (N, S, 2), ``model``'s raw output or field, with its base offsets: the forward of every DT
-    pass, with or without autograd.  ``la``: the (7,) stacked absorption scalars."""
+    pass, with or without autograd.  ``la``: the stacked absorption scalars, (7,) or one per channel of a ``ResponseSet``."""
+    if isinstance(tables, ResponseSet):
+        return ops.dt_response_fwd(raw, z_vals, rays_o, rays_d, wavelengths, tables, la, vol_c, model.base_log_density,
+                                   model.base_log_temperature, pixel_factor, reg_radius, want_epilogues=want_epilogues)
     return ops.dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, tables[0], tables[1], la, vol_c,
                                model.base_log_density, model.base_log_temperature, pixel_factor, reg_radius,
                                want_epilogues=want_epilogues)
@@ -366,6 +392,9 @@ def _dt_backward(ctx, saved, g_image, g_reg):
     tables, pixel_factor, reg_radius, base_d, base_t = ctx.dt
     if g_image is None:
         g_image = torch.zeros(z_vals.shape[0], wavelengths.shape[1], dtype=torch.float32, device=z_vals.device)
+    if isinstance(tables, ResponseSet):
+        return ops.dt_response_bwd(raw, z_vals, rays_o, rays_d, wavelengths, tables, la, vol_c, base_d, base_t, pixel_factor,
+                                   reg_radius, g_image.contiguous(), g_reg)
     return ops.dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, tables[0], tables[1], la, vol_c, base_d, base_t,
                                pixel_factor, reg_radius, g_image.contiguous(), g_reg)
 
@@ -378,7 +407,7 @@ class _DtPass(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, tables, pixel_factor, rays_o, rays_d, times, z_vals, wavelengths, reg_radius, want_epilogues,
                 vol_c, *params):
-        n_la = len(ops.AIA_WAVELENGTHS)
+        n_la = len(tables) if isinstance(tables, ResponseSet) else len(ops.AIA_WAVELENGTHS)
         la = torch.stack([p.detach() for p in params[:n_la]])
         training = any(ctx.needs_input_grad[10:])
         ctx.set_materialize_grads(False)
@@ -417,7 +446,7 @@ def _field_raw(model, rays_o, rays_d, z_vals, times):
 
 def dt_pass(model, tables, pixel_factor, rays_o, rays_d, times, z_vals, wavelengths, reg_radius, want_epilogues):
     """Dict of one DT pass' outputs (image (N,W), weights, regularizing_quantity[, maps, regularization])."""
-    la = [model.log_absortpion[str(w)] for w in ops.AIA_WAVELENGTHS]
+    la = _absorption_scalars(model.log_absortpion, tables)
     if hasattr(model, 'field_on_rays'):
         # analytic field (SimpleStar) or simulation cube (MHDModel) instead of an MLP: same integral (stellar_model.py,
         # mhd_model.py, image_render.py:244-269)

@@ -186,6 +186,22 @@ _EXT_SIGNATURES = {
 EXTENSION_SYMBOLS = tuple(_EXT_SIGNATURES)
 EXT_ABI_VERSION = 1
 
+# The response-set table (include/sunerf_hip_response.h): the DT integral against any instrument's channels.  A third table
+# beside the two above, which stay as they are and keep their versions.
+_RS_HEAD = [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void, c_f32p, c_f32p, c_f32p,
+            c_f32p, c_f32p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int64, ctypes.c_int]
+_RESPONSE_SIGNATURES = {
+    'sunerf_response_abi_version': (ctypes.c_int, []),
+    'sunerf_dt_response_bwd_lds_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'sunerf_dt_response_fwd': (ctypes.c_int, _RS_HEAD + [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_void]),
+    'sunerf_dt_response_bwd': (ctypes.c_int, _RS_HEAD + [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_void, c_void]),
+    'sunerf_dt_response_bwd_full': (ctypes.c_int, _RS_HEAD + [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_void,
+                                                              c_void]),
+}
+
+RESPONSE_SYMBOLS = tuple(_RESPONSE_SIGNATURES)
+RESPONSE_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -212,6 +228,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_ext_abi_version() != EXT_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so extension ABI version mismatch')
+        for name, (res, args) in _RESPONSE_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_response_abi_version() != RESPONSE_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so response-set ABI version mismatch')
         _lib = lib
     return _lib
 

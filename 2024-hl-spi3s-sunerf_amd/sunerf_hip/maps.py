@@ -146,7 +146,7 @@ def _tile(rendering, rays_o, rays_d, times, z, wl, kind: str, profiles: bool) ->
         res.update(column_stats(out['raw'], z[0], rays_d, scale, profiles))
         return res
     if kind == 'dt':
-        tables = (rendering.response_logte, rendering.response_table)
+        tables = rendering._tables()      # the AIA pair, or the rendering's response set
         out = F.dt_pass(model, tables, rendering.pixel_intensity_factor, rays_o, rays_d, times, z, wl, 1.25 / rendering.Rs_per_ds,
                         want_epilogues=True)
         res = {'image': out['image'], 'height_map': out['height_map'] * scale, 'absorption_map': out['absorption_map']}

@@ -1061,6 +1061,88 @@ def dt_integral_bwd_full(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, t
                             [('g_reg', g_reg), ('g_weights', g_weights), ('g_reg_q', g_reg_q)])
 
 
+# ---- the same integral against a response set (include/sunerf_hip_response.h, sunerf_hip/response.py) ------------------------
+def _response_set_args(response_set, dev):
+    """The C ABI's ``n_channels, n_nodes_total, offsets, codes, logt, resp`` of a ``ResponseSet`` on ``dev``."""
+    offsets, codes, logt, resp = response_set.to(dev)
+    return (response_set.n_channels, response_set.n_nodes, _ptr(offsets), _ptr(codes), _ptr(logt), _ptr(resp))
+
+
+def dt_response_bwd_lds_bytes(n_samples: int, n_wavelengths: int, n_nodes_total: int) -> int:
+    """LDS bytes the response-set backward needs: a shape above 160 KiB is refused (``response_set.fits`` says which fit)."""
+    return int(_l.load().sunerf_dt_response_bwd_lds_bytes(int(n_samples), int(n_wavelengths), int(n_nodes_total)))
+
+
+def dt_response_fwd(raw, z_vals, rays_o, rays_d, wavelengths, response_set, log_abs, vol_c, base_log_density,
+                    base_log_temperature, pixel_intensity_factor, reg_radius, want_epilogues=False):
+    """:func:`dt_integral_fwd` against ``response_set`` (a ``sunerf_hip.response.ResponseSet``): ``wavelengths`` (N, W <= 8) holds
+    the set's channel codes, ``log_abs`` is (M,) in set order."""
+    n, s = z_vals.shape
+    dev = z_vals.device
+    w = wavelengths.shape[1]
+    m = response_set.n_channels
+    raw = _dev(raw, 'raw', (n, s, 2)); z_vals = _dev(z_vals, 'z_vals', (n, s))
+    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3))
+    wavelengths = _dev(wavelengths.to(torch.float32), 'wavelengths', (n, w))
+    log_abs = _dev(log_abs.detach(), 'log_abs', (m,)); vol_c = _dev(vol_c.detach().reshape(1), 'vol_c', (1,))
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {'image': torch.empty(n, w, **f32), 'weights': torch.empty(n, s, **f32), 'reg_q': torch.empty(n, s, **f32)}
+    hm = am = reg = None
+    if want_epilogues:
+        hm, am, reg = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, s, **f32)
+    _l.call(dev, 'sunerf_dt_response_fwd', _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(wavelengths), w,
+            *_response_set_args(response_set, dev), _ptr(log_abs), _ptr(vol_c), float(base_log_density),
+            float(base_log_temperature), float(pixel_intensity_factor), float(reg_radius), n, s, _ptr(out['image']),
+            _ptr(out['weights']), _ptr(out['reg_q']), _ptr(hm), _ptr(am), _ptr(reg), _stream(dev))
+    if want_epilogues:
+        out.update(height_map=hm, absorption_map=am, regularization=reg)
+    return out
+
+
+def _dt_response_bwd(entry, raw, z_vals, rays_o, rays_d, wavelengths, response_set, log_abs, vol_c, base_log_density,
+                     base_log_temperature, pixel_intensity_factor, reg_radius, g_image, per_sample):
+    """:func:`_dt_integral_bwd` for the response-set entry points -> (g_raw, g_log_abs (M,), g_vol_c, absmax)."""
+    n, s = z_vals.shape
+    dev = z_vals.device
+    w = wavelengths.shape[1]
+    m = response_set.n_channels
+    raw = _dev(raw, 'raw', (n, s, 2)); z_vals = _dev(z_vals, 'z_vals', (n, s))
+    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3))
+    wavelengths = _dev(wavelengths.to(torch.float32), 'wavelengths', (n, w))
+    log_abs = _dev(log_abs.detach(), 'log_abs', (m,)); vol_c = _dev(vol_c.detach().reshape(1), 'vol_c', (1,))
+    g_image = _dev(g_image, 'g_image', (n, w))
+    per_sample = [None if g is None else _dev(g, name, (n, s)) for name, g in per_sample]
+    if n > 0 and dt_response_bwd_lds_bytes(s, w, response_set.n_nodes) > 160 * 1024:
+        raise ValueError(f'{entry}: {s} samples x {w} columns with {response_set.n_nodes} response nodes need more than the 160 KiB '
+                         f'of LDS of a compute unit (at most {response_set.max_samples(w)} samples at this width)')
+    f32 = dict(dtype=torch.float32, device=dev)
+    g_raw = torch.empty(n, s, 2, **f32)
+    small = torch.empty(m + 2, **f32)
+    g_la, g_vc, absmax = small[:m], small[m:m + 1], small[m + 1:m + 2].view(torch.int32)
+    _l.call(dev, entry, _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(wavelengths), w,
+            *_response_set_args(response_set, dev), _ptr(log_abs), _ptr(vol_c), float(base_log_density),
+            float(base_log_temperature), float(pixel_intensity_factor), float(reg_radius), n, s, _ptr(g_image),
+            *[_ptr(g) for g in per_sample], _ptr(g_raw), _ptr(g_la), _ptr(g_vc), _ptr(absmax), _stream(dev))
+    return g_raw, g_la, g_vc, absmax
+
+
+def dt_response_bwd(raw, z_vals, rays_o, rays_d, wavelengths, response_set, log_abs, vol_c, base_log_density,
+                    base_log_temperature, pixel_intensity_factor, reg_radius, g_image, g_reg):
+    """:func:`dt_integral_bwd` against ``response_set`` -> (g_raw (N,S,2), g_log_abs (M,), g_vol_c (1,), absmax), the scalar
+    gradients adjacent views of one buffer as there."""
+    return _dt_response_bwd('sunerf_dt_response_bwd', raw, z_vals, rays_o, rays_d, wavelengths, response_set, log_abs, vol_c,
+                            base_log_density, base_log_temperature, pixel_intensity_factor, reg_radius, g_image,
+                            [('g_reg', g_reg)])
+
+
+def dt_response_bwd_full(raw, z_vals, rays_o, rays_d, wavelengths, response_set, log_abs, vol_c, base_log_density,
+                         base_log_temperature, pixel_intensity_factor, reg_radius, g_image, g_reg, g_weights, g_reg_q):
+    """:func:`dt_integral_bwd_full` against ``response_set``."""
+    return _dt_response_bwd('sunerf_dt_response_bwd_full', raw, z_vals, rays_o, rays_d, wavelengths, response_set, log_abs,
+                            vol_c, base_log_density, base_log_temperature, pixel_intensity_factor, reg_radius, g_image,
+                            [('g_reg', g_reg), ('g_weights', g_weights), ('g_reg_q', g_reg_q)])
+
+
 def simple_star_field_dev(rays_o, rays_d, z_vals, params, t_photosphere: float):
     """:func:`simple_star_field` with the stellar parameters read on the device: ``params`` (4,) fp32 = (Rs, h0, T0, rho_0),
     the order of ``SimpleStar.stellar_parameters`` -> raw (N, S, 2) = (ln rho, log10 T), bit-identical to the host-float form."""

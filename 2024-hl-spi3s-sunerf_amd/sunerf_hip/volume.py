@@ -468,6 +468,12 @@ def sample_volume(field, grid: _Grid, time, wavelengths=None, quantities: Option
     if not per_channel and wavelengths is not None:
         raise ValueError(f'sample_volume: the quantities {quantities} take no wavelengths')
     if per_channel:
+        heads = getattr(net, 'log_absortpion', None)
+        if getattr(rendering, 'response_set', None) is not None or \
+                (heads is not None and tuple(heads.keys()) != tuple(str(w) for w in AIA_WAVELENGTHS)):
+            raise ValueError('sample_volume: per-channel emissivity / absorption exist for the seven AIA channels only; this model '
+                             'has the channels of a response set (' + ', '.join(heads.keys() if heads is not None else ()) +
+                             '): ask for density / log_temperature')
         wl_host = torch.as_tensor(np.asarray(wavelengths.detach().cpu() if isinstance(wavelengths, torch.Tensor) else wavelengths,
                                              dtype=np.float32)).reshape(-1)
         if not 1 <= wl_host.shape[0] <= len(AIA_WAVELENGTHS):
