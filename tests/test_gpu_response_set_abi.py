@@ -21,19 +21,23 @@ pytestmark = pytest.mark.gpu
 # (rays, samples, columns, epilogues / per-sample gradients): one ray, a partial group, a group and one ray, and a ragged
 # three-group batch (8 + 8 + 5 rays) whose sample count is no multiple of the 32-sample chunk
 SHAPES = [(1, 33, 1, 0), (7, 31, 3, 1), (9, 65, 8, 1), (21, 37, 8, 0)]
+# the same on the ragged 64-channel, 4096-node set ``R64r`` of tests/response_set_cases.py (a fifth entry names the set): the
+# extents the header gives at its limits -- offsets[65], codes[64], logt / resp[4096], log_abs[64], g_log_abs[64]
+SET_SHAPES = [(9, 33, 8, 1, 'R64r'), (21, 37, 3, 0, 'R64r')]
 TILES = 'dt_response_set.hip RS_THREADS 256: 8 rays per workgroup, 32 lanes per ray, 32 samples per chunk'
 # the scalar gradients are added with float atomics per ray and per workgroup: from three terms on the order is free
 ORDERED_RAYS = 2
 
 
 @functools.lru_cache(maxsize=None)
-def _case(n, s, w):
-    return rc.make_case(n, s, w, 'nerf_dt', 1000 * n + s)
+def _case(n, s, w, set_name=None):
+    return rc.make_case(n, s, w, 'nerf_dt', 1000 * n + s, channels=list(rc.set_channels(set_name)) if set_name else None)
 
 
-def _inputs(c, n, s, w):
-    e = _case(n, s, w)
-    rset = rc.response_set()
+def _inputs(c, n, s, w, set_name=None):
+    """The input buffers of a call on the 11-channel set, or on the set ``set_name`` of ``response_set_cases.SET_NODES``."""
+    e = _case(n, s, w, set_name)
+    rset = rc.set_of(set_name) if set_name else rc.response_set()
     b = dict(raw=c.IN('raw', e['raw']), z=c.IN('z_vals', e['z']), o=c.IN('rays_o', e['o']), d=c.IN('rays_d', e['d']),
              wl=c.IN('wavelengths', e['wl']), off=c.IN('offsets', torch.from_numpy(rset.offsets)),
              codes=c.IN('codes', torch.tensor(rset.codes, dtype=F32)),
@@ -51,9 +55,9 @@ def _wrapper_args(b, e, rset, n, s, w):
 
 
 def response_fwd(shape, device):
-    n, s, w, epi = shape
+    n, s, w, epi = shape[:4]
     c = Ctx(device)
-    e, rset, b, head = _inputs(c, n, s, w)
+    e, rset, b, head = _inputs(c, n, s, w, *shape[4:])
     image, weights, reg_q = c.OUT('image', F32, n * w), c.OUT('weights', F32, n * s), c.OUT('reg_q', F32, n * s)
     if epi:
         hm, am, reg = c.OUT('height_map', F32, n), c.OUT('absorption_map', F32, n), c.OUT('regularization', F32, n * s)
@@ -69,9 +73,9 @@ def response_fwd(shape, device):
 
 
 def _response_bwd(name, shape, device, full):
-    n, s, w, with_reg = shape
+    n, s, w, with_reg = shape[:4]
     c = Ctx(device)
-    e, rset, b, head = _inputs(c, n, s, w)
+    e, rset, b, head = _inputs(c, n, s, w, *shape[4:])
     m = rset.n_channels
     gen = ac._gen(n * 31 + s)
     g_image = c.IN('g_image', e['g_image'].float())
@@ -110,9 +114,9 @@ def response_bwd_full(shape, device):
     return _response_bwd('sunerf_dt_response_bwd_full', shape, device, True)
 
 
-RESPONSE_CASES = {'sunerf_dt_response_fwd': (response_fwd, tuple(SHAPES)),
-                  'sunerf_dt_response_bwd': (response_bwd, tuple(SHAPES)),
-                  'sunerf_dt_response_bwd_full': (response_bwd_full, tuple(SHAPES))}
+RESPONSE_CASES = {'sunerf_dt_response_fwd': (response_fwd, tuple(SHAPES + SET_SHAPES)),
+                  'sunerf_dt_response_bwd': (response_bwd, tuple(SHAPES + SET_SHAPES)),
+                  'sunerf_dt_response_bwd_full': (response_bwd_full, tuple(SHAPES + SET_SHAPES))}
 PAIRS = [(name, shape) for name, (_, shapes) in RESPONSE_CASES.items() for shape in shapes]
 
 

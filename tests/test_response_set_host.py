@@ -2,8 +2,9 @@
 ``concat``, ``index_of``, ``check_codes``, pickle and ``.npz`` round trips, ``aia()`` against the rendering's buffers), the third
 entry-point table (declared, bound, kept out of the first two, its argument checks in their documented order), ``channels=`` of
 the five density-temperature field classes, and the conditions the cases of tests/response_set_cases.py must meet so that
-tests/test_gpu_response_set.py cannot pass vacuously."""
+tests/test_gpu_response_set.py and tests/test_gpu_response_set_sizes.py cannot pass vacuously."""
 import ctypes
+import hashlib
 import math
 import os
 import pickle
@@ -445,9 +446,236 @@ def test_abi_case_table_of_the_gpu_test():
     from sunerf_hip import lib as binding
     assert set(abi.RESPONSE_CASES) | {'sunerf_response_abi_version', 'sunerf_dt_response_bwd_lds_bytes'} == set(binding.RESPONSE_SYMBOLS)
     assert {s[0] for s in abi.SHAPES} == {1, 7, 9, 21} and 21 % 8 and 21 > 16
+    assert abi.SET_SHAPES == [(9, 33, 8, 1, 'R64r'), (21, 37, 3, 0, 'R64r')]
     for name, (builder, shapes) in abi.RESPONSE_CASES.items():
         argtypes = binding._RESPONSE_SIGNATURES[name][1]
+        assert shapes == tuple(abi.SHAPES + abi.SET_SHAPES)
         for shape in shapes:
             case = builder(shape, 'cpu')
             assert len(case.args) == len(argtypes), (name, len(case.args), len(argtypes))
+            sizes = {b.name: b.numel for b in case.arena.buffers}
+            if len(shape) == 5:             # the header's extents at their limits
+                assert (sizes['offsets'], sizes['codes'], sizes['logt'], sizes['resp'], sizes['log_abs']) == (65, 64, 4096, 4096, 64)
+                assert case.args[6:8] == [64, 4096] and sizes.get('g_log_abs', 64) == 64
+            else:
+                assert (sizes['offsets'], sizes['codes'], sizes['logt'], sizes['log_abs']) == (12, 11, 1005, 11)
             assert case.args[18] == shape[0] and case.args[19] == shape[1] and case.empty == {18: 0}
+
+
+# ---- the sets at the header's limits and their cases (tests/test_gpu_response_set_sizes.py) ------------------------------------
+def test_existing_cases_are_unchanged_by_the_case_maker_taking_a_set():
+    """``make_case`` without ``channels=`` draws what it drew before it took a set: the digest of one case, taken before."""
+    c = rc.group1_case(9, 33, 8, 'generic')
+    h = hashlib.sha256()
+    for k in sorted(c):
+        h.update(k.encode())
+        h.update(c[k].numpy().tobytes() if torch.is_tensor(c[k]) else repr(c[k]).encode())
+    assert h.hexdigest() == 'f6cc3424729c3eeb8d86932ee415c1b2fd4a91da6238952e307cca60326589b3'
+    assert rc.CODES == rc.AIA + rc.NEW_CODES and len(rc.TAUS) == 11 and [x.numel() for x in rc.grids()] == [101, 2, 3, 37, 256]
+
+
+def test_rough_sets():
+    from sunerf_hip.response import ResponseSet
+    peaks = [float(y.max()) for _, _, _, y in rc.channels()[:7]]
+    assert min(peaks) <= 2e-25 and max(peaks) >= 2e-26          # the decade of the rough responses is that of the AIA rows
+    for name, counts in rc.SET_NODES.items():
+        ch = rc.set_channels(name)
+        rset = ResponseSet(list(ch))                           # distinct codes, strictly increasing fp32 grids, finite
+        assert [len(c[2]) for c in ch] == counts and rset.n_nodes == sum(counts)
+        assert rset.codes[:3] == rc.FIRST_CODES[:len(ch)] and int(rc.UNKNOWN) not in rset.codes
+        assert rc.half_code(rset.codes) - 0.5 in rset.codes and rc.half_code(rset.codes) not in rset.codes
+        assert float(torch.tensor(rc.half_code(rset.codes), dtype=torch.float32)) == rc.half_code(rset.codes)
+        for code, _, x, y in ch:
+            assert x.dtype == y.dtype == torch.float32 and bool((x[1:] > x[:-1]).all())
+            assert 4.0 <= float(x[0]) <= 6.0 and 0.99 <= float(x[-1] - x[0]) <= 3.01
+            assert bool((y >= 1.99e-26).all()) and bool((y <= 2.01e-25).all())
+            if len(x) >= 32:                                    # non-uniform steps, and neighbouring nodes that differ by O(1)
+                d = (x[1:] - x[:-1]).double()
+                assert 3.0 < float(d.max() / d.min()) < 6.1
+                assert float((y[1:] / y[:-1]).log10().abs().mean()) > 0.2
+    assert [len(rc.SET_NODES[k]) for k in ('R1', 'R32', 'R33', 'R64', 'R64r')] == [1, 32, 33, 64, 64]
+    assert sum(rc.SET_NODES['R64']) == sum(rc.SET_NODES['R64r']) == sum(rc.SET_NODES['R1']) == 4096
+    off = np.cumsum([0] + rc.SET_NODES['R64r'])
+    assert rc.SET_NODES['R64r'][40] == 3969 and off[41] > 4000 and all(o > 4000 for o in off[41:])
+    assert rc.set_taus(64)[:11] == rc.TAUS and rc.set_taus(64)[32 + 1] == rc.TAUS[0] and rc.set_taus(64).count(None) == 6
+
+
+@pytest.fixture(scope='module')
+def sizes():
+    """Every case of ``SIZE_CASES`` with its fp64 and fp32 restatements."""
+    out = []
+    for shape in rc.SIZE_CASES:
+        ch = list(rc.set_channels(shape[0]))
+        c = rc.size_case(*shape)
+        out.append((shape, ch, c, rr.oracle(c, ch, torch.float64), rr.oracle(c, ch, torch.float32)))
+    return out
+
+
+def test_size_case_table_is_the_issues():
+    want = {'R1': {(9, 33, 1, 'generic'), (9, 33, 8, 'nerf_dt')}, 'R32': {(72, 33, 8, 'generic')},
+            'R33': {(72, 33, 8, 'nerf_dt'), (9, 65, 3, 'generic')},
+            'R64r': {(72, 129, 8, 'nerf_dt'), (72, 33, 3, 'generic')}}
+    for name, shapes in want.items():
+        assert {s[1:] for s in rc.SIZE_CASES if s[0] == name} == shapes, name
+    r64 = {s[1:] for s in rc.SIZE_CASES if s[0] == 'R64'}
+    assert {(72, 33, 8, 'generic'), (72, 33, 8, 'nerf_dt'), (72, 129, 8, 'generic'), (9, 508, 8, 'generic')} <= r64
+    assert {s[:3] for s in r64} == {(72, 33, 8), (9, 3, 8), (9, 31, 8), (9, 32, 8), (72, 129, 8), (9, 508, 8)}
+    assert len(rc.SIZE_CASES) == len(set(rc.SIZE_CASES)) == 14
+
+
+def test_size_cases_node_totals_and_lds():
+    """Which launch path each case takes: only the two 129-sample cases and the 508-sample one need more than 64 KiB, through
+    the 4096 nodes (the same shapes on the 11-channel set stay below); 508 samples are the most 4096 nodes leave room for."""
+    for name, n, s, w, base in rc.SIZE_CASES:
+        rset = rc.set_of(name)
+        assert rset.n_channels == len(rc.SET_NODES[name]) and rset.n_nodes == sum(rc.SET_NODES[name])
+        lds = rset.bwd_lds_bytes(s, w)
+        assert lds == (200 + 2 * rset.n_nodes + 8 * s * w) * 4 <= 160 * 1024
+        assert (lds > 64 * 1024) == (s in (129, 508)), (name, s, lds)
+        if s == 129:
+            assert rset.n_nodes == 4096 and _set().bwd_lds_bytes(s, w) <= 64 * 1024
+        if s == 508:
+            assert rset.max_samples(w) == 508 and rset.bwd_lds_bytes(509, w) > 160 * 1024 and not rset.fits(509, w)
+
+
+def _grid_hits(logt, x):
+    inf = torch.tensor(math.inf)
+    k = x.numel()
+    tags = (('knot', torch.isin(logt, x)), ('first', (logt > x[0]) & (logt < x[1])), ('last', (logt > x[k - 2]) & (logt < x[k - 1])),
+            ('below', logt == torch.nextafter(x[0], -inf)), ('above', logt == torch.nextafter(x[-1], inf)),
+            ('lo', logt == x[0]), ('hi', logt == x[-1]))
+    return {tag for tag, hit in tags if bool(hit.any())}
+
+
+ALL_TAGS = {'knot', 'first', 'last', 'below', 'above', 'lo', 'hi'}
+
+
+def test_size_cases_cannot_pass_vacuously(sizes):
+    """The conditions of the cases.  Those that a 9-ray case has no room for (64 codes twice over in 27 or 72 columns, seven
+    kinds of sample on each of six grids in 27 samples) hold over the cases of each set together and on each of its 72-ray,
+    8-column cases by itself."""
+    by_set = {}
+    for shape, ch, c, ref64, _ in sizes:
+        name, n, s, w, base = shape
+        codes = [x[0] for x in ch]
+        m_ch = len(codes)
+        wl, logt = c['wl'], torch.relu(c['inf'][..., 1])
+        assert wl.dtype == torch.float32 and wl.shape == (n, w) and c['log_abs'].numel() == m_ch
+        assert int((c['log_abs'] < 0).sum()) == rc.set_taus(m_ch).count(None) and bool((c['log_abs'] != 0).all())
+        # the five odd values, each in column 0 and in the last column of some ray; today's replacements
+        half = rc.half_code(codes)
+        for col in (0, w - 1):
+            v = wl[:, col]
+            assert bool(torch.isnan(v).any()) and bool((v == math.inf).any()) and bool((v == half).any()) \
+                and bool((v == 16777216.0).any()) and bool((v == 1e-40).any()), (shape, col)
+        assert 0 < float(torch.tensor(1e-40)) < 1.17e-38 and half not in codes            # a denormal that fp32 keeps
+        known = torch.isin(wl, torch.tensor(codes, dtype=torch.float64).float())
+        plain = {v for v in (0., -1., rc.UNKNOWN) if bool((wl == v).any())}
+        assert n < 72 or len(plain) == 3, (shape, plain)
+        if w > 1 and (n >= 72 or m_ch == 1):
+            srt = torch.sort(torch.where(known, wl, -torch.arange(n * w, dtype=torch.float32).reshape(n, w) - 2), -1).values
+            assert bool((srt[:, 1:] == srt[:, :-1]).any()), shape                  # a code twice in one row
+        # the two codes one lane looks at, in adjacent columns, every 7th ray
+        if m_ch >= 33 and w >= 2:
+            row = {float(code): i for i, code in enumerate(codes)}
+            for i in range(3, n, 7):
+                pairs = [(row.get(float(a)), row.get(float(b))) for a, b in zip(wl[i, :-1], wl[i, 1:])]
+                assert any(a is not None and b is not None and b == a + 32 for a, b in pairs), (shape, i)
+        agg = by_set.setdefault(name, {'rays': torch.zeros(m_ch, dtype=torch.long), 'high': set(), 'hits': {}, 'lit': set()})
+        rays = torch.tensor([int((wl == float(code)).any(-1).sum()) for code in codes])
+        agg['rays'] += rays
+        agg.setdefault('plain', set()).update(plain)
+        high = {col for col in range(w) if bool(torch.isin(wl[:, col], torch.tensor(codes[32:], dtype=torch.float64).float()).any())}
+        agg['high'] |= {(w, col) for col in high}
+        hits = {i: _grid_hits(logt, x) for i, x in zip(rc.pool_rows(ch), rc.grids(ch))}
+        for i, tags in hits.items():
+            agg['hits'].setdefault(i, set()).update(tags)
+        agg['lit'] |= {code for code in codes if bool((ref64['image'][wl == float(code)] != 0).any())}
+        if n >= 72 and w == 8:
+            assert int(rays.min()) >= 2, (shape, rays)
+            assert m_ch < 33 or high == set(range(w)), (shape, high)
+            assert all(tags == ALL_TAGS for tags in hits.values()), (shape, hits)
+        assert {0, m_ch - 1, max(range(m_ch), key=lambda i: len(ch[i][2]))} <= set(rc.pool_rows(ch)) and len(hits) <= 6
+        if n * s >= 100:
+            assert bool(((logt > 9.0) | (logt < 4.0)).any()) and bool((c['inf'][..., 0] <= 0).any()) \
+                and bool((c['inf'][..., 1] <= 0).any()), shape
+        # more than half of the image is lit.  (One column against one channel in 9 rays: the five odd values leave four
+        # entries with a code -- every one of them is lit.)
+        lit = ref64['image'] != 0
+        assert bool(torch.isfinite(ref64['image']).all()) and not bool(lit[~known].any())
+        if w == 1 and n == 9:
+            assert int(known.sum()) == 4 and bool(lit[known].all()), shape
+        else:
+            assert float(lit.double().mean()) > 0.5, (shape, float(lit.double().mean()))
+    for name, agg in by_set.items():
+        m_ch = len(rc.SET_NODES[name])
+        assert int(agg['rays'].min()) >= 2, (name, agg['rays'])
+        assert len(agg['lit']) == m_ch and len(agg['plain']) == 3, name
+        assert all(tags == ALL_TAGS for tags in agg['hits'].values()), (name, agg['hits'])
+        if m_ch >= 33:
+            assert {col for w, col in agg['high'] if w == 8} == set(range(8)), (name, agg['high'])
+
+
+def _size_figures(c, codes, got, ref64, ref32):
+    """``rr.measure`` with the reference's own noise taken out of the bounds: the image's floor set to 0 and g_raw's
+    ``|ref32 - ref64|`` term removed (a reference equal to fp64 in both places)."""
+    return rr.measure(got, c, codes, ref64, ref64)
+
+
+def test_fp32_restatement_has_room_on_the_size_cases(sizes):
+    """The fp32 restatement against the fp64 one, the noise terms of the bounds removed: a quarter of every bound.  What keeps
+    the GPU test's bounds from measuring the inputs instead of the kernels."""
+    from test_gpu_dt_integral import SCALAR_GRADIENT_REL
+    worst = {}
+    for shape, ch, c, ref64, ref32 in sizes:
+        codes = [x[0] for x in ch]
+        got = {k: (v.float() if k not in ('g_log_abs', 'g_vol_c') else v) for k, v in ref32.items()}
+        m = _size_figures(c, codes, got, ref64, ref32)
+        assert m['image'] <= 0.25 and m['g_raw'] <= 0.25, (shape, m)
+        assert m['g_log_abs'] <= SCALAR_GRADIENT_REL / 4 and m['g_vol_c'] <= SCALAR_GRADIENT_REL / 4, (shape, m)
+        assert m['reg_q_bits'] == 0 and m['weights'] <= 1e-5 / 4, (shape, m)
+        for k, v in m.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    print('fp32 restatement against fp64, worst over the size cases: ' + ' '.join(f'{k} {v:.2e}' for k, v in worst.items()))
+
+
+def test_size_cases_see_a_lookup_that_drops_the_upper_half(sizes):
+    """A restatement that reads row ``m - 32`` (tables and absorption) for ``m >= 32`` -- what a lookup that lost the second
+    code of a lane would render -- fails the image bound on every case with M >= 33."""
+    from conftest import gate_units
+    seen = 0
+    for shape, ch, c, ref64, ref32 in sizes:
+        if len(ch) < 33:
+            continue
+        mutant = [(code,) + (ch[i - 32][1:] if i >= 32 else ch[i][1:]) for i, (code, *_) in enumerate(ch)]
+        la = c['log_abs'].clone()
+        la[32:] = c['log_abs'][:len(ch) - 32]
+        wrong = rr.oracle(dict(c, log_abs=la), mutant, torch.float64)
+        try:
+            units = gate_units(wrong['image'], ref64['image'], floor=2 * (ref32['image'].double() - ref64['image']).abs())
+        except AssertionError:                  # lit where the image is exactly 0: gate_units' own assertion
+            units = math.inf
+        assert units > 1.0, (shape, units)
+        seen += 1
+    assert seen == 11
+
+
+def test_embedding_and_smooth_sets():
+    from sunerf_hip.response import ResponseSet
+    e = ResponseSet(list(rc.embedded_channels()))
+    assert e.n_channels == 64 and e.n_nodes <= 4096 and sorted(rc.EMBED_PERM) == list(range(11)) and rc.EMBED_PERM != tuple(range(11))
+    assert [e.codes[53 + j] for j in range(11)] == [rc.CODES[p] for p in rc.EMBED_PERM]
+    assert not set(e.codes[:53]) & (set(rc.CODES) | {int(rc.UNKNOWN)})
+    for j, p in enumerate(rc.EMBED_PERM):
+        assert all(np.array_equal(a, b) for a, b in zip(e.table(53 + j), _set().table(p)))
+    assert e.fits(300, 8)
+    s64 = ResponseSet(list(rc.smooth_channels_64()))
+    assert s64.n_channels == 64 and s64.shared_grid() is None and len({len(c[2]) for c in rc.smooth_channels_64()}) > 30
+    for _, _, x, y in rc.smooth_channels_64():
+        assert float(x[0]) < 6.3 and float(x[-1]) > 6.65 and bool((y > 0).all())
+    s40 = ResponseSet(list(rc.smooth_channels_40()))
+    grid = s40.shared_grid()
+    assert s40.n_channels == 40 and s40.n_nodes == 4000 and grid is not None and grid.size == 100
+    d = np.diff(grid.astype(np.float64))
+    assert d.max() / d.min() > 2.5 and grid[0] == 4.0 and grid[-1] == 9.0
+    assert len({tuple(c[3].tolist()) for c in rc.smooth_channels_40()}) == 40            # no two rows alike
