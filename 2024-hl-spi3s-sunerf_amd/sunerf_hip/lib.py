@@ -202,6 +202,22 @@ _RESPONSE_SIGNATURES = {
 RESPONSE_SYMBOLS = tuple(_RESPONSE_SIGNATURES)
 RESPONSE_ABI_VERSION = 1
 
+# The image-preparation table (include/sunerf_hip_prep.h): spline prefilter, affine resample, exact order statistics.  A fourth
+# table beside the three above, which stay as they are and keep their versions.
+_PREP_SIGNATURES = {
+    'sunerf_prep_abi_version': (ctypes.c_int, []),
+    'sunerf_prep_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'sunerf_prep_spline_prefilter': (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void, c_void,
+                                                     c_void, ctypes.c_size_t, c_void]),
+    'sunerf_prep_affine_resample': (ctypes.c_int, [c_void, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+                                    + [ctypes.c_double] * 7 + [c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, c_void]),
+    'sunerf_prep_order_statistics': (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_int64, c_void, ctypes.c_int, c_f32p, c_void,
+                                                     c_void, ctypes.c_size_t, c_void]),
+}
+
+PREP_SYMBOLS = tuple(_PREP_SIGNATURES)
+PREP_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -234,6 +250,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_response_abi_version() != RESPONSE_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so response-set ABI version mismatch')
+        for name, (res, args) in _PREP_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_prep_abi_version() != PREP_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so image-preparation ABI version mismatch')
         _lib = lib
     return _lib
 

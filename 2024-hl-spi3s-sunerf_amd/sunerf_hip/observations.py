@@ -279,6 +279,18 @@ class ObservationSet:
         self._tables = {}
         return len(self.views) - 1
 
+    def add_prepared_view(self, image, wcs: dict, lat, lon, distance=AU_IN_SOLAR_RADII, time=0.0, wavelengths=None,
+                          downscale: int = 1, center=None, name: Optional[str] = None, **prep) -> int:
+        """Prepares a detector image on the device (``sunerf_hip.prep.prepare_image(image, wcs, **prep)``: roll to north,
+        recentre, one plate scale, scaling, norm and clips) and adds the result with the grid it was
+        prepared on: ``add_view(prepared, ..., grid=prepared grid)``.  ``wcs``: the plate-scale dict of the image as given, with
+        an optional ``'crota'`` or ``'pc'``.  With ``nan_policy='propagate'`` the pixels that saw a non-finite input pixel are NaN
+        and ``pool(drop_nonfinite=True)`` leaves their rays out."""
+        from .prep import prepare_image
+        prepared, grid = prepare_image(image, wcs, device=self.device, **prep)
+        return self.add_view(prepared, lat, lon, distance, time, grid=grid, wavelengths=wavelengths, downscale=downscale,
+                             center=center, name=name)
+
     def add_rendered_view(self, loader, lat, lon, time, distance=AU_IN_SOLAR_RADII, wl=None, resolution=None, center=None,
                           key: str = 'image', scale: float = 1.0, **kwargs) -> int:
         """Renders the loader's model from (lat, lon, distance) at ``time`` with ``render_observer_image(as_numpy=False)`` and

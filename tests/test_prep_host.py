@@ -1,0 +1,307 @@
+"""CPU-only checks of the image preparation (no GPU): the geometry of ``sunerf_hip.prep`` against the FITS formulae
+written out by hand, the default output frame, the fourth entry-point table (declared, bound, kept out of the other three, its
+argument checks in their documented order), and the conditions the cases of tests/prep_reference.py must meet so that
+tests/test_gpu_prep.py compares every output pixel and cannot pass vacuously."""
+import ctypes
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import prep_reference as pr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ('sunerf_prep_abi_version', 'sunerf_prep_workspace_bytes', 'sunerf_prep_spline_prefilter',
+               'sunerf_prep_affine_resample', 'sunerf_prep_order_statistics')
+
+
+@pytest.fixture(scope='session')
+def lib():
+    import sunerf_hip
+    if not os.path.exists(sunerf_hip.LIB_PATH):
+        import subprocess
+        subprocess.check_call(['bash', os.path.join(ROOT, '2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh')])
+    return sunerf_hip.load()
+
+
+def _cases():
+    from sunerf_hip import prep
+    return pr.geometry_cases(prep.SEGMENT, prep.HORIZON)
+
+
+# ---- geometry -------------------------------------------------------------------------------------------------------------------
+def _by_hand(wcs, grid, px, py):
+    """The 1-based source pixel of the 1-based output pixel (px, py): out pixel -> angles -> the inverse of the FITS map."""
+    s = grid['cdelt'][0]
+    tx = grid['crval'][0] + s * (px - grid['crpix'][0])
+    ty = grid['crval'][1] + s * (py - grid['crpix'][1])
+    # [tx - crval_x, ty - crval_y] = diag(cdelt) PC [x - crpix_x, y - crpix_y]
+    u, v = (tx - wcs['crval'][0]) / wcs['cdelt'][0], (ty - wcs['crval'][1]) / wcs['cdelt'][1]
+    (a, b), (c, d) = pr.pc_matrix(wcs)
+    det = a * d - b * c
+    return wcs['crpix'][0] + (d * u - b * v) / det, wcs['crpix'][1] + (-c * u + a * v) / det
+
+
+@pytest.mark.parametrize('wcs', [
+    {'shape': (37, 53), 'cdelt': (.6, .6), 'crpix': (27.3, 18.9), 'crval': (3.0, -7.0), 'crota': 0.3217},
+    {'shape': (20, 31), 'cdelt': (1.0, 1.3), 'crpix': (3.9, 2.6), 'crval': (0.0, 0.0), 'crota': -1.0103},
+    {'shape': (23, 19), 'cdelt': (1.1, 0.9), 'crpix': (9.3, 12.2), 'crval': (100.0, 5.5), 'pc': [[0.8, -0.55], [0.62, 0.79]]},
+], ids=['rolled', 'anisotropic', 'pc'])
+@pytest.mark.parametrize('recenter', [True, False])
+def test_affine_matrix_is_the_fits_formula(wcs, recenter):
+    from sunerf_hip import prep
+    grid = prep.output_grid(wcs, target_scale=0.77, out_shape=(29, 33), recenter=recenter)
+    assert grid['cdelt'] == (0.77, 0.77) and grid['crval'] == tuple(wcs['crval']) and 'crota' not in grid and 'pc' not in grid
+    if recenter:
+        assert grid['crpix'] == (17.0, 15.0)
+    else:         # the input's centre pixel lands on the output's centre
+        want = _by_hand(wcs, grid, 17.0, 15.0)
+        assert np.allclose(want, ((wcs['shape'][1] + 1) / 2, (wcs['shape'][0] + 1) / 2), rtol=0, atol=1e-11)
+    matrix, offset = prep.affine_matrix(wcs, grid)
+    assert matrix.shape == (2, 2) and offset.shape == (2,) and matrix.dtype == offset.dtype == np.float64
+    for py, px in ((1, 1), (29, 33), (7, 20), (15, 17)):
+        row, col = matrix @ np.array([py - 1.0, px - 1.0]) + offset
+        x, y = _by_hand(wcs, grid, float(px), float(py))
+        assert abs(col + 1 - x) < 1e-11 and abs(row + 1 - y) < 1e-11
+    ref_matrix, ref_offset = pr.scipy_matrix(wcs, grid)
+    assert np.allclose(matrix, ref_matrix, rtol=1e-13, atol=1e-15) and np.allclose(offset, ref_offset, rtol=0, atol=1e-11)
+
+
+def test_no_roll_and_equal_scale_is_the_identity():
+    from sunerf_hip import prep
+    for crpix in ((27.0, 19.0), (27.3, 18.9)):
+        wcs = {'shape': (37, 53), 'cdelt': (.6, .6), 'crpix': crpix, 'crval': (1.0, 2.0), 'crota': 0.0}
+        grid = prep.output_grid(wcs, recenter=crpix == (27.0, 19.0))
+        assert grid['shape'] == (37, 53) and grid['cdelt'] == (.6, .6)
+        matrix, offset = prep.affine_matrix(wcs, grid)
+        assert np.array_equal(matrix, np.eye(2)) and np.array_equal(offset, np.zeros(2)), (matrix, offset)
+
+
+@pytest.mark.parametrize('turn', [1, -1, 2])
+def test_a_quarter_turn_is_a_pixel_permutation(turn):
+    from sunerf_hip import prep
+    n = 9
+    wcs = {'shape': (n, n), 'cdelt': (1.3, 1.3), 'crota': turn * math.pi / 2}
+    grid = prep.output_grid(wcs)
+    assert grid['shape'] == (n, n)
+    matrix, offset = prep.affine_matrix(wcs, grid)
+    assert np.array_equal(np.abs(matrix), np.eye(2) if turn == 2 else np.eye(2)[::-1])
+    y, x = pr.source_coordinates(matrix, offset, (n, n))
+    assert np.array_equal(y, np.round(y)) and np.array_equal(x, np.round(x))
+    flat = (y * n + x).astype(int).reshape(-1)
+    assert sorted(flat.tolist()) == list(range(n * n))                      # every input pixel exactly once
+    src = np.arange(n * n).reshape(n, n)
+    moved = src.reshape(-1)[flat].reshape(n, n)
+    assert any(np.array_equal(moved, np.rot90(src, k)) for k in range(1, 4))
+
+
+@pytest.mark.parametrize('wcs,s,recenter', [
+    ({'shape': (37, 53), 'cdelt': (.6, .6), 'crpix': (27.3, 18.9), 'crota': 0.3217}, 0.731, True),
+    ({'shape': (37, 53), 'cdelt': (.6, .6), 'crpix': (27.3, 18.9), 'crota': 0.3217}, 0.731, False),
+    ({'shape': (20, 31), 'cdelt': (1.0, 1.3), 'crpix': (3.9, 2.6), 'crota': 2.1}, 0.57, False),
+    ({'shape': (23, 19), 'cdelt': (1.1, 0.9), 'crpix': (9.3, 12.2), 'pc': [[0.8, -0.55], [0.62, 0.79]]}, 1.07, True),
+])
+def test_default_frame_is_the_smallest_that_holds_the_four_corners(wcs, s, recenter):
+    from sunerf_hip import prep
+    h, w = wcs['shape']
+
+    def corners_inside(shape):
+        grid = prep.output_grid(wcs, target_scale=s, out_shape=shape, recenter=recenter)
+        matrix, offset = prep.affine_matrix(wcs, grid)
+        inv = np.linalg.inv(matrix)
+        inside = []
+        for cy, cx in ((-.5, -.5), (-.5, w - .5), (h - .5, -.5), (h - .5, w - .5)):          # 0-based corner of the input
+            oy, ox = inv @ (np.array([cy, cx]) - offset)
+            inside.append(-.5 - 1e-6 <= oy <= shape[0] - .5 + 1e-6 and -.5 - 1e-6 <= ox <= shape[1] - .5 + 1e-6)
+        return inside
+    nh, nw = prep.output_grid(wcs, target_scale=s, recenter=recenter)['shape']
+    assert all(corners_inside((nh, nw)))
+    assert not all(corners_inside((nh - 1, nw))) and not all(corners_inside((nh, nw - 1)))
+
+
+def test_field_of_view_is_the_center_crop():
+    from sunerf_hip import prep
+    wcs = {'shape': (64, 64), 'cdelt': (40.0, 40.0)}
+    grid = prep.output_grid(wcs, target_scale=37.0, field_of_view=(1000.0, 900.0))
+    assert grid['shape'] == (round(1800 / 37.0), round(2000 / 37.0)) and grid['crpix'] == ((grid['shape'][1] + 1) / 2, (grid['shape'][0] + 1) / 2)
+    with pytest.raises(ValueError):
+        prep.output_grid(wcs, out_shape=(3, 3), field_of_view=(1.0, 1.0))
+    with pytest.raises(ValueError):
+        prep.output_grid({**wcs, 'crota': 0.1, 'pc': np.eye(2)})
+
+
+# ---- the cases of the GPU tests -------------------------------------------------------------------------------------------------
+def test_horizons_are_the_smallest_that_reach_1e_17():
+    from sunerf_hip import prep
+    poles = {2: [math.sqrt(8) - 3], 3: [math.sqrt(3) - 2],
+             4: [math.sqrt(664 - math.sqrt(438976)) + math.sqrt(304) - 19, math.sqrt(664 + math.sqrt(438976)) - math.sqrt(304) - 19],
+             5: [math.sqrt(67.5 - math.sqrt(4436.25)) + math.sqrt(26.25) - 6.5, math.sqrt(67.5 + math.sqrt(4436.25)) - math.sqrt(26.25) - 6.5]}
+    assert prep.HORIZON == {0: 0, 1: 0, 2: 23, 3: 30, 4: 39, 5: 47} and prep.SEGMENT >= 64
+    for order, zs in poles.items():
+        ks = [prep.HORIZON[order]] + ([prep.SECOND_HORIZON[order]] if len(zs) == 2 else [])
+        for z, k in zip(zs, ks):
+            assert abs(z) ** k < 1e-17 <= abs(z) ** (k - 1), (order, z, k)
+
+
+@pytest.mark.parametrize('order', range(6))
+def test_every_case_keeps_clear_of_the_borders(order):
+    """No output pixel of a GPU case may be left out of the comparison: on every axis the fp64 source coordinates are either all
+    integers (an exact case) or more than 1e-6 pixels from 0 and n - 1, and for order 0 from the half-integers -- by scipy's
+    matrix and by the project's own."""
+    from sunerf_hip import prep
+    worst = np.inf
+    for case in _cases():
+        wcs = case['wcs']
+        grid, (matrix, offset) = pr.case_matrix(case)
+        own_grid = prep.output_grid(wcs, target_scale=case['s'], out_shape=case['out_shape'])
+        assert own_grid['shape'] == grid['shape'] and own_grid['crpix'] == grid['crpix'] and own_grid['cdelt'] == grid['cdelt']
+        own = prep.affine_matrix(wcs, own_grid)
+        some_inside = False
+        for m, o in ((matrix, offset), own):
+            ys, xs = pr.source_coordinates(m, o, case['out_shape'])
+            exact = []
+            for coords, n in ((ys, wcs['shape'][0]), (xs, wcs['shape'][1])):
+                is_exact, d = pr.border_clearance(coords, n, order)
+                exact.append(is_exact)
+                assert d > 1e-6, (case['name'], order, d)
+                worst = min(worst, d)
+            assert any(exact) == case['exact'], case['name']
+            inside = (ys >= 0) & (ys <= wcs['shape'][0] - 1) & (xs >= 0) & (xs <= wcs['shape'][1] - 1)
+            some_inside |= bool(inside.any())
+        assert some_inside, case['name']
+        if case['exact']:         # the integer axes agree by bits between the two matrices
+            a, b = pr.source_coordinates(matrix, offset, case['out_shape']), pr.source_coordinates(*own, case['out_shape'])
+            for u, v in zip(a, b):
+                if np.array_equal(u, np.round(u)):
+                    assert np.array_equal(u, v), case['name']
+    print(f'order {order}: smallest clearance {worst:.3g} pixels')
+
+
+def test_the_strip_fills_exactly_one_output_row():
+    case = next(c for c in _cases() if c['name'] == 'strip')
+    _, (matrix, offset) = pr.case_matrix(case)
+    img = pr.case_image(case['wcs']['shape'], 1)
+    for order in range(6):
+        out = pr.resample(img, matrix, offset, case['out_shape'], order, missing=-5.0)[0]
+        assert np.array_equal(out[0], np.full(9, -5.0)) and np.array_equal(out[2], np.full(9, -5.0))
+        assert not np.any(out[1] == -5.0)
+        assert np.allclose(out[1], img[0, 0], rtol=1e-12, atol=1e-9)         # the spline interpolates its samples
+
+
+def test_exact_decimation_is_unusable_for_order_0():
+    """Why no case decimates by an exact factor of 2: the coordinates sit on half-integers, where rounding noise picks the pixel."""
+    wcs = {'shape': (8, 8), 'cdelt': (1.0, 1.0), 'crpix': (4.5, 4.5), 'crval': (0.0, 0.0), 'crota': 0.0}
+    matrix, offset = pr.scipy_matrix(wcs, pr.centred_grid((4, 4), 2.0))
+    ys, _ = pr.source_coordinates(matrix, offset, (4, 4))
+    assert pr.border_clearance(ys, 8, 0)[1] == 0.0
+
+
+def test_restatement_epilogue_by_hand():
+    img = np.array([[[1.0, np.nan], [np.inf, 9.0]]], dtype=np.float32)
+    v, out = pr.prepare(img, np.eye(2), np.zeros(2), (2, 3), order=1, missing=-2.0, factor=2.0, norm=(1.0, 5.0), clip_negative=True)
+    assert np.array_equal(out, np.array([[[0.25, 0.0, 0.0], [0.0, 4.25, 0.0]]], dtype=np.float32))
+    _, out = pr.prepare(img, np.eye(2), np.zeros(2), (2, 3), order=0, missing=-2.0, clip_negative=False, nan_policy='propagate')
+    assert np.array_equal(np.isnan(out[0]), np.array([[False, True, False], [True, False, False]]))
+    assert out[0, 0, 2] == -2.0 and out[0, 1, 1] == 9.0
+    assert pr.percentile(np.array([3.0, np.nan, 1.0, 2.0]), 50) == np.float32(2.0)
+
+
+# ---- the fourth table -----------------------------------------------------------------------------------------------------------
+def test_entry_points_are_declared_bound_and_kept_out_of_the_other_tables(lib):
+    import sunerf_hip
+    from sunerf_hip import lib as binding, prep
+    read = lambda *p: open(os.path.join(ROOT, *p)).read()          # noqa: E731
+    header = read('include', 'sunerf_hip_prep.h')
+    declared = set(re.findall(r'\b(sunerf_\w+)\s*\(', header))
+    assert declared == set(NEW_SYMBOLS) == set(sunerf_hip.PREP_SYMBOLS) == set(binding._PREP_SIGNATURES)
+    others = [read('include', n) for n in ('sunerf_hip.h', 'sunerf_hip_ext.h', 'sunerf_hip_response.h')]
+    for name in NEW_SYMBOLS:
+        fn = getattr(lib, name)
+        assert name not in sunerf_hip.EXPORTED_SYMBOLS + sunerf_hip.EXTENSION_SYMBOLS + sunerf_hip.RESPONSE_SYMBOLS
+        assert all(name not in text for text in others)
+        assert fn.restype is binding._PREP_SIGNATURES[name][0] and list(fn.argtypes) == binding._PREP_SIGNATURES[name][1]
+    assert lib.sunerf_abi_version() == 9 and lib.sunerf_ext_abi_version() == 1 and lib.sunerf_response_abi_version() == 1
+    assert lib.sunerf_prep_abi_version() == binding.PREP_ABI_VERSION == 1 and '#define SUNERF_PREP_ABI_VERSION 1' in header
+    assert f'#define SUNERF_PREP_SEGMENT {prep.SEGMENT}' in header
+    assert ', '.join(str(prep.HORIZON[o]) for o in range(6)) in header
+    build = read('2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh')
+    assert len(re.findall(r'\bprep\b', build)) == 2
+    assert 'PREP_SYMBOLS' in read('__graft_entry__.py')
+
+
+def test_workspace_query(lib):
+    q = lib.sunerf_prep_workspace_bytes
+    assert q(0, 3, 10, 20, 3) == 3 * 10 * 20 * 8 and q(0, 3, 10, 20, 1) == 0 and q(0, 3, 1, 20, 5) == 0
+    assert q(0, 3, 10, 20, 6) == 0 and q(0, 0, 10, 20, 3) == 0
+    for n, groups in ((1, 1), (4096, 1), (4097, 2), (4096 * 4096, 128)):
+        assert q(1, 2, n, 1, 3) == 2 * 3 * 16 + 2 * groups * (3 * 256 + 1) * 4
+    assert q(1, 2, 100, 1, 0) == 0 and q(1, 2, 100, 1, 9) == 0 and q(7, 2, 100, 1, 1) == 0
+
+
+def test_argument_checks_come_in_the_documented_order(lib):
+    """Unsupported (-2) first, then the empty call (0), then negative counts and null pointers (-1), then the workspace (-3): all
+    before anything touches a device, so this runs without one.  ``P`` stands for any non-null pointer: no call here reaches a
+    launch."""
+    P = ctypes.c_void_p(4096)
+    pre = lib.sunerf_prep_spline_prefilter
+    assert pre(None, 0, 4, 4, 6, None, None, None, 0, None) == -2
+    assert pre(None, 0, 4, 4, 3, None, None, None, 0, None) == 0 and pre(None, 2, 4, 0, 3, None, None, None, 0, None) == 0
+    assert pre(P, -1, 4, 0, 3, P, None, P, 1 << 20, None) == -1
+    assert pre(None, 2, 4, 4, 3, P, None, P, 1 << 20, None) == -1 and pre(P, 2, 4, 4, 3, None, None, P, 1 << 20, None) == -1
+    assert pre(P, 2, 4, 4, 3, P, None, None, 1 << 20, None) == -1
+    assert pre(P, 2, 4, 4, 3, P, None, P, 2 * 4 * 4 * 8 - 1, None) == -3
+
+    m = (1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0)
+    res = lib.sunerf_prep_affine_resample
+    assert res(None, None, 0, 4, 4, 6, *m, None, 0, 4, 4, None, None) == -2
+    assert res(P, None, 1, 4, 4, 3, *m, P, 32, 4, 4, P, None) == -2
+    assert res(None, None, 0, 4, 4, 3, *m, None, 0, 4, 4, None, None) == 0
+    assert res(None, None, 1, 4, 4, 3, *m, None, 0, 0, 4, None, None) == 0
+    assert res(P, None, -1, 4, 4, 3, *m, P, 0, 0, 4, P, None) == -1
+    assert res(P, None, 1, 0, 4, 3, *m, P, 0, 4, 4, P, None) == -1
+    for args in ((None, None, 1, 4, 4, 3, *m, P, 0, 4, 4, P), (P, None, 1, 4, 4, 3, *m, None, 0, 4, 4, P),
+                 (P, None, 1, 4, 4, 3, *m, P, 0, 4, 4, None), (P, None, 1, 4, 4, 3, *m, P, 16, 4, 4, P)):
+        assert res(*args, None) == -1
+
+    sel = lib.sunerf_prep_order_statistics
+    assert sel(None, 0, 10, None, 9, None, None, None, 0, None) == -2 and sel(None, 0, 10, None, 0, None, None, None, 0, None) == -2
+    assert sel(None, 0, 10, None, 2, None, None, None, 0, None) == 0 and sel(None, 3, 0, None, 2, None, None, None, 0, None) == 0
+    assert sel(P, -1, 0, P, 2, P, P, P, 1 << 20, None) == -1
+    for k in range(5):
+        ptrs = [P] * 5
+        ptrs[k] = None
+        assert sel(ptrs[0], 1, 10, ptrs[1], 2, ptrs[2], ptrs[3], ptrs[4], 1 << 20, None) == -1
+    need = lib.sunerf_prep_workspace_bytes(1, 1, 10, 1, 2)
+    assert need > 0 and sel(P, 1, 10, P, 2, P, P, P, need - 1, None) == -3
+
+
+def test_host_side_rejections():
+    import torch
+    from sunerf_hip import SunerfHipError, prep
+    wcs = {'shape': (4, 4), 'cdelt': (1.0, 1.0)}
+    with pytest.raises(SunerfHipError):
+        prep.prepare_image(torch.zeros(4, 4), wcs)                       # no CPU path
+    with pytest.raises(SunerfHipError):
+        prep.plane_quantiles(torch.zeros(1, 4), 50.0)
+    with pytest.raises(ValueError):
+        prep.prepare_image(torch.zeros(4, 4), wcs, order=6)
+    with pytest.raises(ValueError):
+        prep.prepare_image(torch.zeros(4, 4), wcs, nan_policy='keep')
+    with pytest.raises(ValueError):
+        prep.output_grid({'shape': (4, 4), 'cdelt': (1.0, 0.0)})
+    with pytest.raises(ValueError):
+        prep.output_grid({'shape': (4, 4), 'cdelt': (1.0, 1.0), 'pc': [[1.0, 2.0], [2.0, 4.0]]})
+
+
+def test_abi_cases_cover_the_launching_entry_points(lib):
+    """The cases of tests/test_gpu_prep_abi.py: one table entry per launching entry point, every argument of the signature."""
+    import test_gpu_prep_abi as abi
+    from sunerf_hip import lib as binding
+    assert set(abi.PREP_CASES) | {'sunerf_prep_abi_version', 'sunerf_prep_workspace_bytes'} == set(binding.PREP_SYMBOLS)
+    for name, (builder, shapes) in abi.PREP_CASES.items():
+        for shape in shapes:
+            case = builder(shape, 'cpu')
+            assert case.name == name and len(case.args) == len(binding._PREP_SIGNATURES[name][1])
+            assert case.empty and (case.ws_index is None or case.args[case.ws_index] > 0)
