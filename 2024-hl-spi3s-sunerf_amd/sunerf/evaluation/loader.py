@@ -205,6 +205,37 @@ class SuNeRFLoader:
         time = normalize_datetime(time, self.seconds_per_dt, self.ref_time)
         return self._render(lat, lon, time, distance, center, resolution, batch_size, None, as_numpy, strides)
 
+    def _observe(self, lat, lon, time: float, instrument, seed, distance, center, resolution, batch_size, wl, as_numpy, poisson,
+                 read):
+        """The frame rendered at ``instrument.bin`` times the detector resolution over the same field of view -- the bin x bin
+        sub-pixels tile each detector pixel -- moved to planes and seen through ``instrument``; back in (H, W[, C]) layout."""
+        from sunerf_hip.observations import resampled_grid
+        if not isinstance(self.ref_map, dict) or 'shape' not in self.ref_map:
+            raise TypeError('observe_image needs a plate-scale dict with a shape as the reference map')
+        if resolution is None:
+            resolution = self.ref_map['shape']
+        nh, nw = (resolution, resolution) if np.isscalar(resolution) else resolution
+        b = instrument.bin
+        fine = (int(nh) * b, int(nw) * b)
+        frame = self._render(lat, lon, time, distance, center, fine, batch_size, wl, as_numpy=False)['image']
+        planes = (frame[None] if frame.dim() == 2 else frame.permute(2, 0, 1)).contiguous()
+        out = instrument.observe(planes, seed, poisson=poisson, read=read)
+        out = {k: (v[0] if frame.dim() == 2 else v.permute(1, 2, 0).contiguous()) for k, v in out.items()}
+        if as_numpy:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+        out['grid'] = instrument.detector_grid(resampled_grid(self.ref_map, fine))
+        return out
+
+    @torch.no_grad()
+    def observe_image(self, lat, lon, time: datetime, instrument, seed: int = 0, resolution=None,
+                      distance=AU_IN_SOLAR_RADII, center: Tuple[float, float, float] = None, batch_size: int = 1 << 18,
+                      as_numpy: bool = True, poisson: bool = True, read: bool = True):
+        """What ``instrument`` (``sunerf_hip.instrument.Instrument``) records of the observer's view at ``time``: ``image`` (one
+        noisy realisation), ``expected`` (blurred and binned, noise-free), ``sigma``, ``saturated`` at the detector's
+        ``resolution`` (default: the reference map's) and ``grid``, the plate-scale dict of that frame.  ``seed`` fixes the noise."""
+        time = normalize_datetime(time, self.seconds_per_dt, self.ref_time)
+        return self._observe(lat, lon, time, instrument, seed, distance, center, resolution, batch_size, None, as_numpy, poisson, read)
+
     def _columns(self, lat, lon, time: float, grid, r_range, n_samples, batch_size, profiles, wl, as_numpy):
         wavelengths = None if wl is None else torch.as_tensor(np.asarray(wl), dtype=torch.float32, device=self.device)
         lat = torch.from_numpy(_radians_array(lat).reshape(-1)).to(self.device)
@@ -413,6 +444,13 @@ class ModelLoader(SuNeRFLoader):
         """loader.py:159-242: ``time`` is already normalised here (a float); ``strides`` as in
         :meth:`SuNeRFLoader.render_observer_image`."""
         return self._render(lat, lon, time, distance, center, resolution, batch_size, wl, as_numpy, strides)
+
+    @torch.no_grad()
+    def observe_image(self, lat, lon, time: float, instrument, seed: int = 0, resolution=None, distance=AU_IN_SOLAR_RADII,
+                      wl: Optional[np.ndarray] = None, center: Tuple[float, float, float] = None, batch_size: int = 1 << 17,
+                      as_numpy: bool = True, poisson: bool = True, read: bool = True):
+        """:meth:`SuNeRFLoader.observe_image` with ``time`` already normalised (a float) and the channels ``wl``."""
+        return self._observe(lat, lon, time, instrument, seed, distance, center, resolution, batch_size, wl, as_numpy, poisson, read)
 
     @torch.no_grad()
     def render_heliographic_map(self, time: float, lat_range=(-np.pi / 2, np.pi / 2), lon_range=(-np.pi, np.pi),

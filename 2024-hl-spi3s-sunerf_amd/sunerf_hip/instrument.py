@@ -1,0 +1,263 @@
+"""A render observed through an instrument (include/sunerf_hip_instrument.h): correlation with the point-spread
+function, summation of ``bin x bin`` sub-pixels into detector pixels, photon and read noise, digitisation, saturation -- the way
+from a noise-free pinhole render back to what a detector would have recorded, and the error model (``sigma``) that goes with it.
+
+The PSF and the box of the binning are folded into ONE kernel on the host (:meth:`Instrument.effective_kernel`), so a detector
+pixel costs ``(k + bin - 1)^2`` multiply-adds and not ``bin^2 k^2``; the device runs one strided correlation
+(``sunerf_instrument_correlate_bin``) and one per-element noise kernel (``sunerf_instrument_noise``) whose randomness is the
+counter-based Philox4x32-10 of the header: an element's draw depends on the seed and on its index alone, so tiles, ranks and
+reruns agree by bits.  There is no CPU path for either; :meth:`Instrument.errors` and the kernel builders are plain host code.
+
+Units: ``unit`` photons-per-second-per-pixel per image unit (what one unit of the render is worth at the detector), ``exposure``
+seconds, ``dn_per_photon`` the gain, ``read_noise``, ``pedestal`` and ``saturation`` in DN.  Images go in and come out in image units."""
+import ctypes
+import math
+from typing import Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import lib as _l
+
+MAX_KERNEL, MAX_BIN = 96, 8                      # include/sunerf_hip_instrument.h
+BOUNDARY = {'zero': 0, 'nearest': 1}
+POISSON, READ, QUANTISE, SATURATE = 1, 2, 4, 8
+N_PARAMS = 8
+FWHM_PER_SIGMA = 2.0 * math.sqrt(2.0 * math.log(2.0))
+_SCALARS = ('unit', 'exposure', 'dn_per_photon', 'read_noise', 'pedestal', 'saturation')
+
+
+def _radial_grid(radius: int):
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError(f'radius must be >= 0, got {radius}')
+    ax = np.arange(-radius, radius + 1, dtype=np.float64)
+    return ax[:, None] ** 2 + ax[None, :] ** 2
+
+
+def gaussian_psf(fwhm: float, radius: int) -> np.ndarray:
+    """A Gaussian of full width at half maximum ``fwhm`` (pixels of the rendered grid) sampled at the pixel centres of a
+    ``(2 radius + 1)^2`` stamp, fp64, normalised to sum to 1."""
+    if not fwhm > 0:
+        raise ValueError(f'fwhm must be > 0, got {fwhm}')
+    sigma = float(fwhm) / FWHM_PER_SIGMA
+    k = np.exp(-_radial_grid(radius) / (2.0 * sigma * sigma))
+    return k / k.sum()
+
+
+def moffat_psf(fwhm: float, beta: float, radius: int) -> np.ndarray:
+    """A Moffat profile ``(1 + r^2 / alpha^2)^-beta`` of full width at half maximum ``fwhm`` (pixels of the rendered grid), fp64,
+    on a ``(2 radius + 1)^2`` stamp, normalised to sum to 1."""
+    if not fwhm > 0 or not beta > 0:
+        raise ValueError(f'fwhm and beta must be > 0, got {fwhm}, {beta}')
+    alpha = float(fwhm) / (2.0 * math.sqrt(2.0 ** (1.0 / float(beta)) - 1.0))
+    k = (1.0 + _radial_grid(radius) / (alpha * alpha)) ** -float(beta)
+    return k / k.sum()
+
+
+Scalar = Union[float, Sequence[float]]
+
+
+class Instrument:
+    """The forward model of a detector.  ``psf``: ``(kh, kw)`` or per channel ``(C, kh, kw)``, its centre at index
+    ``((kh - 1) // 2, (kw - 1) // 2)`` (``scipy.signal.convolve2d(mode='same')``'s); None: no blur.  ``bin``: sub-pixels per
+    detector pixel and axis, ``bin_mode`` their 'mean' (an intensity) or 'sum' (a flux).  ``boundary``: what the PSF reads past
+    the frame's edge, the 'nearest' pixel or 'zero'.  Every scalar may be one value or one per channel."""
+
+    def __init__(self, psf=None, bin: int = 1, bin_mode: str = 'mean', boundary: str = 'nearest', unit: Scalar = 1.,
+                 exposure: Scalar = 1., dn_per_photon: Scalar = 1., read_noise: Scalar = 0., pedestal: Scalar = 0.,
+                 saturation: Scalar = math.inf, quantise: bool = False):
+        if bin_mode not in ('mean', 'sum'):
+            raise ValueError(f"bin_mode must be 'mean' or 'sum', got {bin_mode!r}")
+        if boundary not in BOUNDARY:
+            raise ValueError(f"boundary must be 'nearest' or 'zero', got {boundary!r}")
+        if int(bin) != bin or not 1 <= int(bin) <= MAX_BIN:
+            raise ValueError(f'bin must be an integer in 1 .. {MAX_BIN}, got {bin}')
+        self.bin, self.bin_mode, self.boundary, self.quantise = int(bin), bin_mode, boundary, bool(quantise)
+        self.psf = None
+        if psf is not None:
+            psf = np.asarray(psf.detach().cpu().numpy() if isinstance(psf, torch.Tensor) else psf, dtype=np.float64)
+            if psf.ndim not in (2, 3) or 0 in psf.shape:
+                raise ValueError(f'psf must be (kh, kw) or (C, kh, kw), got {psf.shape}')
+            if max(psf.shape[-2:]) + self.bin - 1 > MAX_KERNEL:
+                raise ValueError(f'psf {psf.shape[-2:]} with bin {self.bin}: the effective kernel exceeds {MAX_KERNEL} taps per axis')
+            self.psf = psf
+        for name, value in zip(_SCALARS, (unit, exposure, dn_per_photon, read_noise, pedestal, saturation)):
+            v = np.asarray(value, dtype=np.float64)
+            if v.ndim > 1:
+                raise ValueError(f'{name} must be a scalar or one value per channel')
+            setattr(self, name, v)
+        self._device_kernels = {}
+
+    # ---- host side ----------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_spec(cls, spec: str) -> 'Instrument':
+        """``'fwhm=2.5,bin=2,exposure=2.9,dn_per_photon=1.2,read_noise=1.2,unit=40'``: a Gaussian PSF of that FWHM (``beta=``
+        makes it a Moffat; ``radius=`` its half-size, default ceil(3 fwhm) for a Gaussian, ceil(4 fwhm) for a Moffat) and the
+        constructor's scalars; ``quantise=1``, ``bin_mode=sum``, ``boundary=zero`` as named."""
+        fields = {}
+        for item in filter(None, (s.strip() for s in spec.split(','))):
+            key, sep, value = item.partition('=')
+            if not sep:
+                raise ValueError(f'instrument spec: {item!r} is not key=value')
+            fields[key.strip()] = value.strip()
+        kw = {}
+        fwhm, beta, radius = fields.pop('fwhm', None), fields.pop('beta', None), fields.pop('radius', None)
+        if fwhm is not None:
+            fwhm = float(fwhm)
+            if beta is None:
+                kw['psf'] = gaussian_psf(fwhm, int(radius) if radius is not None else math.ceil(3 * fwhm))
+            else:
+                kw['psf'] = moffat_psf(fwhm, float(beta), int(radius) if radius is not None else math.ceil(4 * fwhm))
+        elif beta is not None or radius is not None:
+            raise ValueError('instrument spec: beta / radius need fwhm')
+        for key, value in fields.items():
+            if key in _SCALARS:
+                kw[key] = float(value)
+            elif key == 'bin':
+                kw[key] = int(value)
+            elif key in ('bin_mode', 'boundary'):
+                kw[key] = value
+            elif key == 'quantise':
+                kw[key] = value.lower() in ('1', 'true', 'yes')
+            else:
+                raise ValueError(f'instrument spec: unknown key {key!r}')
+        return cls(**kw)
+
+    def effective_kernel(self) -> Tuple[np.ndarray, Tuple[int, int]]:
+        """``(K, (anchor_y, anchor_x))``, ``K`` fp64 ``(n, kh + bin - 1, kw + bin - 1)`` with n = 1 or C: the flipped PSF
+        convolved with the ``bin x bin`` box of ones, so that the blurred and summed detector pixel (R, C) is
+        ``sum_ij K[i, j] in[R bin + i - anchor_y, C bin + j - anchor_x]``; the 'mean' of ``bin_mode`` is the ``scale`` of the
+        device call, not part of ``K``."""
+        psf = np.ones((1, 1, 1)) if self.psf is None else (self.psf[None] if self.psf.ndim == 2 else self.psf)
+        n, kh, kw = psf.shape
+        b = self.bin
+        flipped = psf[:, ::-1, ::-1]
+        K = np.zeros((n, kh + b - 1, kw + b - 1))
+        for dy in range(b):
+            for dx in range(b):
+                K[:, dy:dy + kh, dx:dx + kw] += flipped
+        return K, (kh // 2, kw // 2)          # kh - 1 - (kh - 1) // 2
+
+    @property
+    def scale(self) -> float:
+        return 1.0 / (self.bin * self.bin) if self.bin_mode == 'mean' else 1.0
+
+    def params(self, n_channels: int) -> np.ndarray:
+        """``[C, 8]`` fp64: unit, exposure, dn_per_photon, read_noise, pedestal, saturation, 0, 0 per channel."""
+        out = np.zeros((n_channels, N_PARAMS))
+        for k, name in enumerate(_SCALARS):
+            v = getattr(self, name)
+            if v.ndim == 1 and v.shape[0] != n_channels:
+                raise ValueError(f'{name} has {v.shape[0]} values, the frame {n_channels} channels')
+            out[:, k] = v
+        return out
+
+    def detector_grid(self, grid: dict) -> dict:
+        """The plate-scale dict of the binned frame of a rendered frame ``grid`` (``shape``, ``cdelt``, optional ``crpix`` /
+        ``crval``): ``bin`` times the pixel size, the reference pixel moved with the field of view (the rule of
+        ``sunerf.evaluation.loader.linear_plate_scale_axes``), trailing rows and columns that fill no detector pixel dropped."""
+        h, w = grid['shape']
+        b = self.bin
+        cdx, cdy = grid['cdelt']
+        cpx, cpy = grid.get('crpix', ((w + 1) / 2., (h + 1) / 2.))
+        out = {k: v for k, v in grid.items() if k not in ('shape', 'cdelt', 'crpix')}
+        out.update(shape=(h // b, w // b), cdelt=(cdx * b, cdy * b), crpix=((cpx - 0.5) / b + 0.5, (cpy - 0.5) / b + 0.5))
+        return out
+
+    def errors(self, image, channel_axis: int = -1):
+        """The ``sigma`` of an OBSERVED image (image units, any device, plain torch): the sigma formula of :meth:`observe` with
+        the photon count estimated from the image itself, ``lam = max(dn - pedestal, 0) / dn_per_photon``.  Same shape as
+        ``image`` -- ``(..., M)`` with the channels last is what ``invert_dem(errors=...)`` takes; per-channel scalars are laid
+        along ``channel_axis`` (0 for planes)."""
+        image = torch.as_tensor(image)
+        x = image.double()
+
+        def s(name):
+            v = getattr(self, name)
+            if v.ndim == 0:
+                return float(v)
+            if x.dim() == 0 or x.shape[channel_axis] != v.shape[0]:
+                raise ValueError(f'{name} has {v.shape[0]} values, the image {tuple(x.shape)} along axis {channel_axis}')
+            shape = [1] * x.dim()
+            shape[channel_axis] = v.shape[0]
+            return torch.as_tensor(v, device=x.device).view(shape)
+        unit, exposure, g, rn = s('unit'), s('exposure'), s('dn_per_photon'), s('read_noise')
+        signal = (x * unit * exposure).clamp_min(0.0)          # dn - pedestal
+        lam = signal / g
+        var = lam * (g * g) + rn * rn + (1.0 / 12.0 if self.quantise else 0.0)
+        return (var.sqrt() / exposure / unit).to(torch.float32)
+
+    # ---- device side --------------------------------------------------------------------------------------------------------
+    def _planes(self, planes, what):
+        if not isinstance(planes, torch.Tensor):
+            raise TypeError(f'{what}: planes must be a torch.Tensor')
+        if not planes.is_cuda:
+            raise _l.SunerfHipError(f'{what} runs on a ROCm device (there is no CPU path)')
+        if planes.dim() == 2:
+            planes = planes[None]
+        if planes.dim() != 3 or planes.dtype != torch.float32:
+            raise ValueError(f'{what}: planes must be float32 [C, H, W], got {planes.dtype} {tuple(planes.shape)}')
+        return planes.contiguous()
+
+    def expected(self, planes: torch.Tensor) -> torch.Tensor:
+        """``[C, H // bin, W // bin]`` float32: ``planes`` [C, H, W] blurred by the PSF and binned, noise-free."""
+        from .ops import _ptr, _stream
+        planes = self._planes(planes, 'Instrument.expected')
+        c, h, w = planes.shape
+        K, (ay, ax) = self.effective_kernel()
+        if K.shape[0] not in (1, c):
+            raise ValueError(f'the psf has {K.shape[0]} channels, the frame {c}')
+        dev = planes.device
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+        if key not in self._device_kernels:
+            self._device_kernels[key] = torch.as_tensor(K, dtype=torch.float64).contiguous().to(dev)
+        taps = self._device_kernels[key]
+        out = torch.empty((c, h // self.bin, w // self.bin), dtype=torch.float32, device=dev)
+        _l.call(dev, 'sunerf_instrument_correlate_bin', _ptr(planes), c, h, w, _ptr(taps), K.shape[0], K.shape[1], K.shape[2],
+                self.bin, ay, ax, self.scale, BOUNDARY[self.boundary], _ptr(out), _stream(dev))
+        return out
+
+    def flags(self, poisson: bool = True, read: bool = True) -> int:
+        saturate = bool(np.isfinite(self.saturation).any())
+        return (POISSON if poisson else 0) | (READ if read else 0) | (QUANTISE if self.quantise else 0) | (SATURATE if saturate else 0)
+
+    def noise(self, expected: torch.Tensor, seed: int, index_offset: int = 0, poisson: bool = True, read: bool = True,
+              want_sigma: bool = True, want_saturated: bool = True):
+        """The noise stage alone on ``expected`` [C, H, W] (image units): ``(image, sigma, saturated)``; element (c, r, k) draws
+        with the counter ``index_offset + (c H + r) W + k``."""
+        from .ops import _ptr, _stream
+        expected = self._planes(expected, 'Instrument.noise')
+        c, h, w = expected.shape
+        dev = expected.device
+        if not 0 <= int(seed) < 1 << 64 or int(index_offset) < 0:
+            raise ValueError('seed must fit 64 bits and index_offset be >= 0')
+        params = torch.as_tensor(self.params(c), dtype=torch.float64).to(dev)
+        image = torch.empty_like(expected)
+        sigma = torch.empty_like(expected) if want_sigma else None
+        saturated = torch.empty(expected.shape, dtype=torch.uint8, device=dev) if want_saturated else None
+        _l.call(dev, 'sunerf_instrument_noise', _ptr(expected), c, h, w, _ptr(params), ctypes.c_uint64(int(seed)), int(index_offset),
+                self.flags(poisson, read), _ptr(image), _ptr(sigma), _ptr(saturated), _stream(dev))
+        return image, sigma, saturated
+
+    def observe(self, planes: torch.Tensor, seed: int, index_offset: int = 0, poisson: bool = True, read: bool = True) -> dict:
+        """``planes`` [C, H, W] seen through the instrument: ``expected`` (blurred, binned, noise-free), ``image`` (one noisy
+        realisation of it, image units), ``sigma`` (its standard deviation from the expected count) and ``saturated`` (uint8),
+        each [C, H // bin, W // bin].  The same ``seed`` gives the same bits; ``index_offset`` places a tile in a larger frame."""
+        expected = self.expected(planes)
+        image, sigma, saturated = self.noise(expected, seed, index_offset, poisson, read)
+        return {'image': image, 'expected': expected, 'sigma': sigma, 'saturated': saturated}
+
+
+def philox(counters: torch.Tensor, key0: int, key1: int) -> torch.Tensor:
+    """Philox4x32-10 of ``counters`` [n, 4] (int32 / uint32 bit patterns, on the device) under the key: [n, 4], same dtype."""
+    from .ops import _ptr, _stream
+    if not counters.is_cuda:
+        raise _l.SunerfHipError('philox runs on a ROCm device (there is no CPU path)')
+    if counters.dim() != 2 or counters.shape[1] != 4 or counters.element_size() != 4:
+        raise ValueError(f'counters must be [n, 4] of 32-bit words, got {counters.dtype} {tuple(counters.shape)}')
+    counters = counters.contiguous()
+    out = torch.empty_like(counters)
+    _l.call(counters.device, 'sunerf_instrument_philox', _ptr(counters), counters.shape[0], int(key0) & 0xFFFFFFFF,
+            int(key1) & 0xFFFFFFFF, _ptr(out), _stream(counters.device))
+    return out

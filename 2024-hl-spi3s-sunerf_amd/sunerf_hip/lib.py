@@ -218,6 +218,21 @@ _PREP_SIGNATURES = {
 PREP_SYMBOLS = tuple(_PREP_SIGNATURES)
 PREP_ABI_VERSION = 1
 
+# The instrument table (include/sunerf_hip_instrument.h): PSF-and-bin correlation, detector noise, the Philox generator.  A fifth
+# table beside the four above, which stay as they are and keep their versions.
+_INSTRUMENT_SIGNATURES = {
+    'sunerf_instrument_abi_version': (ctypes.c_int, []),
+    'sunerf_instrument_correlate_bin': (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void, ctypes.c_int,
+                                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                        ctypes.c_double, ctypes.c_int, c_f32p, c_void]),
+    'sunerf_instrument_philox': (ctypes.c_int, [c_void, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint32, c_void, c_void]),
+    'sunerf_instrument_noise': (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void, ctypes.c_uint64,
+                                                ctypes.c_int64, ctypes.c_int, c_f32p, c_f32p, c_void, c_void]),
+}
+
+INSTRUMENT_SYMBOLS = tuple(_INSTRUMENT_SIGNATURES)
+INSTRUMENT_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -256,6 +271,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_prep_abi_version() != PREP_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so image-preparation ABI version mismatch')
+        for name, (res, args) in _INSTRUMENT_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_instrument_abi_version() != INSTRUMENT_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so instrument ABI version mismatch')
         _lib = lib
     return _lib
 

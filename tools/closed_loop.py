@@ -13,7 +13,15 @@ data fixture tests/golden/g9_simple_star.npz.  ``--module emission``: frames of 
 the training views seen from the held-out pose), scored as ``validation_metrics`` scores the model -- the same
 images, the MSE over all channels, the SSIM of channel 0 -- and printed next to the model's scores.
 
+``--instrument SPEC`` (``sunerf_hip.instrument.Instrument.from_spec``, e.g.
+``fwhm=2.5,bin=2,exposure=2.9,dn_per_photon=1.2,read_noise=1.2,unit=200``): the loop is run a second time with every training
+view rendered at ``bin`` times the frame's resolution and passed through the instrument -- PSF, binning, photon and read noise,
+seed = the view's index -- before ``ObservationSet.add_view``.  ``unit`` counts photons per second for an image value of one
+(the frames are of order one).  The held-out view stays the clean render, so its score says what the noise costs the
+reconstruction; it is printed next to the clean run's.
+
     python tools/closed_loop.py [--module dt|emission] [--views 8] [--size 64] [--steps 300] [--batch 2048] [--d-filter 256] [--baseline]
+                                [--instrument SPEC]
 """
 import argparse
 import json
@@ -33,7 +41,8 @@ from sunerf.model.sunerf import DensityTemperatureSuNeRFModule, EmissionSuNeRFMo
 from sunerf.rendering.density_temperature import DensityTemperatureRadiativeTransfer   # noqa: E402
 from sunerf_hip import ops                                                        # noqa: E402
 from sunerf_hip.feed import training_batches                                      # noqa: E402
-from sunerf_hip.observations import ObservationSet                                # noqa: E402
+from sunerf_hip.instrument import Instrument                                      # noqa: E402
+from sunerf_hip.observations import ObservationSet, hold_out_index, resampled_grid   # noqa: E402
 
 WL = [94., 131., 171., 193., 211., 304., 335.]
 
@@ -58,7 +67,17 @@ def baseline_scores(module, obs):
     return {'baseline.loss': loss.item(), 'baseline.ssim': scores['ssim'][0].item(), 'baseline.psnr': (-10. * torch.log10(loss)).item()}
 
 
-def density_temperature_problem(args, grid, poses):
+def observed_view(instrument, render, grid, index, n_views):
+    """``render(grid)`` -> planes (C, H, W) of view ``index`` on ``grid``; a training view of an instrument run is rendered
+    ``bin`` times finer over the same field of view and observed, the held-out view and a clean run are not."""
+    if instrument is None or index == hold_out_index(n_views):
+        return render(grid)
+    h, w = grid['shape']
+    fine = resampled_grid(grid, (h * instrument.bin, w * instrument.bin))
+    return instrument.observe(render(fine).contiguous(), seed=index)['image']
+
+
+def density_temperature_problem(args, grid, poses, instrument=None):
     fx = np.load(os.path.join(R, 'tests', 'golden', 'g9_simple_star.npz'))
     table = (fx['aia_logte'], fx['aia_tresp'])
     cfg = dict(sampling_config={'type': 'stratified', 'n_samples': 64, 'perturb': True},
@@ -74,8 +93,15 @@ def density_temperature_problem(args, grid, poses):
     first = truth.render_observer_image(poses[0][0], poses[0][1], 0.0, wl=np.array(WL), as_numpy=False)['image']
     scale = 1.0 / first.abs().max().item()           # images of order one, as the reference's loaders normalise them
     obs = ObservationSet(Rs_per_ds=1.0, seconds_per_dt=1.0, device='cuda')
-    for lat, lon in poses:
-        obs.add_rendered_view(truth, lat, lon, 0.0, wl=np.array(WL), scale=scale)
+    for index, (lat, lon) in enumerate(poses):
+        if instrument is None:
+            obs.add_rendered_view(truth, lat, lon, 0.0, wl=np.array(WL), scale=scale)
+            continue
+
+        def render(g):
+            frame = truth.render_observer_image(lat, lon, 0.0, wl=np.array(WL), resolution=g['shape'], as_numpy=False)['image']
+            return frame.permute(2, 0, 1) * scale
+        obs.add_view(observed_view(instrument, render, grid, index, len(poses)), lat, lon, time=0.0, grid=grid, wavelengths=np.array(WL))
     module = DensityTemperatureSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={}, model=NeRF_DT,
                                             pixel_intensity_factor=1e10, response_table=table,
                                             model_config={'d_filter': args.d_filter},
@@ -84,16 +110,18 @@ def density_temperature_problem(args, grid, poses):
     return obs, module
 
 
-def emission_problem(args, grid, poses):
+def emission_problem(args, grid, poses, instrument=None):
     from sunerf.evaluation.loader import linear_plate_scale_axes
     from sunerf_hip.rays import grid_rays, pose_spherical
     obs = ObservationSet(Rs_per_ds=1.0, seconds_per_dt=1.0, device='cuda')
-    tx, ty = linear_plate_scale_axes(grid, None, 'cuda')
-    for lat, lon in poses:
-        o, d = grid_rays(tx, ty, pose_spherical(-lon, lat, 215.03215567054764))
-        b = torch.linalg.cross(o, d).norm(dim=-1) / d.norm(dim=-1)                        # impact parameter in solar radii
-        image = torch.where(b < 1, 0.25 * torch.sqrt((1 - b * b).clamp_min(0)) + 0.06, 0.06 * torch.exp(-(b - 1) / 0.12))
-        obs.add_view(image.reshape(args.size, args.size), lat, lon, time=0.0, grid=grid)
+    for index, (lat, lon) in enumerate(poses):
+        def render(g):
+            tx, ty = linear_plate_scale_axes(g, None, 'cuda')
+            o, d = grid_rays(tx, ty, pose_spherical(-lon, lat, 215.03215567054764))
+            b = torch.linalg.cross(o, d).norm(dim=-1) / d.norm(dim=-1)                    # impact parameter in solar radii
+            image = torch.where(b < 1, 0.25 * torch.sqrt((1 - b * b).clamp_min(0)) + 0.06, 0.06 * torch.exp(-(b - 1) / 0.12))
+            return image.reshape(1, *g['shape'])
+        obs.add_view(observed_view(instrument, render, grid, index, len(poses))[0], lat, lon, time=0.0, grid=grid)
     module = EmissionSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={'vmax': 1, 'a': 0.005},
                                   sampling_config={'type': 'stratified', 'n_samples': 64, 'perturb': True},
                                   hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 128, 'perturb': True},
@@ -111,12 +139,25 @@ def main():
     ap.add_argument('--batch', type=int, default=2048)
     ap.add_argument('--d-filter', type=int, default=256)
     ap.add_argument('--baseline', action='store_true')
+    ap.add_argument('--instrument', metavar='SPEC', default=None)
     args = ap.parse_args()
-    torch.manual_seed(0)
     grid = {'shape': (args.size, args.size), 'cdelt': (2.2 * 960. / args.size, 2.2 * 960. / args.size),
             'meta': {'t_obs': '2022-01-01T00:00:00.000'}}
     poses = [(0.1 * (k % 3 - 1), 0.3 - 6.2832 / args.views * k) for k in range(args.views)]
-    obs, module = (density_temperature_problem if args.module == 'dt' else emission_problem)(args, grid, poses)
+    report = run(args, grid, poses, None)
+    if args.instrument is not None:
+        seen = run(args, grid, poses, Instrument.from_spec(args.instrument))
+        print(f"held-out view {seen['held_out'][0]}: clean views PSNR {report['after']['validation.psnr']:.2f} dB, SSIM "
+              f"{report['after']['validation.ssim']:.4f}; through the instrument ({args.instrument}) PSNR "
+              f"{seen['after']['validation.psnr']:.2f} dB, SSIM {seen['after']['validation.ssim']:.4f}", file=sys.stderr)
+        report['instrument'] = {'spec': args.instrument, **{k: seen[k] for k in ('loss_first_10', 'loss_last_10', 'train_seconds',
+                                                                                  'before', 'after')}}
+    print(json.dumps({'closed_loop': report}))
+
+
+def run(args, grid, poses, instrument):
+    torch.manual_seed(0)
+    obs, module = (density_temperature_problem if args.module == 'dt' else emission_problem)(args, grid, poses, instrument)
     obs.hold_out('reference')
     pool = obs.pool(batch_size=args.batch, seed=0, reshuffle='rays')
     module.strict_finite_check = False
@@ -129,14 +170,14 @@ def main():
     module.check_finite(module.optimizer)
     after = held_out_scores(module, obs, 1 << 14)
     baseline = baseline_scores(module, obs) if args.baseline else None
-    if baseline is not None:
+    if baseline is not None and instrument is None:
         print(f"held-out view {obs.held_out[0]}: model PSNR {after['validation.psnr']:.2f} dB, SSIM {after['validation.ssim']:.4f}; "
               f"reprojection baseline PSNR {baseline['baseline.psnr']:.2f} dB, SSIM {baseline['baseline.ssim']:.4f}", file=sys.stderr)
-    print(json.dumps({'closed_loop': {
+    return {
         'module': args.module, 'views': args.views, 'held_out': obs.held_out, 'size': args.size, 'channels': pool.data['target_image'].shape[1], 'training_rays': pool.n_rays,
         'steps': args.steps, 'batch': args.batch, 'd_filter': args.d_filter, 'epochs_built': pool.built_epoch + 1,
         'loss_first_10': losses[:10].mean().item(), 'loss_last_10': losses[-10:].mean().item(), 'train_seconds': seconds,
-        'before': before, 'after': after, **({} if baseline is None else {'baseline': baseline})}}))
+        'before': before, 'after': after, **({} if baseline is None else {'baseline': baseline})}
 
 
 if __name__ == '__main__':

@@ -1,0 +1,90 @@
+"""Cost of the instrument model (csrc/instrument.hip, sunerf_hip.instrument) on a 1024^2 x 7 and a 4096^2 x 1 frame, Gaussian PSFs
+of 9^2 and 33^2 taps, bin 1 and 2, next to scipy.signal.fftconvolve and numpy.random.Generator.poisson on the host.
+
+Per frame, PSF and bin: milliseconds of the PSF-and-bin correlation and of the noise kernel (Poisson + read noise + quantise on
+the binned frame, a signal of 0.1 to 1000 photons so that both samplers run; CUDA-event median over ``--repeats`` windows of
+``--calls`` back-to-back calls, after a warm-up), the fp64 multiply-adds of the correlation -- output pixels times effective taps
+-- and the rate they imply, and -- unless ``--no-host`` -- the wall time of ``fftconvolve(mode='same')`` + a block mean per plane
+with ``--threads`` host threads, one plane per thread, and of ``Generator.poisson`` + ``standard_normal`` on the binned frame.
+One JSON line.
+
+    python tools/instrument_time.py [--repeats 5] [--calls 5] [--threads 16] [--no-host]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, '2024-hl-spi3s-sunerf_amd')]
+
+
+def _timed(fn, repeats, calls):
+    fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(repeats):
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(calls):
+            fn()
+        stop.record()
+        torch.cuda.synchronize()
+        times.append(start.elapsed_time(stop) / calls)
+    return sorted(times)[len(times) // 2]
+
+
+def measure(c, n, taps, b, repeats, calls, threads, with_host):
+    from sunerf_hip.instrument import Instrument, gaussian_psf
+    g = torch.Generator(device='cuda').manual_seed(n + taps + b)
+    frame = 10.0 ** (torch.rand(c, n, n, device='cuda', generator=g) * 4.0 - 1.0)
+    psf = gaussian_psf(taps / 4.0, taps // 2)
+    inst = Instrument(psf=psf, bin=b, read_noise=1.2, dn_per_photon=1.2, exposure=2.9, unit=1.0 / 2.9, quantise=True)
+    expected = inst.expected(frame)
+    K, _ = inst.effective_kernel()
+    macs = expected.numel() * K.shape[1] * K.shape[2]
+    row = {'shape': [c, n, n], 'psf': [taps, taps], 'bin': b, 'effective_kernel': list(K.shape[1:])}
+    ms = _timed(lambda: inst.expected(frame), repeats, calls)
+    row['correlate_bin'] = {'ms': ms, 'fp64_multiply_adds': macs, 'G_multiply_adds_per_s': macs / ms / 1e6}
+    ms = _timed(lambda: inst.noise(expected, seed=1), repeats, calls)
+    row['noise'] = {'ms': ms, 'elements': expected.numel(), 'G_elements_per_s': expected.numel() / ms / 1e6}
+    if with_host:
+        from scipy import signal
+        host = frame.cpu().numpy().astype(np.float64)
+
+        def one(p):
+            full = signal.fftconvolve(p, psf, mode='same')
+            return full.reshape(n // b, b, n // b, b).mean((1, 3))
+        t0 = time.perf_counter()
+        with ThreadPoolExecutor(max_workers=threads) as pool:
+            planes = np.stack(list(pool.map(one, host)))
+        t1 = time.perf_counter()
+        rng = np.random.default_rng(1)
+        lam = np.maximum(planes, 0.0)
+        rng.poisson(lam) * 1.2 + 1.2 * rng.standard_normal(lam.shape)
+        t2 = time.perf_counter()
+        row['host'] = {'threads': min(threads, c), 'fftconvolve_and_bin_ms': (t1 - t0) * 1e3, 'poisson_and_normal_ms': (t2 - t1) * 1e3}
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--calls', type=int, default=5)
+    ap.add_argument('--threads', type=int, default=16)
+    ap.add_argument('--no-host', action='store_true')
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('instrument_time.py needs a ROCm device')
+    rows = [measure(c, n, taps, b, args.repeats, args.calls, args.threads, not args.no_host)
+            for c, n in ((7, 1024), (1, 4096)) for taps in (9, 33) for b in (1, 2)]
+    print(json.dumps({'instrument_time': rows}))
+
+
+if __name__ == '__main__':
+    main()
