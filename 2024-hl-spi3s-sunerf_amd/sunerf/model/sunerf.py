@@ -179,6 +179,19 @@ def _other_outputs(outputs):
     return [v for k, v in outputs.items() if k not in skip]
 
 
+def _observed_windows(tracing, outputs):
+    """The patch branch of a training step: the rendered windows seen through the batch's instrument.
+    ``(coarse, fine, target)`` as ``[n P P, C]`` detector pixels; the regularization stays that of all rendered rays."""
+    spec = tracing['patch']
+    n, hw, ww, instrument = spec['n'], spec['hw'], spec['ww'], spec['instrument']
+
+    def observe(image):
+        windows = image.reshape(n, hw, ww, -1).permute(0, 3, 1, 2).contiguous()
+        return instrument.expected_windows(windows).permute(0, 2, 3, 1).reshape(-1, windows.shape[1])
+    target = tracing['target_image'].permute(0, 2, 3, 1).reshape(-1, spec['C'])
+    return observe(outputs['coarse_image']), observe(outputs['fine_image']), target.contiguous()
+
+
 def save_state(sunerf: BaseSuNeRFModule, data_module, save_path):
     """sunerf.py:62-74: pickles the rendering module + data configuration (the ``.snf`` file)."""
     output_path = '/'.join(save_path.split('/')[0:-1])
@@ -216,6 +229,14 @@ class EmissionSuNeRFModule(BaseSuNeRFModule):
     def training_step(self, batch, batch_nb):
         tracing = batch['tracing']
         rays, time, target_image = tracing['rays'], tracing['time'], tracing['target_image']
+        if 'patch' in tracing:          # windows of detector-pixel patches: the loss compares instrument(render) with the target
+            rays = rays.reshape(-1, 2, 3)
+            outputs = self.rendering(rays[:, 0].contiguous(), rays[:, 1].contiguous(), time)
+            coarse, fine, target = _observed_windows(tracing, outputs)
+            loss, stats = training_loss(coarse, fine, target, outputs['regularization'], self.lambda_image,
+                                        self.lambda_regularization, asinh_scaling=self._asinh_constants(),
+                                        finite_check=_other_outputs(outputs))
+            return self._finish_step(self._with_smoothness(loss), stats)
         rays_o, rays_d = rays[:, 0].contiguous(), rays[:, 1].contiguous()
         outputs = self.rendering(rays_o, rays_d, time)
         # sunerf.py:105-125 in one kernel: finite check of all outputs, asinh scaling, 2 x MSE, regularization mean, psnr
@@ -270,8 +291,14 @@ class DensityTemperatureSuNeRFModule(BaseSuNeRFModule):
         tracing = batch['tracing']
         rays, time, target_image, wavelengths = (tracing['rays'], tracing['time'], tracing['target_image'],
                                                  tracing['wavelength'])
-        rays_o, rays_d = rays[:, 0].contiguous(), rays[:, 1].contiguous()
-        outputs = self.rendering.forward(rays_o, rays_d, time, wavelengths)
+        if 'patch' in tracing:          # windows of detector-pixel patches: the loss compares instrument(render) with the target
+            rays = rays.reshape(-1, 2, 3)
+            outputs = self.rendering.forward(rays[:, 0].contiguous(), rays[:, 1].contiguous(), time, wavelengths)
+            coarse, fine, target_image = _observed_windows(tracing, outputs)
+            outputs = {**outputs, 'coarse_image': coarse, 'fine_image': fine}
+        else:
+            rays_o, rays_d = rays[:, 0].contiguous(), rays[:, 1].contiguous()
+            outputs = self.rendering.forward(rays_o, rays_d, time, wavelengths)
         if not isinstance(self.loss, nn.MSELoss) or self.loss.reduction != 'mean':
             return self._training_step_generic_loss(outputs, target_image)
         loss, stats = training_loss(outputs['coarse_image'], outputs['fine_image'], target_image,

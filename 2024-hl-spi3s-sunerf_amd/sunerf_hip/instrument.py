@@ -200,23 +200,70 @@ class Instrument:
             raise ValueError(f'{what}: planes must be float32 [C, H, W], got {planes.dtype} {tuple(planes.shape)}')
         return planes.contiguous()
 
+    def _taps(self, K: np.ndarray, dev, repeat: int = 1) -> torch.Tensor:
+        """``K`` on the device (fp64), ``repeat`` copies of its kernels in a row; kept per device and stream."""
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream) if repeat == 1 else \
+            (dev, torch.cuda.current_stream(dev).cuda_stream, repeat)
+        if key not in self._device_kernels:
+            taps = torch.as_tensor(K, dtype=torch.float64).contiguous().to(dev)
+            self._device_kernels[key] = taps if repeat == 1 else taps.repeat(repeat, 1, 1).contiguous()
+        return self._device_kernels[key]
+
     def expected(self, planes: torch.Tensor) -> torch.Tensor:
-        """``[C, H // bin, W // bin]`` float32: ``planes`` [C, H, W] blurred by the PSF and binned, noise-free."""
-        from .ops import _ptr, _stream
+        """``[C, H // bin, W // bin]`` float32: ``planes`` [C, H, W] blurred by the PSF and binned, noise-free.  Differentiable
+        with respect to ``planes``: the backward is ``sunerf_patch_correlate_bin_adjoint`` with the same kernel, anchor, scale
+        and boundary (the PSF itself takes no gradient)."""
         planes = self._planes(planes, 'Instrument.expected')
-        c, h, w = planes.shape
+        c = planes.shape[0]
         K, (ay, ax) = self.effective_kernel()
         if K.shape[0] not in (1, c):
             raise ValueError(f'the psf has {K.shape[0]} channels, the frame {c}')
-        dev = planes.device
-        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-        if key not in self._device_kernels:
-            self._device_kernels[key] = torch.as_tensor(K, dtype=torch.float64).contiguous().to(dev)
-        taps = self._device_kernels[key]
-        out = torch.empty((c, h // self.bin, w // self.bin), dtype=torch.float32, device=dev)
-        _l.call(dev, 'sunerf_instrument_correlate_bin', _ptr(planes), c, h, w, _ptr(taps), K.shape[0], K.shape[1], K.shape[2],
-                self.bin, ay, ax, self.scale, BOUNDARY[self.boundary], _ptr(out), _stream(dev))
-        return out
+        call = (self._taps(K, planes.device), K.shape[0], K.shape[1], K.shape[2], self.bin, ay, ax, self.scale,
+                BOUNDARY[self.boundary])
+        if torch.is_grad_enabled() and planes.requires_grad:
+            return _CorrelateBin.apply(planes, *call)
+        return _correlate_bin(planes, *call)
+
+    def window_shape(self, patch: int) -> Tuple[int, int]:
+        """``(hw, ww)``: the sub-pixels a patch of ``patch x patch`` detector pixels reads, halo included."""
+        K, _ = self.effective_kernel()
+        return (int(patch) - 1) * self.bin + K.shape[1], (int(patch) - 1) * self.bin + K.shape[2]
+
+    def expected_windows(self, windows: torch.Tensor) -> torch.Tensor:
+        """``[n, C, P, P]`` float32: the VALID correlation of ``windows`` [n, C, hw, ww] that carry their full halo,
+        ``(hw, ww) = window_shape(P)`` -- detector pixel (r, c) of a window reads its sub-pixels
+        ``[r bin, r bin + kh) x [c bin, c bin + kw)`` and nothing past its edge, so no boundary rule takes part.
+        Differentiable with respect to ``windows``.  The forward correlation with anchor (0, 0) over the ``n C`` planes; its
+        surplus output rows and columns (those whose taps leave the window) are cropped and take no gradient.  A per-channel
+        PSF is expanded to one kernel per plane."""
+        if not isinstance(windows, torch.Tensor):
+            raise TypeError('Instrument.expected_windows: windows must be a torch.Tensor')
+        if not windows.is_cuda:
+            raise _l.SunerfHipError('Instrument.expected_windows runs on a ROCm device (there is no CPU path)')
+        if windows.dim() != 4 or windows.dtype != torch.float32:
+            raise ValueError(f'Instrument.expected_windows: windows must be float32 [n, C, hw, ww], got {windows.dtype} '
+                             f'{tuple(windows.shape)}')
+        n, c, hw, ww = windows.shape
+        K, _ = self.effective_kernel()
+        if K.shape[0] not in (1, c):
+            raise ValueError(f'the psf has {K.shape[0]} channels, the windows {c}')
+        kh, kw = K.shape[1:]
+        b = self.bin
+        if hw < kh or ww < kw or (hw - kh) % b or (ww - kw) % b or (hw - kh) // b != (ww - kw) // b:
+            raise ValueError(f'windows of {hw} x {ww} sub-pixels are no ((P - 1) {b} + {kh}) x ((P - 1) {b} + {kw}) window of a '
+                             'P x P patch')
+        p = (hw - kh) // b + 1
+        if n == 0:
+            return windows.new_zeros((0, c, p, p))
+        per_plane = K.shape[0] > 1
+        call = (self._taps(K, windows.device, n if per_plane else 1), n * c if per_plane else 1, kh, kw, b, 0, 0, self.scale,
+                BOUNDARY['zero'])
+        planes = windows.contiguous().view(n * c, hw, ww)
+        if torch.is_grad_enabled() and planes.requires_grad:
+            out = _CorrelateBin.apply(planes, *call)
+        else:
+            out = _correlate_bin(planes, *call)
+        return out[:, :p, :p].reshape(n, c, p, p)
 
     def flags(self, poisson: bool = True, read: bool = True) -> int:
         saturate = bool(np.isfinite(self.saturation).any())
@@ -247,6 +294,47 @@ class Instrument:
         expected = self.expected(planes)
         image, sigma, saturated = self.noise(expected, seed, index_offset, poisson, read)
         return {'image': image, 'expected': expected, 'sigma': sigma, 'saturated': saturated}
+
+
+def _correlate_bin(planes, taps, n_kernels, kh, kw, bin_factor, ay, ax, scale, boundary):
+    from .ops import _ptr, _stream
+    c, h, w = planes.shape
+    dev = planes.device
+    out = torch.empty((c, h // bin_factor, w // bin_factor), dtype=torch.float32, device=dev)
+    _l.call(dev, 'sunerf_instrument_correlate_bin', _ptr(planes), c, h, w, _ptr(taps), n_kernels, kh, kw, bin_factor, ay, ax,
+            scale, boundary, _ptr(out), _stream(dev))
+    return out
+
+
+def correlate_bin_adjoint(g_out, height, width, taps, n_kernels, kh, kw, bin_factor, ay, ax, scale, boundary):
+    """``g_in`` [C, height, width] float32: the transpose of the strided correlation applied to ``g_out``
+    [C, height // bin, width // bin] (``sunerf_patch_correlate_bin_adjoint``)."""
+    from .ops import _ptr, _stream
+    c = g_out.shape[0]
+    dev = g_out.device
+    if tuple(g_out.shape) != (c, height // bin_factor, width // bin_factor) or g_out.dtype != torch.float32:
+        raise ValueError(f'g_out must be float32 [{c}, {height // bin_factor}, {width // bin_factor}], got {g_out.dtype} '
+                         f'{tuple(g_out.shape)}')
+    if g_out.numel() == 0:          # the empty call writes nothing: no detector pixel, no gradient
+        return torch.zeros((c, height, width), dtype=torch.float32, device=dev)
+    g_out = g_out.contiguous()
+    g_in = torch.empty((c, height, width), dtype=torch.float32, device=dev)
+    _l.call(dev, 'sunerf_patch_correlate_bin_adjoint', _ptr(g_out), c, height, width, _ptr(taps), n_kernels, kh, kw, bin_factor,
+            ay, ax, scale, boundary, _ptr(g_in), _stream(dev))
+    return g_in
+
+
+class _CorrelateBin(torch.autograd.Function):
+    """The strided correlation with its adjoint as the backward; the kernel is a constant."""
+
+    @staticmethod
+    def forward(ctx, planes, *call):
+        ctx.call, ctx.frame = call, tuple(planes.shape[1:])
+        return _correlate_bin(planes, *call)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (correlate_bin_adjoint(g.to(torch.float32), *ctx.frame, *ctx.call),) + (None,) * len(ctx.call)
 
 
 def philox(counters: torch.Tensor, key0: int, key1: int) -> torch.Tensor:

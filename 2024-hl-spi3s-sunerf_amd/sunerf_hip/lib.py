@@ -233,6 +233,20 @@ _INSTRUMENT_SIGNATURES = {
 INSTRUMENT_SYMBOLS = tuple(_INSTRUMENT_SIGNATURES)
 INSTRUMENT_ABI_VERSION = 1
 
+# The patch table (include/sunerf_hip_patch.h): the adjoint of the PSF-and-bin correlation and the records of a batch of patches.
+# A sixth table beside the five above, which stay as they are and keep their versions.
+_PATCH_SIGNATURES = {
+    'sunerf_patch_abi_version': (ctypes.c_int, []),
+    'sunerf_patch_correlate_bin_adjoint': (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void, ctypes.c_int,
+                                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                           ctypes.c_double, ctypes.c_int, c_f32p, c_void]),
+    'sunerf_patch_records': (ctypes.c_int, [c_void, ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_void]),
+}
+
+PATCH_SYMBOLS = tuple(_PATCH_SIGNATURES)
+PATCH_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -277,6 +291,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_instrument_abi_version() != INSTRUMENT_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so instrument ABI version mismatch')
+        for name, (res, args) in _PATCH_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_patch_abi_version() != PATCH_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so patch ABI version mismatch')
         _lib = lib
     return _lib
 

@@ -348,6 +348,18 @@ class ObservationSet:
         return ObservationPool(self._table(self.training_views, drop_nonfinite), not self._single, batch_size, rank, world,
                                seed, reshuffle, drop_last)
 
+    def patch_pool(self, instrument, patch: int = 16, patches_per_batch=None, rank: int = 0, world: int = 1, seed: int = 0):
+        """The training views as a :class:`sunerf_hip.patch.PatchPool` for training THROUGH ``instrument``:
+        patches of ``patch x patch`` detector pixels on the lattice 0, P, 2 P, ... of every view, the last patch of an axis
+        shifted inward so that it ends at the edge (every pixel is covered, a few twice); a view smaller than ``patch`` raises.
+        Patches whose target holds a non-finite value are dropped and counted (``pool.dropped``).  Epoch ``e`` visits the
+        patches in the order ``np.random.default_rng([seed, e]).permutation(n_patches)``, rank ``r`` taking ``[r::world]``:
+        ranks need nothing from each other.  ``patches_per_batch``: default what brings a batch nearest to 8192 rays.  The
+        views must have uniform 1-d axes and ``downscale == 1`` (the instrument's ``bin`` does the averaging)."""
+        from .patch import PatchPool
+        return PatchPool([self.views[i] for i in self.training_views], instrument, self.device, not self._single, patch,
+                         patches_per_batch, rank, world, seed)
+
     def validation_batches(self, batch_size: int = 2 ** 13) -> List[dict]:
         """One entry per held-out view: ``{'name', 'index', 'image_shape': (H, W), 'batches': [...]}`` with the view's rays in
         pixel order (nothing dropped, nothing shuffled) as the batch dicts ``validation_step`` reads; ``image_shape`` is

@@ -20,8 +20,17 @@ seed = the view's index -- before ``ObservationSet.add_view``.  ``unit`` counts 
 (the frames are of order one).  The held-out view stays the clean render, so its score says what the noise costs the
 reconstruction; it is printed next to the clean run's.
 
+``--through-instrument`` (with ``--instrument``): a third run trains on the same observed views THROUGH the instrument
+(DESIGN.md 8p): ``ObservationSet.patch_pool`` hands out patches of ``--patch`` detector pixels as the rays of their sub-pixel
+windows, PSF halo included, and the loss compares ``instrument(render)`` with the observed pixels -- forward-model deconvolution.
+A step renders ``patches_per_batch hw ww`` rays (``rays_per_step`` in the report) against ``--batch`` of the ray runs;
+``--through-steps`` sets its step count apart from ``--steps`` for a comparison at equal rays rendered.  Every instrument run is
+also scored on the clean held-out view rendered at ``bin`` times the resolution (``after_fine``): what the model knows about the
+scene in front of the telescope.
+
     python tools/closed_loop.py [--module dt|emission] [--views 8] [--size 64] [--steps 300] [--batch 2048] [--d-filter 256] [--baseline]
-                                [--instrument SPEC]
+                                [--instrument SPEC [--through-instrument] [--patch 16] [--patches-per-batch N] [--through-steps K]]
+                                [--skip-clean]
 """
 import argparse
 import json
@@ -93,41 +102,59 @@ def density_temperature_problem(args, grid, poses, instrument=None):
     first = truth.render_observer_image(poses[0][0], poses[0][1], 0.0, wl=np.array(WL), as_numpy=False)['image']
     scale = 1.0 / first.abs().max().item()           # images of order one, as the reference's loaders normalise them
     obs = ObservationSet(Rs_per_ds=1.0, seconds_per_dt=1.0, device='cuda')
+
+    def render_of(lat, lon):
+        def render(g):
+            frame = truth.render_observer_image(lat, lon, 0.0, wl=np.array(WL), resolution=g['shape'], as_numpy=False)['image']
+            return frame.permute(2, 0, 1) * scale
+        return render
     for index, (lat, lon) in enumerate(poses):
         if instrument is None:
             obs.add_rendered_view(truth, lat, lon, 0.0, wl=np.array(WL), scale=scale)
             continue
-
-        def render(g):
-            frame = truth.render_observer_image(lat, lon, 0.0, wl=np.array(WL), resolution=g['shape'], as_numpy=False)['image']
-            return frame.permute(2, 0, 1) * scale
-        obs.add_view(observed_view(instrument, render, grid, index, len(poses)), lat, lon, time=0.0, grid=grid, wavelengths=np.array(WL))
+        obs.add_view(observed_view(instrument, render_of(lat, lon), grid, index, len(poses)), lat, lon, time=0.0, grid=grid,
+                     wavelengths=np.array(WL))
     module = DensityTemperatureSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={}, model=NeRF_DT,
                                             pixel_intensity_factor=1e10, response_table=table,
                                             model_config={'d_filter': args.d_filter},
                                             lr_config={'start': 5e-4, 'end': 5e-5, 'iterations': args.steps},
                                             **{k: dict(v) for k, v in cfg.items()}).cuda()
-    return obs, module
+    return obs, module, render_of, np.array(WL)
 
 
 def emission_problem(args, grid, poses, instrument=None):
     from sunerf.evaluation.loader import linear_plate_scale_axes
     from sunerf_hip.rays import grid_rays, pose_spherical
     obs = ObservationSet(Rs_per_ds=1.0, seconds_per_dt=1.0, device='cuda')
-    for index, (lat, lon) in enumerate(poses):
+
+    def render_of(lat, lon):
         def render(g):
             tx, ty = linear_plate_scale_axes(g, None, 'cuda')
             o, d = grid_rays(tx, ty, pose_spherical(-lon, lat, 215.03215567054764))
             b = torch.linalg.cross(o, d).norm(dim=-1) / d.norm(dim=-1)                    # impact parameter in solar radii
             image = torch.where(b < 1, 0.25 * torch.sqrt((1 - b * b).clamp_min(0)) + 0.06, 0.06 * torch.exp(-(b - 1) / 0.12))
             return image.reshape(1, *g['shape'])
-        obs.add_view(observed_view(instrument, render, grid, index, len(poses))[0], lat, lon, time=0.0, grid=grid)
+        return render
+    for index, (lat, lon) in enumerate(poses):
+        obs.add_view(observed_view(instrument, render_of(lat, lon), grid, index, len(poses))[0], lat, lon, time=0.0, grid=grid)
     module = EmissionSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={'vmax': 1, 'a': 0.005},
                                   sampling_config={'type': 'stratified', 'n_samples': 64, 'perturb': True},
                                   hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 128, 'perturb': True},
                                   model_config={'d_filter': args.d_filter},
                                   lr_config={'start': 5e-4, 'end': 5e-5, 'iterations': args.steps}).cuda()
-    return obs, module
+    return obs, module, render_of, None
+
+
+def fine_scores(module, render, grid, pose, wavelengths, factor, batch_size):
+    """The held-out pose rendered clean at ``factor`` times the resolution over the same field of view, scored like the
+    held-out view itself."""
+    h, w = grid['shape']
+    fine = resampled_grid(grid, (h * factor, w * factor))
+    obs = ObservationSet(Rs_per_ds=1.0, seconds_per_dt=1.0, device='cuda')
+    planes = render(fine).contiguous()
+    obs.add_view(planes if wavelengths is not None else planes[0], pose[0], pose[1], time=0.0, grid=fine, wavelengths=wavelengths)
+    obs.hold_out(0)
+    return held_out_scores(module, obs, batch_size)
 
 
 def main():
@@ -140,44 +167,77 @@ def main():
     ap.add_argument('--d-filter', type=int, default=256)
     ap.add_argument('--baseline', action='store_true')
     ap.add_argument('--instrument', metavar='SPEC', default=None)
+    ap.add_argument('--through-instrument', action='store_true', help='a third run trained on patches through the instrument')
+    ap.add_argument('--patch', type=int, default=16, help='detector pixels per patch and axis')
+    ap.add_argument('--patches-per-batch', type=int, default=None, help='default: what brings a batch nearest to 8192 rays')
+    ap.add_argument('--through-steps', type=int, default=None, help='steps of the through-instrument run (default: --steps)')
+    ap.add_argument('--skip-clean', action='store_true', help='leave out the run on clean views')
     args = ap.parse_args()
+    if args.through_instrument and args.instrument is None:
+        ap.error('--through-instrument needs --instrument SPEC')
     grid = {'shape': (args.size, args.size), 'cdelt': (2.2 * 960. / args.size, 2.2 * 960. / args.size),
             'meta': {'t_obs': '2022-01-01T00:00:00.000'}}
     poses = [(0.1 * (k % 3 - 1), 0.3 - 6.2832 / args.views * k) for k in range(args.views)]
-    report = run(args, grid, poses, None)
+    report = {} if args.skip_clean else run(args, grid, poses, None)
     if args.instrument is not None:
+        keys = ('steps', 'rays_per_step', 'loss_first_10', 'loss_last_10', 'train_seconds', 'before', 'after', 'after_fine')
         seen = run(args, grid, poses, Instrument.from_spec(args.instrument))
-        print(f"held-out view {seen['held_out'][0]}: clean views PSNR {report['after']['validation.psnr']:.2f} dB, SSIM "
-              f"{report['after']['validation.ssim']:.4f}; through the instrument ({args.instrument}) PSNR "
+        clean = '' if args.skip_clean else (f"clean views PSNR {report['after']['validation.psnr']:.2f} dB, SSIM "
+                                            f"{report['after']['validation.ssim']:.4f}; ")
+        print(f"held-out view {seen['held_out'][0]}: {clean}views seen through the instrument ({args.instrument}) PSNR "
               f"{seen['after']['validation.psnr']:.2f} dB, SSIM {seen['after']['validation.ssim']:.4f}", file=sys.stderr)
-        report['instrument'] = {'spec': args.instrument, **{k: seen[k] for k in ('loss_first_10', 'loss_last_10', 'train_seconds',
-                                                                                  'before', 'after')}}
+        report['instrument'] = {'spec': args.instrument, **{k: seen[k] for k in keys}}
+        if args.through_instrument:
+            through = run(args, grid, poses, Instrument.from_spec(args.instrument), through=True)
+            print(f"trained through the instrument, {through['steps']} steps of {through['rays_per_step']} rays: PSNR "
+                  f"{through['after']['validation.psnr']:.2f} dB, SSIM {through['after']['validation.ssim']:.4f}; at bin times the "
+                  f"resolution {through['after_fine']['validation.psnr']:.2f} dB against {seen['after_fine']['validation.psnr']:.2f} dB "
+                  f"of ray training ({seen['steps']} steps of {seen['rays_per_step']} rays)", file=sys.stderr)
+            report['through_instrument'] = {k: through[k] for k in keys + ('patch', 'patches', 'dropped', 'halo_overhead')}
     print(json.dumps({'closed_loop': report}))
 
 
-def run(args, grid, poses, instrument):
+def run(args, grid, poses, instrument, through=False):
     torch.manual_seed(0)
-    obs, module = (density_temperature_problem if args.module == 'dt' else emission_problem)(args, grid, poses, instrument)
+    problem = density_temperature_problem if args.module == 'dt' else emission_problem
+    obs, module, render_of, wavelengths = problem(args, grid, poses, instrument)
     obs.hold_out('reference')
-    pool = obs.pool(batch_size=args.batch, seed=0, reshuffle='rays')
+    steps = args.steps
+    if through:
+        steps = args.steps if args.through_steps is None else args.through_steps
+        pool = obs.patch_pool(instrument, patch=args.patch, patches_per_batch=args.patches_per_batch, seed=0)
+        rays_per_step = pool.rays_per_batch
+    else:
+        pool = obs.pool(batch_size=args.batch, seed=0, reshuffle='rays')
+        rays_per_step = args.batch
     module.strict_finite_check = False
     before = held_out_scores(module, obs, 1 << 14)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    losses = torch.stack(fit_steps(module, training_batches(pool, args.steps)))
+    losses = torch.stack(fit_steps(module, training_batches(pool, steps)))
     torch.cuda.synchronize()
     seconds = time.perf_counter() - t0
     module.check_finite(module.optimizer)
     after = held_out_scores(module, obs, 1 << 14)
+    extra = {}
+    if instrument is not None:
+        held = obs.held_out[0]
+        extra['after_fine'] = fine_scores(module, render_of(*poses[held]), grid, poses[held], wavelengths, instrument.bin, 1 << 14)
+    if through:
+        extra.update(patch=pool.patch, patches=pool.n_patches, dropped=pool.dropped, halo_overhead=pool.halo_overhead)
+        return {'held_out': obs.held_out, 'steps': steps, 'rays_per_step': rays_per_step,
+                'loss_first_10': losses[:10].mean().item(), 'loss_last_10': losses[-10:].mean().item(), 'train_seconds': seconds,
+                'before': before, 'after': after, **extra}
     baseline = baseline_scores(module, obs) if args.baseline else None
     if baseline is not None and instrument is None:
         print(f"held-out view {obs.held_out[0]}: model PSNR {after['validation.psnr']:.2f} dB, SSIM {after['validation.ssim']:.4f}; "
               f"reprojection baseline PSNR {baseline['baseline.psnr']:.2f} dB, SSIM {baseline['baseline.ssim']:.4f}", file=sys.stderr)
     return {
         'module': args.module, 'views': args.views, 'held_out': obs.held_out, 'size': args.size, 'channels': pool.data['target_image'].shape[1], 'training_rays': pool.n_rays,
-        'steps': args.steps, 'batch': args.batch, 'd_filter': args.d_filter, 'epochs_built': pool.built_epoch + 1,
+        'steps': args.steps, 'rays_per_step': rays_per_step, 'batch': args.batch, 'd_filter': args.d_filter,
+        'epochs_built': pool.built_epoch + 1,
         'loss_first_10': losses[:10].mean().item(), 'loss_last_10': losses[-10:].mean().item(), 'train_seconds': seconds,
-        'before': before, 'after': after, **({} if baseline is None else {'baseline': baseline})}
+        'before': before, 'after': after, **extra, **({} if baseline is None else {'baseline': baseline})}
 
 
 if __name__ == '__main__':

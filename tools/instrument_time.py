@@ -6,9 +6,12 @@ the binned frame, a signal of 0.1 to 1000 photons so that both samplers run; CUD
 ``--calls`` back-to-back calls, after a warm-up), the fp64 multiply-adds of the correlation -- output pixels times effective taps
 -- and the rate they imply, and -- unless ``--no-host`` -- the wall time of ``fftconvolve(mode='same')`` + a block mean per plane
 with ``--threads`` host threads, one plane per thread, and of ``Generator.poisson`` + ``standard_normal`` on the binned frame.
+Next to the correlation its adjoint (csrc/patch.hip, the backward of ``Instrument.expected``): the same multiply-adds, gathered
+per input pixel; and -- with ``--torch`` -- fp64 ``torch.nn.functional.conv_transpose2d(stride=bin)`` on the device, plane by plane,
+where its column buffer (taps x detector pixels x 8 bytes per plane) stays below ``--torch-limit-gib``.
 One JSON line.
 
-    python tools/instrument_time.py [--repeats 5] [--calls 5] [--threads 16] [--no-host]
+    python tools/instrument_time.py [--repeats 5] [--calls 5] [--threads 16] [--no-host] [--torch] [--torch-limit-gib 8]
 """
 import argparse
 import json
@@ -39,8 +42,8 @@ def _timed(fn, repeats, calls):
     return sorted(times)[len(times) // 2]
 
 
-def measure(c, n, taps, b, repeats, calls, threads, with_host):
-    from sunerf_hip.instrument import Instrument, gaussian_psf
+def measure(c, n, taps, b, repeats, calls, threads, with_host, with_torch=False, torch_limit_gib=8.0):
+    from sunerf_hip.instrument import BOUNDARY, Instrument, correlate_bin_adjoint, gaussian_psf
     g = torch.Generator(device='cuda').manual_seed(n + taps + b)
     frame = 10.0 ** (torch.rand(c, n, n, device='cuda', generator=g) * 4.0 - 1.0)
     psf = gaussian_psf(taps / 4.0, taps // 2)
@@ -51,6 +54,26 @@ def measure(c, n, taps, b, repeats, calls, threads, with_host):
     row = {'shape': [c, n, n], 'psf': [taps, taps], 'bin': b, 'effective_kernel': list(K.shape[1:])}
     ms = _timed(lambda: inst.expected(frame), repeats, calls)
     row['correlate_bin'] = {'ms': ms, 'fp64_multiply_adds': macs, 'G_multiply_adds_per_s': macs / ms / 1e6}
+    g_out = torch.rand(expected.shape, device='cuda', generator=g)
+    dev_taps = inst._taps(K, frame.device)
+    _, (ay, ax) = inst.effective_kernel()
+    adjoint = lambda: correlate_bin_adjoint(g_out, n, n, dev_taps, K.shape[0], K.shape[1], K.shape[2], b, ay, ax, inst.scale,   # noqa: E731
+                                            BOUNDARY[inst.boundary])
+    ms_adjoint = _timed(adjoint, repeats, calls)
+    row['correlate_bin_adjoint'] = {'ms': ms_adjoint, 'over_forward': ms_adjoint / ms, 'G_multiply_adds_per_s': macs / ms_adjoint / 1e6}
+    if with_torch:
+        column_gib = K.shape[1] * K.shape[2] * (n // b) * (n // b) * 8 / 2.0 ** 30
+        if column_gib <= torch_limit_gib:
+            weight = torch.as_tensor(K[0], dtype=torch.float64, device='cuda')[None, None]
+            g64 = g_out.double()
+
+            def transposed():
+                for plane in g64:
+                    torch.nn.functional.conv_transpose2d(plane[None, None], weight, stride=b)
+            row['torch_conv_transpose2d_fp64'] = {'ms': _timed(transposed, repeats, calls), 'column_buffer_gib_per_plane': column_gib}
+        else:
+            row['torch_conv_transpose2d_fp64'] = {'ms': None, 'column_buffer_gib_per_plane': column_gib,
+                                                  'skipped': f'column buffer above {torch_limit_gib} GiB'}
     ms = _timed(lambda: inst.noise(expected, seed=1), repeats, calls)
     row['noise'] = {'ms': ms, 'elements': expected.numel(), 'G_elements_per_s': expected.numel() / ms / 1e6}
     if with_host:
@@ -78,10 +101,12 @@ def main():
     ap.add_argument('--calls', type=int, default=5)
     ap.add_argument('--threads', type=int, default=16)
     ap.add_argument('--no-host', action='store_true')
+    ap.add_argument('--torch', action='store_true', help='also time fp64 conv_transpose2d of torch on the device')
+    ap.add_argument('--torch-limit-gib', type=float, default=8.0)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('instrument_time.py needs a ROCm device')
-    rows = [measure(c, n, taps, b, args.repeats, args.calls, args.threads, not args.no_host)
+    rows = [measure(c, n, taps, b, args.repeats, args.calls, args.threads, not args.no_host, args.torch, args.torch_limit_gib)
             for c, n in ((7, 1024), (1, 4096)) for taps in (9, 33) for b in (1, 2)]
     print(json.dumps({'instrument_time': rows}))
 
