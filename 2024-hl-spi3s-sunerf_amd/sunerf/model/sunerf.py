@@ -36,7 +36,7 @@ class BaseSuNeRFModule(LightningModule):
     """sunerf.py:15-59."""
 
     def __init__(self, Rs_per_ds, seconds_per_dt, rendering: SuNeRFRendering, validation_dataset_mapping=None,
-                 lr_config=None):
+                 lr_config=None, likelihood=None):
         super().__init__()
         self.Rs_per_ds = Rs_per_ds
         self.seconds_per_dt = seconds_per_dt
@@ -44,11 +44,30 @@ class BaseSuNeRFModule(LightningModule):
         self.validation_dataset_mapping = validation_dataset_mapping
         self.validation_outputs = {}
         self.lr_config = {'start': 1e-4, 'end': 1e-5, 'iterations': 1e6} if lr_config is None else lr_config
+        # a sunerf_hip.likelihood.NoiseLikelihood replaces the MSE of training_step by the detector model's
+        # noise likelihood; a child module, so that checkpoints carry its log_gain.  None: the reference's loss.
+        self.likelihood = likelihood
+        self.last_channel_stats = None
+
+    def _trainable_parameters(self):
+        """What the optimiser updates: the rendering's parameters and, when any gain of the likelihood is free, its log_gain."""
+        params = list(self.rendering.parameters())
+        if self.likelihood is not None and any(p.requires_grad for p in self.likelihood.parameters()):
+            params += list(self.likelihood.parameters())
+        return params
+
+    def _likelihood_step(self, coarse, fine, target, codes, outputs):
+        """The loss section of a training step under ``self.likelihood``: no asinh scaling (the weighting replaces it)."""
+        from sunerf_hip.likelihood import likelihood_loss
+        loss, stats, self.last_channel_stats = likelihood_loss(
+            coarse, fine, target, outputs['regularization'], self.likelihood, codes=codes, lambda_image=self.lambda_image,
+            lambda_regularization=self.lambda_regularization, finite_check=_other_outputs(outputs))
+        return self._finish_step(self._with_smoothness(loss), stats)
 
     def configure_optimizers(self):
         # sunerf.py:31: Adam(lr = start).  ClipAdam is the same update on one flat buffer (and can take the gradient
         # clip that run_emission.py:72 configures on the Trainer: fit_steps below sets optimizer.max_norm).
-        self.optimizer = ClipAdam(self.rendering.parameters(), lr=self.lr_config['start'])
+        self.optimizer = ClipAdam(self._trainable_parameters(), lr=self.lr_config['start'])
         self.optimizer.nonfinite_source = self._step_nonfinite_count      # (Lightning's step(closure) passes no count)
         self.scheduler = ExponentialLR(self.optimizer, gamma=(self.lr_config['end'] / self.lr_config['start']) ** (
                 1 / self.lr_config['iterations']))
@@ -192,6 +211,15 @@ def _observed_windows(tracing, outputs):
     return observe(outputs['coarse_image']), observe(outputs['fine_image']), target.contiguous()
 
 
+def _patch_codes(tracing):
+    """The codes of a patch batch's detector pixels ``[n P P, C]``: those of their patch -- the ``wavelength`` row of the first
+    ray of each window, expanded over ``P x P``."""
+    spec = tracing['patch']
+    n, per_window, pixels = spec['n'], spec['hw'] * spec['ww'], spec['P'] * spec['P']
+    first = tracing['wavelength'].reshape(n, per_window, -1)[:, 0]
+    return first[:, None, :].expand(n, pixels, first.shape[-1]).reshape(n * pixels, -1).contiguous()
+
+
 def save_state(sunerf: BaseSuNeRFModule, data_module, save_path):
     """sunerf.py:62-74: pickles the rendering module + data configuration (the ``.snf`` file)."""
     output_path = '/'.join(save_path.split('/')[0:-1])
@@ -233,12 +261,16 @@ class EmissionSuNeRFModule(BaseSuNeRFModule):
             rays = rays.reshape(-1, 2, 3)
             outputs = self.rendering(rays[:, 0].contiguous(), rays[:, 1].contiguous(), time)
             coarse, fine, target = _observed_windows(tracing, outputs)
+            if self.likelihood is not None:
+                return self._likelihood_step(coarse, fine, target, None, outputs)
             loss, stats = training_loss(coarse, fine, target, outputs['regularization'], self.lambda_image,
                                         self.lambda_regularization, asinh_scaling=self._asinh_constants(),
                                         finite_check=_other_outputs(outputs))
             return self._finish_step(self._with_smoothness(loss), stats)
         rays_o, rays_d = rays[:, 0].contiguous(), rays[:, 1].contiguous()
         outputs = self.rendering(rays_o, rays_d, time)
+        if self.likelihood is not None:
+            return self._likelihood_step(outputs['coarse_image'], outputs['fine_image'], target_image.reshape(-1, 1), None, outputs)
         # sunerf.py:105-125 in one kernel: finite check of all outputs, asinh scaling, 2 x MSE, regularization mean, psnr
         loss, stats = training_loss(outputs['coarse_image'], outputs['fine_image'], target_image.reshape(-1, 1),
                                     outputs['regularization'], self.lambda_image, self.lambda_regularization,
@@ -296,9 +328,13 @@ class DensityTemperatureSuNeRFModule(BaseSuNeRFModule):
             outputs = self.rendering.forward(rays[:, 0].contiguous(), rays[:, 1].contiguous(), time, wavelengths)
             coarse, fine, target_image = _observed_windows(tracing, outputs)
             outputs = {**outputs, 'coarse_image': coarse, 'fine_image': fine}
+            codes = _patch_codes(tracing) if self.likelihood is not None else None
         else:
             rays_o, rays_d = rays[:, 0].contiguous(), rays[:, 1].contiguous()
             outputs = self.rendering.forward(rays_o, rays_d, time, wavelengths)
+            codes = wavelengths
+        if self.likelihood is not None:
+            return self._likelihood_step(outputs['coarse_image'], outputs['fine_image'], target_image, codes, outputs)
         if not isinstance(self.loss, nn.MSELoss) or self.loss.reduction != 'mean':
             return self._training_step_generic_loss(outputs, target_image)
         loss, stats = training_loss(outputs['coarse_image'], outputs['fine_image'], target_image,

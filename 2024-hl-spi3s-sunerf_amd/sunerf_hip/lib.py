@@ -247,6 +247,21 @@ _PATCH_SIGNATURES = {
 PATCH_SYMBOLS = tuple(_PATCH_SIGNATURES)
 PATCH_ABI_VERSION = 1
 
+# The likelihood table (include/sunerf_hip_likelihood.h): the Gaussian noise likelihood of the detector model as the training loss,
+# with per-row calibration gains.  A seventh table beside the six above, which stay as they are and keep their versions.
+_LIKELIHOOD_SIGNATURES = {
+    'sunerf_likelihood_abi_version': (ctypes.c_int, []),
+    'sunerf_likelihood_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int]),
+    'sunerf_likelihood_loss': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, c_f32p, c_void, c_f32p,
+                                               ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int64,
+                                               ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
+                                               ctypes.c_float, ctypes.c_float, c_f32p, c_f32p, c_void, c_void, c_f32p, c_void,
+                                               ctypes.c_size_t, c_void]),
+}
+
+LIKELIHOOD_SYMBOLS = tuple(_LIKELIHOOD_SIGNATURES)
+LIKELIHOOD_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -297,6 +312,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_patch_abi_version() != PATCH_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so patch ABI version mismatch')
+        for name, (res, args) in _LIKELIHOOD_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_likelihood_abi_version() != LIKELIHOOD_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so likelihood ABI version mismatch')
         _lib = lib
     return _lib
 

@@ -28,9 +28,13 @@ A step renders ``patches_per_batch hw ww`` rays (``rays_per_step`` in the report
 also scored on the clean held-out view rendered at ``bin`` times the resolution (``after_fine``): what the model knows about the
 scene in front of the telescope.
 
+``--likelihood observed|model`` (with ``--instrument``): the instrument runs -- on rays and, with ``--through-instrument``, on
+patches -- train on the noise likelihood of that instrument (``sunerf_hip.likelihood.NoiseLikelihood``, gains frozen at 1) in
+place of the MSE; their reports carry ``likelihood`` and the reduced chi-square of the last step.
+
     python tools/closed_loop.py [--module dt|emission] [--views 8] [--size 64] [--steps 300] [--batch 2048] [--d-filter 256] [--baseline]
                                 [--instrument SPEC [--through-instrument] [--patch 16] [--patches-per-batch N] [--through-steps K]]
-                                [--skip-clean]
+                                [--likelihood observed|model] [--skip-clean]
 """
 import argparse
 import json
@@ -51,6 +55,7 @@ from sunerf.rendering.density_temperature import DensityTemperatureRadiativeTran
 from sunerf_hip import ops                                                        # noqa: E402
 from sunerf_hip.feed import training_batches                                      # noqa: E402
 from sunerf_hip.instrument import Instrument                                      # noqa: E402
+from sunerf_hip.likelihood import NoiseLikelihood                                 # noqa: E402
 from sunerf_hip.observations import ObservationSet, hold_out_index, resampled_grid   # noqa: E402
 
 WL = [94., 131., 171., 193., 211., 304., 335.]
@@ -86,7 +91,7 @@ def observed_view(instrument, render, grid, index, n_views):
     return instrument.observe(render(fine).contiguous(), seed=index)['image']
 
 
-def density_temperature_problem(args, grid, poses, instrument=None):
+def density_temperature_problem(args, grid, poses, instrument=None, mode=None):
     fx = np.load(os.path.join(R, 'tests', 'golden', 'g9_simple_star.npz'))
     table = (fx['aia_logte'], fx['aia_tresp'])
     cfg = dict(sampling_config={'type': 'stratified', 'n_samples': 64, 'perturb': True},
@@ -118,11 +123,12 @@ def density_temperature_problem(args, grid, poses, instrument=None):
                                             pixel_intensity_factor=1e10, response_table=table,
                                             model_config={'d_filter': args.d_filter},
                                             lr_config={'start': 5e-4, 'end': 5e-5, 'iterations': args.steps},
+                                            likelihood=None if mode is None else NoiseLikelihood(instrument, codes=[int(w) for w in WL], mode=mode),
                                             **{k: dict(v) for k, v in cfg.items()}).cuda()
     return obs, module, render_of, np.array(WL)
 
 
-def emission_problem(args, grid, poses, instrument=None):
+def emission_problem(args, grid, poses, instrument=None, mode=None):
     from sunerf.evaluation.loader import linear_plate_scale_axes
     from sunerf_hip.rays import grid_rays, pose_spherical
     obs = ObservationSet(Rs_per_ds=1.0, seconds_per_dt=1.0, device='cuda')
@@ -141,7 +147,8 @@ def emission_problem(args, grid, poses, instrument=None):
                                   sampling_config={'type': 'stratified', 'n_samples': 64, 'perturb': True},
                                   hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 128, 'perturb': True},
                                   model_config={'d_filter': args.d_filter},
-                                  lr_config={'start': 5e-4, 'end': 5e-5, 'iterations': args.steps}).cuda()
+                                  lr_config={'start': 5e-4, 'end': 5e-5, 'iterations': args.steps},
+                                  likelihood=None if mode is None else NoiseLikelihood(instrument, mode=mode)).cuda()
     return obs, module, render_of, None
 
 
@@ -172,7 +179,11 @@ def main():
     ap.add_argument('--patches-per-batch', type=int, default=None, help='default: what brings a batch nearest to 8192 rays')
     ap.add_argument('--through-steps', type=int, default=None, help='steps of the through-instrument run (default: --steps)')
     ap.add_argument('--skip-clean', action='store_true', help='leave out the run on clean views')
+    ap.add_argument('--likelihood', choices=('observed', 'model'), default=None,
+                    help="the instrument runs train on the instrument's noise likelihood in place of the MSE")
     args = ap.parse_args()
+    if args.likelihood is not None and args.instrument is None:
+        ap.error('--likelihood needs --instrument SPEC')
     if args.through_instrument and args.instrument is None:
         ap.error('--through-instrument needs --instrument SPEC')
     grid = {'shape': (args.size, args.size), 'cdelt': (2.2 * 960. / args.size, 2.2 * 960. / args.size),
@@ -181,6 +192,8 @@ def main():
     report = {} if args.skip_clean else run(args, grid, poses, None)
     if args.instrument is not None:
         keys = ('steps', 'rays_per_step', 'loss_first_10', 'loss_last_10', 'train_seconds', 'before', 'after', 'after_fine')
+        if args.likelihood is not None:
+            keys += ('likelihood', 'reduced_chi2')
         seen = run(args, grid, poses, Instrument.from_spec(args.instrument))
         clean = '' if args.skip_clean else (f"clean views PSNR {report['after']['validation.psnr']:.2f} dB, SSIM "
                                             f"{report['after']['validation.ssim']:.4f}; ")
@@ -200,7 +213,7 @@ def main():
 def run(args, grid, poses, instrument, through=False):
     torch.manual_seed(0)
     problem = density_temperature_problem if args.module == 'dt' else emission_problem
-    obs, module, render_of, wavelengths = problem(args, grid, poses, instrument)
+    obs, module, render_of, wavelengths = problem(args, grid, poses, instrument, args.likelihood if instrument is not None else None)
     obs.hold_out('reference')
     steps = args.steps
     if through:
@@ -220,6 +233,8 @@ def run(args, grid, poses, instrument, through=False):
     module.check_finite(module.optimizer)
     after = held_out_scores(module, obs, 1 << 14)
     extra = {}
+    if module.likelihood is not None:
+        extra.update(likelihood=module.likelihood.mode, reduced_chi2=module.likelihood.reduced_chi2(module.last_channel_stats).cpu().tolist())
     if instrument is not None:
         held = obs.held_out[0]
         extra['after_fine'] = fine_scores(module, render_of(*poses[held]), grid, poses[held], wavelengths, instrument.bin, 1 << 14)

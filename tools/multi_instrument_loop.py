@@ -6,7 +6,14 @@
 
 through one ResponseSet, and scored on a held-out view between them (longitude 0.6 rad) in all seven channels.  The same fit
 with the second instrument's rays dropped shows what those rays add.  Prints the per-channel PSNR of the held-out view for both.
-Usage:  python tools/multi_instrument_loop.py [steps] [resolution]"""
+
+``--gain-error F``: the second instrument's views are multiplied by the hidden factor F, as two instruments never
+share one intensity scale, and the fit on both instruments runs under the noise likelihood (``sunerf_hip.likelihood``, 'observed'
+mode, every channel read as 1e4 photons at the mean intensity of the first view, read noise 1) -- once with every gain frozen at
+1 and, with ``--fit-gains``, once with the second instrument's rows free.  Prints the recovered gains next to the held-out
+scores; the held-out view carries no gain error, and the prediction scored is the model's own, before any gain.
+Usage:  python tools/multi_instrument_loop.py [steps] [resolution] [--gain-error 1.3 [--fit-gains] [--gain-rate 50]]"""
+import argparse
 import os
 import sys
 
@@ -22,8 +29,16 @@ from sunerf.rendering.density_temperature import DensityTemperatureRadiativeTran
 from sunerf_hip.rays import observer_rays                                         # noqa: E402
 from sunerf_hip.response import ResponseSet                                       # noqa: E402
 
-steps = int(sys.argv[1]) if len(sys.argv) > 1 else 300
-res = int(sys.argv[2]) if len(sys.argv) > 2 else 64
+ap = argparse.ArgumentParser()
+ap.add_argument('steps', type=int, nargs='?', default=300)
+ap.add_argument('resolution', type=int, nargs='?', default=64)
+ap.add_argument('--gain-error', type=float, default=None, help="hidden factor on the second instrument's views")
+ap.add_argument('--fit-gains', action='store_true', help="a further fit with the second instrument's gains free")
+ap.add_argument('--gain-rate', type=float, default=50.0, help='gain_rate of the likelihood: how much faster than the network the gains move')
+args = ap.parse_args()
+if args.fit_gains and args.gain_error is None:
+    ap.error('--fit-gains needs --gain-error F')
+steps, res = args.steps, args.resolution
 g9 = np.load(os.path.join(R, 'tests', 'golden', 'g9_simple_star.npz'))
 aia = ResponseSet.aia((g9['aia_logte'], g9['aia_tresp']), exposure=2.9)
 AIA_CODES = (171, 193, 211)
@@ -69,10 +84,18 @@ def view(phi, codes):
 first, other, held_out = view(0.0, A), view(1.2, B), view(0.6, A + B)
 
 
-def fit(batches):
+def likelihood(free):
+    """Every channel a detector that counts 1e4 photons at the mean intensity of the first view, read noise 1 DN."""
+    from sunerf_hip.instrument import Instrument
+    from sunerf_hip.likelihood import NoiseLikelihood
+    unit = 1e4 / first['tracing']['target_image'][:, :len(A)].mean().item()
+    return NoiseLikelihood(Instrument(unit=unit, read_noise=1.0), codes=rset, mode='observed', free=free, gain_rate=args.gain_rate)
+
+
+def fit(batches, like=None):
     torch.manual_seed(1)
     lm = DensityTemperatureSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={}, model=NeRF_DT,
-                                        response_set=rset, pixel_intensity_factor=1e10, lambda_regularization=0.0,
+                                        response_set=rset, pixel_intensity_factor=1e10, lambda_regularization=0.0, likelihood=like,
                                         model_config={'d_filter': 128, 'channels': rset, 'base_log_density': 17.0,
                                                       'base_log_temperature': 6.0}, **sampling()).cuda()
     thin(lm.rendering, False)
@@ -92,3 +115,12 @@ print(f'{"training rays":>28s} ' + ' '.join(f'{c:>7d}' for c in rset.codes) + ' 
 for name, batches in (('both instruments', [first, other]), ('AIA only', [first])):
     l0, l1, psnr = fit(batches)
     print(f'{name:>28s} ' + ' '.join(f'{p:7.2f}' for p in psnr) + f'   {l0:.3e} -> {l1:.3e}')
+if args.gain_error is not None:
+    wrong = {'tracing': {**other['tracing'], 'target_image': other['tracing']['target_image'] * args.gain_error}}
+    print(f"second instrument's views x {args.gain_error} (hidden); noise likelihood, 'observed' mode; gain_rate {args.gain_rate}")
+    runs = [('gains frozen at 1', ())] + ([('second instrument free', [int(c) for c in B])] if args.fit_gains else [])
+    for name, free in runs:
+        like = likelihood(free)
+        l0, l1, psnr = fit([first, wrong], like)
+        print(f'{name:>28s} ' + ' '.join(f'{p:7.2f}' for p in psnr) + f'   {l0:.3e} -> {l1:.3e}')
+        print(f'{"gains":>28s} ' + ' '.join(f'{g:7.4f}' for g in like.gains().cpu().tolist()))
