@@ -48,6 +48,51 @@ class BaseSuNeRFModule(LightningModule):
         # noise likelihood; a child module, so that checkpoints carry its log_gain.  None: the reference's loss.
         self.likelihood = likelihood
         self.last_channel_stats = None
+        self._init_ssim()
+
+    # the structural term of a patch batch: lambda_ssim (dssim(coarse) + dssim(fine)) beside the pixel loss; the
+    # subclasses set the three attributes before this constructor runs.  Off (0.0) by default: nothing is launched then.
+    lambda_ssim, ssim_window, ssim_data_range = 0.0, 7, None
+
+    def _init_ssim(self):
+        from sunerf_hip.ssim_loss import check_shape
+        self.last_ssim = None
+        if not float(self.lambda_ssim) >= 0.0:
+            raise ValueError(f'lambda_ssim must be >= 0, got {self.lambda_ssim}')
+        check_shape(self.ssim_window, self.ssim_window)
+        if self.lambda_ssim > 0 and self._ssim_scaling()[0] is None:
+            raise ValueError('lambda_ssim > 0 needs ssim_data_range: the images of this module have no natural scale')
+        if self.lambda_ssim > 0 and self.likelihood is not None and bool(self.likelihood.free.any()):
+            raise ValueError('lambda_ssim > 0 cannot be combined with a likelihood that has free gains: the structural term sees '
+                             'the prediction, not the gained prediction')
+
+    def _ssim_scaling(self):
+        """``(data_range, asinh_scaling)`` of the structural term: this module's images as they are, in the user's range."""
+        return self.ssim_data_range, None
+
+    def _ssim_spec(self, tracing):
+        """The patch geometry the structural term needs, or None where the term is off (a ray batch, or lambda_ssim = 0); raises
+        before anything is rendered when the patches are smaller than the window."""
+        self.last_ssim = None
+        if not self.lambda_ssim > 0 or 'patch' not in tracing:
+            return None
+        spec = tracing['patch']
+        if spec['P'] < self.ssim_window:
+            raise ValueError(f"patches of {spec['P']} x {spec['P']} detector pixels are smaller than ssim_window = {self.ssim_window}")
+        return spec
+
+    def _with_ssim(self, loss, coarse, fine, target, spec):
+        """``loss + lambda_ssim (dssim(coarse) + dssim(fine))`` on the rows the pixel loss got; ``loss`` itself where the term is
+        off.  ``last_ssim``: the kernel's four statistics; the log carries the mean SSIM of the two images."""
+        if spec is None:
+            return loss
+        from sunerf_hip.ssim_loss import ssim_loss
+        data_range, asinh_scaling = self._ssim_scaling()
+        term, stats, _ = ssim_loss(coarse, fine, target, spec['n'], spec['P'], data_range, window=self.ssim_window,
+                                   asinh_scaling=asinh_scaling)
+        self.last_ssim = stats
+        self.log('train_ssim', {'coarse': 1.0 - stats[0], 'fine': 1.0 - stats[1]})
+        return loss + (self.lambda_ssim * term).to(loss.dtype)
 
     def _trainable_parameters(self):
         """What the optimiser updates: the rendering's parameters and, when any gain of the likelihood is free, its log_gain."""
@@ -56,13 +101,13 @@ class BaseSuNeRFModule(LightningModule):
             params += list(self.likelihood.parameters())
         return params
 
-    def _likelihood_step(self, coarse, fine, target, codes, outputs):
+    def _likelihood_step(self, coarse, fine, target, codes, outputs, ssim_spec=None):
         """The loss section of a training step under ``self.likelihood``: no asinh scaling (the weighting replaces it)."""
         from sunerf_hip.likelihood import likelihood_loss
         loss, stats, self.last_channel_stats = likelihood_loss(
             coarse, fine, target, outputs['regularization'], self.likelihood, codes=codes, lambda_image=self.lambda_image,
             lambda_regularization=self.lambda_regularization, finite_check=_other_outputs(outputs))
-        return self._finish_step(self._with_smoothness(loss), stats)
+        return self._finish_step(self._with_ssim(self._with_smoothness(loss), coarse, fine, target, ssim_spec), stats)
 
     def configure_optimizers(self):
         # sunerf.py:31: Adam(lr = start).  ClipAdam is the same update on one flat buffer (and can take the gradient
@@ -233,17 +278,23 @@ class EmissionSuNeRFModule(BaseSuNeRFModule):
 
     def __init__(self, Rs_per_ds, seconds_per_dt, image_scaling_config, lambda_image=1.0, lambda_regularization=1.0,
                  sampling_config=None, hierarchical_sampling_config=None, model_config=None, model=NeRF,
-                 lambda_smoothness=0.0, lambda_temporal=0.0, **kwargs):
+                 lambda_smoothness=0.0, lambda_temporal=0.0, lambda_ssim=0.0, ssim_window=7, **kwargs):
         self.lambda_image = lambda_image
         self.lambda_regularization = lambda_regularization
         self.lambda_smoothness = lambda_smoothness
         self.lambda_temporal = lambda_temporal
+        self.lambda_ssim, self.ssim_window = lambda_ssim, ssim_window
         rendering = EmissionRadiativeTransfer(Rs_per_ds=Rs_per_ds, sampling_config=sampling_config,
                                               hierarchical_sampling_config=hierarchical_sampling_config,
                                               model_config=model_config, model=model)
         super().__init__(Rs_per_ds=Rs_per_ds, seconds_per_dt=seconds_per_dt, rendering=rendering, **kwargs)
         self.image_scaling = ImageAsinhScaling(**image_scaling_config)
         self.mse_loss = nn.MSELoss()
+
+    def _ssim_scaling(self):
+        """The structural term always sees the images under the module's asinh stretch, whose range is 1 -- under the MSE and
+        under a likelihood alike."""
+        return 1.0, (self._asinh_constants() if hasattr(self, 'image_scaling') else None)
 
     def _asinh_constants(self):
         """(vmax, a) of the image scaling as host floats, read from the module's buffers once (not per step: a device ->
@@ -257,16 +308,17 @@ class EmissionSuNeRFModule(BaseSuNeRFModule):
     def training_step(self, batch, batch_nb):
         tracing = batch['tracing']
         rays, time, target_image = tracing['rays'], tracing['time'], tracing['target_image']
+        ssim_spec = self._ssim_spec(tracing)
         if 'patch' in tracing:          # windows of detector-pixel patches: the loss compares instrument(render) with the target
             rays = rays.reshape(-1, 2, 3)
             outputs = self.rendering(rays[:, 0].contiguous(), rays[:, 1].contiguous(), time)
             coarse, fine, target = _observed_windows(tracing, outputs)
             if self.likelihood is not None:
-                return self._likelihood_step(coarse, fine, target, None, outputs)
+                return self._likelihood_step(coarse, fine, target, None, outputs, ssim_spec)
             loss, stats = training_loss(coarse, fine, target, outputs['regularization'], self.lambda_image,
                                         self.lambda_regularization, asinh_scaling=self._asinh_constants(),
                                         finite_check=_other_outputs(outputs))
-            return self._finish_step(self._with_smoothness(loss), stats)
+            return self._finish_step(self._with_ssim(self._with_smoothness(loss), coarse, fine, target, ssim_spec), stats)
         rays_o, rays_d = rays[:, 0].contiguous(), rays[:, 1].contiguous()
         outputs = self.rendering(rays_o, rays_d, time)
         if self.likelihood is not None:
@@ -306,11 +358,13 @@ class DensityTemperatureSuNeRFModule(BaseSuNeRFModule):
 
     def __init__(self, Rs_per_ds, seconds_per_dt, image_scaling_config, model, loss=nn.MSELoss(), lambda_image=1.0,
                  lambda_regularization=1.0, sampling_config=None, hierarchical_sampling_config=None,
-                 pixel_intensity_factor=1e17, model_config=None, lambda_smoothness=0.0, lambda_temporal=0.0, **kwargs):
+                 pixel_intensity_factor=1e17, model_config=None, lambda_smoothness=0.0, lambda_temporal=0.0, lambda_ssim=0.0,
+                 ssim_window=7, ssim_data_range=None, **kwargs):
         self.lambda_image = lambda_image
         self.lambda_regularization = lambda_regularization
         self.lambda_smoothness = lambda_smoothness
         self.lambda_temporal = lambda_temporal
+        self.lambda_ssim, self.ssim_window, self.ssim_data_range = lambda_ssim, ssim_window, ssim_data_range
         rendering_kwargs = {k: kwargs.pop(k) for k in ('response_table', 'response_path', 'response_set') if k in kwargs}
         rendering = DensityTemperatureRadiativeTransfer(Rs_per_ds=Rs_per_ds, sampling_config=sampling_config,
                                                         hierarchical_sampling_config=hierarchical_sampling_config,
@@ -323,6 +377,7 @@ class DensityTemperatureSuNeRFModule(BaseSuNeRFModule):
         tracing = batch['tracing']
         rays, time, target_image, wavelengths = (tracing['rays'], tracing['time'], tracing['target_image'],
                                                  tracing['wavelength'])
+        ssim_spec = self._ssim_spec(tracing)
         if 'patch' in tracing:          # windows of detector-pixel patches: the loss compares instrument(render) with the target
             rays = rays.reshape(-1, 2, 3)
             outputs = self.rendering.forward(rays[:, 0].contiguous(), rays[:, 1].contiguous(), time, wavelengths)
@@ -334,13 +389,16 @@ class DensityTemperatureSuNeRFModule(BaseSuNeRFModule):
             outputs = self.rendering.forward(rays_o, rays_d, time, wavelengths)
             codes = wavelengths
         if self.likelihood is not None:
-            return self._likelihood_step(outputs['coarse_image'], outputs['fine_image'], target_image, codes, outputs)
+            return self._likelihood_step(outputs['coarse_image'], outputs['fine_image'], target_image, codes, outputs, ssim_spec)
         if not isinstance(self.loss, nn.MSELoss) or self.loss.reduction != 'mean':
+            if ssim_spec is not None:
+                raise NotImplementedError('lambda_ssim > 0 is built for the MSE and the likelihood, not for a user-supplied loss module')
             return self._training_step_generic_loss(outputs, target_image)
         loss, stats = training_loss(outputs['coarse_image'], outputs['fine_image'], target_image,
                                     outputs['regularization'], self.lambda_image, self.lambda_regularization,
                                     asinh_scaling=None, finite_check=_other_outputs(outputs))
-        return self._finish_step(self._with_smoothness(loss), stats)
+        loss = self._with_ssim(self._with_smoothness(loss), outputs['coarse_image'], outputs['fine_image'], target_image, ssim_spec)
+        return self._finish_step(loss, stats)
 
     def _training_step_generic_loss(self, outputs, target_image):
         """A user-supplied loss module other than nn.MSELoss (sunerf.py:159 takes any callable): torch ops."""

@@ -262,6 +262,19 @@ _LIKELIHOOD_SIGNATURES = {
 LIKELIHOOD_SYMBOLS = tuple(_LIKELIHOOD_SIGNATURES)
 LIKELIHOOD_ABI_VERSION = 1
 
+# The structural-loss table (include/sunerf_hip_ssim_loss.h): D-SSIM of a batch of patches with its gradient.  An eighth table
+# beside the seven above, which stay as they are and keep their versions.
+_SSIM_LOSS_SIGNATURES = {
+    'sunerf_ssim_loss_abi_version': (ctypes.c_int, []),
+    'sunerf_ssim_loss_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    'sunerf_ssim_loss': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, c_f32p, c_f32p, c_void,
+                                         c_void, c_void, ctypes.c_size_t, c_void]),
+}
+
+SSIM_LOSS_SYMBOLS = tuple(_SSIM_LOSS_SIGNATURES)
+SSIM_LOSS_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -318,6 +331,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_likelihood_abi_version() != LIKELIHOOD_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so likelihood ABI version mismatch')
+        for name, (res, args) in _SSIM_LOSS_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_ssim_loss_abi_version() != SSIM_LOSS_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so structural-loss ABI version mismatch')
         _lib = lib
     return _lib
 

@@ -32,9 +32,14 @@ scene in front of the telescope.
 patches -- train on the noise likelihood of that instrument (``sunerf_hip.likelihood.NoiseLikelihood``, gains frozen at 1) in
 place of the MSE; their reports carry ``likelihood`` and the reduced chi-square of the last step.
 
+``--lambda-ssim L`` (with ``--through-instrument``): the patch run adds ``L (dssim(coarse) + dssim(fine))`` to its loss, the
+structural term of DESIGN.md 8r with a window of ``--ssim-window`` detector pixels (the emission module on its asinh-stretched
+images; the DT module on its images of order one, data range 1); its report carries ``lambda_ssim`` and the mean SSIM of the last
+step's patches.  Ray runs have no neighbouring pixels and ignore it.
+
     python tools/closed_loop.py [--module dt|emission] [--views 8] [--size 64] [--steps 300] [--batch 2048] [--d-filter 256] [--baseline]
                                 [--instrument SPEC [--through-instrument] [--patch 16] [--patches-per-batch N] [--through-steps K]]
-                                [--likelihood observed|model] [--skip-clean]
+                                [--likelihood observed|model] [--lambda-ssim L [--ssim-window 7]] [--skip-clean]
 """
 import argparse
 import json
@@ -124,6 +129,8 @@ def density_temperature_problem(args, grid, poses, instrument=None, mode=None):
                                             model_config={'d_filter': args.d_filter},
                                             lr_config={'start': 5e-4, 'end': 5e-5, 'iterations': args.steps},
                                             likelihood=None if mode is None else NoiseLikelihood(instrument, codes=[int(w) for w in WL], mode=mode),
+                                            lambda_ssim=args.lambda_ssim, ssim_window=args.ssim_window,
+                                            ssim_data_range=1.0 if args.lambda_ssim > 0 else None,
                                             **{k: dict(v) for k, v in cfg.items()}).cuda()
     return obs, module, render_of, np.array(WL)
 
@@ -148,7 +155,8 @@ def emission_problem(args, grid, poses, instrument=None, mode=None):
                                   hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 128, 'perturb': True},
                                   model_config={'d_filter': args.d_filter},
                                   lr_config={'start': 5e-4, 'end': 5e-5, 'iterations': args.steps},
-                                  likelihood=None if mode is None else NoiseLikelihood(instrument, mode=mode)).cuda()
+                                  likelihood=None if mode is None else NoiseLikelihood(instrument, mode=mode),
+                                  lambda_ssim=args.lambda_ssim, ssim_window=args.ssim_window).cuda()
     return obs, module, render_of, None
 
 
@@ -181,7 +189,11 @@ def main():
     ap.add_argument('--skip-clean', action='store_true', help='leave out the run on clean views')
     ap.add_argument('--likelihood', choices=('observed', 'model'), default=None,
                     help="the instrument runs train on the instrument's noise likelihood in place of the MSE")
+    ap.add_argument('--lambda-ssim', type=float, default=0.0, help='weight of the structural (D-SSIM) term of the patch run')
+    ap.add_argument('--ssim-window', type=int, default=7, help='side of the SSIM window in detector pixels (odd, 3 .. 11)')
     args = ap.parse_args()
+    if args.lambda_ssim > 0 and not args.through_instrument:
+        ap.error('--lambda-ssim needs --through-instrument: only patch batches have neighbouring pixels')
     if args.likelihood is not None and args.instrument is None:
         ap.error('--likelihood needs --instrument SPEC')
     if args.through_instrument and args.instrument is None:
@@ -206,7 +218,8 @@ def main():
                   f"{through['after']['validation.psnr']:.2f} dB, SSIM {through['after']['validation.ssim']:.4f}; at bin times the "
                   f"resolution {through['after_fine']['validation.psnr']:.2f} dB against {seen['after_fine']['validation.psnr']:.2f} dB "
                   f"of ray training ({seen['steps']} steps of {seen['rays_per_step']} rays)", file=sys.stderr)
-            report['through_instrument'] = {k: through[k] for k in keys + ('patch', 'patches', 'dropped', 'halo_overhead')}
+            more = ('patch', 'patches', 'dropped', 'halo_overhead') + (('lambda_ssim', 'train_ssim') if args.lambda_ssim > 0 else ())
+            report['through_instrument'] = {k: through[k] for k in keys + more}
     print(json.dumps({'closed_loop': report}))
 
 
@@ -240,6 +253,8 @@ def run(args, grid, poses, instrument, through=False):
         extra['after_fine'] = fine_scores(module, render_of(*poses[held]), grid, poses[held], wavelengths, instrument.bin, 1 << 14)
     if through:
         extra.update(patch=pool.patch, patches=pool.n_patches, dropped=pool.dropped, halo_overhead=pool.halo_overhead)
+        if module.last_ssim is not None:
+            extra.update(lambda_ssim=module.lambda_ssim, train_ssim=(1.0 - module.last_ssim[:2]).cpu().tolist())
         return {'held_out': obs.held_out, 'steps': steps, 'rays_per_step': rays_per_step,
                 'loss_first_10': losses[:10].mean().item(), 'loss_last_10': losses[-10:].mean().item(), 'train_seconds': seconds,
                 'before': before, 'after': after, **extra}
