@@ -165,6 +165,18 @@ class Instrument:
         out.update(shape=(h // b, w // b), cdelt=(cdx * b, cdy * b), crpix=((cpx - 0.5) / b + 0.5, (cpy - 0.5) / b + 0.5))
         return out
 
+    def latent_grid(self, grid: dict) -> dict:
+        """The inverse of :meth:`detector_grid`: the plate-scale dict of the ``bin``-times-finer frame whose binning is the
+        detector frame ``grid`` -- the frame of a deconvolved view (:meth:`deconvolve`), which is added with
+        ``ObservationSet.add_view(..., grid=latent_grid(grid))``."""
+        h, w = grid['shape']
+        b = self.bin
+        cdx, cdy = grid['cdelt']
+        cpx, cpy = grid.get('crpix', ((w + 1) / 2., (h + 1) / 2.))
+        out = {k: v for k, v in grid.items() if k not in ('shape', 'cdelt', 'crpix')}
+        out.update(shape=(h * b, w * b), cdelt=(cdx / b, cdy / b), crpix=((cpx - 0.5) * b + 0.5, (cpy - 0.5) * b + 0.5))
+        return out
+
     def errors(self, image, channel_axis: int = -1):
         """The ``sigma`` of an OBSERVED image (image units, any device, plain torch): the sigma formula of :meth:`observe` with
         the photon count estimated from the image itself, ``lam = max(dn - pedestal, 0) / dn_per_photon``.  Same shape as
@@ -294,6 +306,12 @@ class Instrument:
         expected = self.expected(planes)
         image, sigma, saturated = self.noise(expected, seed, index_offset, poisson, read)
         return {'image': image, 'expected': expected, 'sigma': sigma, 'saturated': saturated}
+
+    def deconvolve(self, image: torch.Tensor, **kw) -> dict:
+        """Richardson-Lucy deconvolution of an observed ``image`` [C, h, w] against this instrument:
+        :func:`sunerf_hip.deconvolve.richardson_lucy` (``iterations``, ``stop``, ``bad``, ``init``)."""
+        from .deconvolve import richardson_lucy
+        return richardson_lucy(image, self, **kw)
 
 
 def _correlate_bin(planes, taps, n_kernels, kh, kw, bin_factor, ay, ax, scale, boundary):

@@ -275,6 +275,20 @@ _SSIM_LOSS_SIGNATURES = {
 SSIM_LOSS_SYMBOLS = tuple(_SSIM_LOSS_SIGNATURES)
 SSIM_LOSS_ABI_VERSION = 1
 
+# The deconvolution table (include/sunerf_hip_deconvolve.h): Richardson-Lucy against the PSF-and-bin kernel, the iterations
+# enqueued by one call.  A ninth table beside the eight above, which stay as they are and keep their versions.
+_DECONVOLVE_SIGNATURES = {
+    'sunerf_deconvolve_abi_version': (ctypes.c_int, []),
+    'sunerf_deconvolve_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 6),
+    'sunerf_deconvolve_richardson_lucy': (ctypes.c_int, [c_f32p, c_f32p, c_void, c_f32p, c_void, ctypes.c_int, ctypes.c_int,
+                                                          ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                                          ctypes.c_int, ctypes.c_double, c_f32p, c_void, c_void, c_void]),
+}
+
+DECONVOLVE_SYMBOLS = tuple(_DECONVOLVE_SIGNATURES)
+DECONVOLVE_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -337,6 +351,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_ssim_loss_abi_version() != SSIM_LOSS_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so structural-loss ABI version mismatch')
+        for name, (res, args) in _DECONVOLVE_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_deconvolve_abi_version() != DECONVOLVE_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so deconvolution ABI version mismatch')
         _lib = lib
     return _lib
 

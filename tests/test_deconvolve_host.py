@@ -1,0 +1,237 @@
+"""CPU-only checks of the Richardson-Lucy deconvolution (no GPU): the properties of the iteration on the fp64
+restatement tests/deconvolve_reference.py -- the one the GPU tests hold the kernels to by bits -- and the ninth entry-point table
+(declared, bound, its argument checks in their documented order, the workspace query).
+
+The case is 48 x 48 latent pixels (a limb-brightened disc with four compact sources) under a Gaussian PSF of FWHM 2.5 px and the
+closed loop's detector scalars (unit 1000, exposure 2.9 s, 1.2 DN per photon, read noise 1.2 DN), with Poisson and read noise drawn
+by NumPy; the start is the replicated observed image.  Bounds are reasoned in each test's docstring; every figure is printed."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import deconvolve_reference as dr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SETTINGS = [(1, 'nearest'), (2, 'nearest'), (2, 'zero')]
+H = W = 48
+
+
+@pytest.fixture(scope='session')
+def lib():
+    import sunerf_hip
+    if not os.path.exists(sunerf_hip.LIB_PATH):
+        import subprocess
+        subprocess.check_call(['bash', os.path.join(ROOT, '2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh')])
+    return sunerf_hip.load()
+
+
+def _run(hc, n, stop=0.0, u0=None, history=None):
+    b, boundary = hc['bin'], hc['boundary']
+    norm = dr.norm_of(hc['d'], None, hc['K'], H, W, b, hc['anchor'], hc['scale'], boundary)
+    u0 = dr.initial_image(hc['d'], None, b) if u0 is None else u0
+    u, state, _ = dr.richardson_lucy(u0, hc['d'], None, norm, hc['K'], b, hc['anchor'], hc['scale'], boundary, hc['c'], hc['v'], n, stop,
+                                     history)
+    return u, state, norm
+
+
+@pytest.fixture(scope='module')
+def thirty():
+    """30 updates of the three settings, run once: (case, u, per-pixel deviance of every iterate)."""
+    out = {}
+    for b, boundary in SETTINGS:
+        hc = dr.host_case(b, boundary)
+        history = []
+        u, state, _ = _run(hc, 30, history=history)
+        assert state[0, 2] == 30 and state[0, 3] == 0
+        out[(b, boundary)] = (hc, u, [dev / n for dev, n, _ in history[0]])
+    return out
+
+
+@pytest.mark.parametrize('b,boundary', SETTINGS)
+def test_deviance_falls_monotonically(thirty, b, boundary):
+    """EM raises the likelihood with every update, so the deviance of the shifted-Poisson model does not rise.  Required: a
+    relative decrease above 1e-6 in each of the first five updates (fp64 sums of 2304 terms carry 1e-13 of rounding; the smallest
+    decrease seen is some per cent)."""
+    per = thirty[(b, boundary)][2]
+    drop = [(per[k] - per[k + 1]) / per[k] for k in range(len(per) - 1)]
+    print(f'bin {b} {boundary}: deviance per valid pixel {per[0]:.3f} at the start, {per[5]:.3f} after 5 updates, {per[29]:.3f} after 29; '
+          f'smallest relative decrease {min(drop[:5]):.3e} (first five), {min(drop):.3e} (all 30)')
+    assert min(drop[:5]) > 1e-6
+
+
+@pytest.mark.parametrize('b,boundary', SETTINGS)
+def test_flux_is_conserved_without_read_noise(b, boundary):
+    """With read_noise = 0 (off = 0): sum(u' norm) = sum(u A^T ratio) = sum((A u) ratio) = sum(valid ? d : 0).  u' and ratio are
+    each rounded to fp32 once, 2^-24 relative on positive terms, so the sums agree to 1.2e-7; gate 1e-6.  (With read noise the
+    flux is not conserved and nothing is asserted.)"""
+    hc = dr.host_case(b, boundary, read_noise=0.0)
+    assert hc['v'] == 0.0 and (hc['d'] >= 0).all()
+    u, _, norm = _run(hc, 1)
+    got = float((u.astype(np.float64) * norm.astype(np.float64)).sum())
+    want = float(hc['d'].astype(np.float64).sum())
+    print(f'bin {b} {boundary}: sum(u norm) {got:.9g}, sum(d) {want:.9g}, relative difference {abs(got - want) / want:.3e}')
+    assert abs(got - want) <= 1e-6 * want
+
+
+@pytest.mark.parametrize('b,boundary', SETTINGS)
+def test_truth_is_a_fixed_point_of_noise_free_data(b, boundary):
+    """d = expected(truth), v = 0, u0 = truth: ratio = 1 up to the fp32 rounding of d and of itself, so an update moves u by the
+    roundings of d, norm and u' -- 3 x 2^-24 relative -- and after n = 5 updates |u - truth| <= 4 n 2^-24 truth."""
+    hc = dr.host_case(b, boundary, read_noise=0.0, noise=False)
+    n = 5
+    u, state, _ = _run(hc, n, u0=hc['truth'].copy())
+    truth = hc['truth'].astype(np.float64)
+    err = np.abs(u.astype(np.float64) - truth) / truth
+    print(f'bin {b} {boundary}: largest |u - truth| / truth after {n} updates {err.max() * 2 ** 24:.2f} x 2^-24; '
+          f'deviance per pixel {state[0, 0] / state[0, 1]:.3e}')
+    assert err.max() <= 4 * n * 2.0 ** -24
+
+
+@pytest.mark.parametrize('b,boundary', SETTINGS[:2])
+def test_thirty_updates_recover_more_than_the_observed_image(thirty, b, boundary):
+    hc, u, _ = thirty[(b, boundary)]
+    rms = lambda a: float(np.sqrt(np.mean((a.astype(np.float64) - hc['truth']) ** 2)))          # noqa: E731
+    observed = np.repeat(np.repeat(hc['d'], b, axis=1), b, axis=2)
+    print(f'bin {b} {boundary}: RMS error {rms(u):.4f} deconvolved, {rms(observed):.4f} observed (replicated)')
+    assert (u >= 0).all() and rms(u) < rms(observed)
+
+
+def test_discrepancy_rule_stops_at_the_first_iterate_that_fits(thirty):
+    """stop = 1.0: the plane stops at the first iterate whose deviance per valid pixel is <= 1 -- its u, its deviance and its count
+    are that iterate's.  No iterate of the case lies within 1e-6 relative of the threshold (checked), so a ``log`` that differs
+    from NumPy's in its last bits decides the same way."""
+    hc, _, per = thirty[(1, 'nearest')]
+    assert all(abs(x - 1.0) > 1e-6 for x in per), per
+    first = next(k for k, x in enumerate(per) if x <= 1.0)
+    print(f'deviance per valid pixel: {", ".join(f"{x:.3f}" for x in per[:first + 2])}; the rule stops after {first} updates')
+    assert first >= 1 and per[first - 1] > 1.0
+    u, state, _ = _run(hc, 30, stop=1.0)
+    assert state[0, 2] == first and state[0, 3] == 1 and state[0, 0] / state[0, 1] == per[first]
+    fixed, fixed_state, _ = _run(hc, first)
+    assert np.array_equal(u.view(np.uint32), fixed.view(np.uint32)) and fixed_state[0, 0] == state[0, 0]
+    assert fixed_state[0, 3] == 0 and fixed_state[0, 2] == first          # a fixed count does not look at the threshold
+    _, early, _ = _run(hc, first - 1, stop=1.0)
+    assert early[0, 2] == first - 1 and early[0, 3] == 0                  # the count ran out before the rule was met
+
+
+def test_initial_image_matches_the_restatement():
+    """sunerf_hip.deconvolve.initial_image is plain torch: on the CPU it gives the restatement's start for both bin modes and
+    inits, NaN and non-positive pixels replaced by the plane's mean over its valid positive pixels."""
+    import torch
+    from sunerf_hip.deconvolve import initial_image
+    from sunerf_hip.instrument import Instrument
+    rng = np.random.default_rng(3)
+    d = rng.uniform(0.1, 2.0, size=(2, 5, 7)).astype(np.float32)
+    d[0, 1, 2], d[0, 3, 3], d[1, 0, 0] = np.nan, -0.5, 0.0
+    bad = np.zeros(d.shape, dtype=np.uint8)
+    bad[1, 2, 2] = 1
+    d[1, 4] = np.nan
+    valid = torch.from_numpy(dr.valid_mask(d, bad))
+    for mode in ('mean', 'sum'):
+        for init in ('image', 'flat'):
+            got = initial_image(torch.from_numpy(d), valid, Instrument(bin=3, bin_mode=mode), init).numpy()
+            want = dr.initial_image(d, bad, 3, mode, init)
+            assert got.shape == (2, 15, 21) and (got > 0).all()
+            np.testing.assert_allclose(got, want, rtol=2e-7, atol=0)          # one fp32 rounding of the mean apart at most
+    empty = initial_image(torch.full((1, 2, 2), float('nan')), torch.zeros((1, 2, 2), dtype=torch.bool), Instrument(), 'image')
+    assert (empty == 1).all()
+
+
+def test_photon_params_match_the_restatement():
+    from sunerf_hip.deconvolve import photon_params
+    from sunerf_hip.instrument import Instrument
+    inst = Instrument(unit=[1000., 40.], exposure=2.9, dn_per_photon=1.2, read_noise=[1.2, 0.0], quantise=True)
+    got = photon_params(inst, 2)
+    for k, (unit, rn) in enumerate(((1000., 1.2), (40., 0.0))):
+        assert tuple(got[k]) == dr.photon_params(unit, 2.9, 1.2, rn, quantise=True)
+
+
+def test_latent_grid_inverts_detector_grid():
+    """detector_grid(latent_grid(g)) == g.  For bin 1, 2, 4, 8 every step is exact; for the other bins cdelt / b * b and
+    ((crpix - 0.5) b + 0.5 - 0.5) / b + 0.5 round up to three times, so they are held to 4 ulp of fp64 (and shape, crval, extra keys
+    exactly)."""
+    from sunerf_hip.instrument import Instrument
+    g = {'shape': (37, 52), 'cdelt': (0.6, 0.613), 'crpix': (26.25, 19.4), 'crval': (1.5, -2.0), 'unit': 'arcsec'}
+    for b in range(1, 9):
+        inst = Instrument(bin=b)
+        fine = inst.latent_grid(g)
+        assert fine['shape'] == (37 * b, 52 * b) and fine['crval'] == g['crval'] and fine['unit'] == 'arcsec'
+        back = inst.detector_grid(fine)
+        assert set(back) == set(g) and back['shape'] == g['shape'] and back['crval'] == g['crval']
+        if b in (1, 2, 4, 8):
+            assert back == g, (b, back)
+        else:
+            for key in ('cdelt', 'crpix'):
+                np.testing.assert_allclose(back[key], g[key], rtol=4 * 2.0 ** -52, atol=0)
+        # a frame without crpix: the centre of the detector frame is the centre of the latent frame
+        centred = inst.detector_grid(inst.latent_grid({'shape': (6, 10), 'cdelt': (2.0, 2.0)}))
+        assert centred['crpix'] == (5.5, 3.5) and centred['shape'] == (6, 10)
+
+
+# ---- the ninth table --------------------------------------------------------------------------------------------------------------
+NEW_SYMBOLS = ('sunerf_deconvolve_abi_version', 'sunerf_deconvolve_workspace_bytes', 'sunerf_deconvolve_richardson_lucy')
+
+
+def test_entry_points_are_declared_and_bound(lib):
+    import sunerf_hip
+    from sunerf_hip import lib as binding
+    read = lambda *p: open(os.path.join(ROOT, *p)).read()          # noqa: E731
+    header = read('include', 'sunerf_hip_deconvolve.h')
+    declared = set(re.findall(r'\b(sunerf_\w+)\s*\(', header))
+    assert declared == set(NEW_SYMBOLS) == set(sunerf_hip.DECONVOLVE_SYMBOLS) == set(binding._DECONVOLVE_SIGNATURES)
+    assert binding.DECONVOLVE_SYMBOLS == tuple(binding._DECONVOLVE_SIGNATURES)
+    taken = (sunerf_hip.EXPORTED_SYMBOLS + sunerf_hip.EXTENSION_SYMBOLS + sunerf_hip.RESPONSE_SYMBOLS + sunerf_hip.PREP_SYMBOLS
+             + sunerf_hip.INSTRUMENT_SYMBOLS + sunerf_hip.PATCH_SYMBOLS + sunerf_hip.LIKELIHOOD_SYMBOLS + sunerf_hip.SSIM_LOSS_SYMBOLS)
+    for name in NEW_SYMBOLS:
+        fn = getattr(lib, name)
+        assert name not in taken
+        assert fn.restype is binding._DECONVOLVE_SIGNATURES[name][0] and list(fn.argtypes) == binding._DECONVOLVE_SIGNATURES[name][1]
+    assert lib.sunerf_deconvolve_abi_version() == binding.DECONVOLVE_ABI_VERSION == 1
+    assert '#define SUNERF_DECONVOLVE_ABI_VERSION 1' in header
+    build = read('2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh')
+    assert len(re.findall(r'\bdeconvolve\b', build)) == 2
+    assert 'DECONVOLVE_SYMBOLS' in read('__graft_entry__.py')
+    # the workspace query: 16 bytes per tile of the forward correlation (T = min(32, (127 - k) / bin + 1)) and plane
+    q = lib.sunerf_deconvolve_workspace_bytes
+    assert [q(*a) for a in ((1, 5, 7, 1, 1, 1), (2, 33, 65, 3, 3, 1), (1, 70, 67, 9, 9, 2), (1, 40, 40, 96, 96, 8), (3, 64, 64, 5, 5, 2))] \
+        == [16, 2 * 2 * 3 * 16, 2 * 2 * 16, 2 * 2 * 16, 3 * 16]
+    assert [q(*a) for a in ((0, 5, 7, 1, 1, 1), (-1, 5, 7, 1, 1, 1), (1, 5, 7, 97, 1, 1), (1, 5, 7, 1, 1, 9), (1, 5, 7, 0, 1, 1),
+                            (1, 1, 7, 1, 1, 2))] == [0] * 6
+
+
+def check_argument_order(lib):
+    """Limits (-2) first, then the empty call (0), then counts, iteration count, threshold, null pointers and alignment (-1): all
+    before anything touches a device, so this runs without one.  ``Q`` stands for any non-null aligned pointer: no call here
+    reaches a launch."""
+    Q = ctypes.c_void_p(4096)
+    fn = lib.sunerf_deconvolve_richardson_lucy
+    names = ('u', 'd', 'bad', 'norm', 'params', 'K', 'ratio', 'state', 'workspace')
+
+    def call(n_planes=2, h=9, w=11, n_kernels=1, kh=3, kw=5, b=1, ay=1, ax=2, scale=1.0, boundary=1, n_it=3, stop=0.0, **ptrs):
+        p = {k: Q for k in names}
+        p.update(ptrs)
+        return fn(p['u'], p['d'], p['bad'], p['norm'], p['params'], n_planes, h, w, p['K'], n_kernels, kh, kw, b, ay, ax, scale, boundary,
+                  n_it, stop, p['ratio'], p['state'], p['workspace'], None)
+    none = {k: None for k in names}
+    assert call(kh=97, **none) == -2 and call(kw=97, **none) == -2 and call(b=9, **none) == -2
+    assert call(boundary=2, **none) == -2 and call(boundary=-1, **none) == -2
+    assert call(kh=97, n_planes=0, **none) == -2 and call(b=9, n_planes=-1, **none) == -2          # the limits come first
+    for empty in (dict(n_planes=0), dict(h=0), dict(w=0), dict(h=1, b=2), dict(w=3, b=4)):
+        assert call(n_it=-1, stop=-1.0, n_kernels=7, ay=-1, **empty, **none) == 0, empty           # then the empty call
+    assert call(n_planes=-1) == -1 and call(h=-1) == -1 and call(kh=0) == -1 and call(b=0) == -1 and call(n_planes=-1, h=0) == -1
+    assert call(n_kernels=3) == -1
+    assert call(n_kernels=0) == -1 and call(ay=3) == -1 and call(ax=-1) == -1 and call(ax=5) == -1
+    assert call(n_it=-1) == -1 and call(n_it=10001) == -1
+    assert call(stop=-1e-300) == -1 and call(stop=float('nan')) == -1
+    for k in names:
+        if k != 'bad':
+            assert call(**{k: None}) == -1, k
+    for k in ('params', 'K', 'state', 'workspace'):
+        assert call(**{k: ctypes.c_void_p(4100)}) == -1, k
+
+
+def test_argument_checks_come_in_the_documented_order(lib):
+    check_argument_order(lib)

@@ -37,9 +37,16 @@ structural term of DESIGN.md 8r with a window of ``--ssim-window`` detector pixe
 images; the DT module on its images of order one, data range 1); its report carries ``lambda_ssim`` and the mean SSIM of the last
 step's patches.  Ray runs have no neighbouring pixels and ignore it.
 
+``--deconvolve N|auto`` (with ``--instrument``): a further run, the classical alternative to training through the instrument
+(DESIGN.md 8s).  The same observed training views are deconvolved first -- ``Instrument.deconvolve``, Richardson-Lucy against
+the instrument's PSF, binning and noise model, ``N`` updates, or ``auto``: at most 200, stopped per channel by the discrepancy
+rule -- added on the ``bin`` times finer frame ``Instrument.latent_grid`` describes, and trained on rays with the pixel loss (a
+deconvolved pixel no longer follows the detector's noise model, so ``--likelihood`` does not apply to this run).  Its report
+carries the updates applied and the deviance per valid pixel of every view and channel.
+
     python tools/closed_loop.py [--module dt|emission] [--views 8] [--size 64] [--steps 300] [--batch 2048] [--d-filter 256] [--baseline]
                                 [--instrument SPEC [--through-instrument] [--patch 16] [--patches-per-batch N] [--through-steps K]]
-                                [--likelihood observed|model] [--lambda-ssim L [--ssim-window 7]] [--skip-clean]
+                                [--likelihood observed|model] [--lambda-ssim L [--ssim-window 7]] [--deconvolve N|auto] [--skip-clean]
 """
 import argparse
 import json
@@ -86,17 +93,24 @@ def baseline_scores(module, obs):
     return {'baseline.loss': loss.item(), 'baseline.ssim': scores['ssim'][0].item(), 'baseline.psnr': (-10. * torch.log10(loss)).item()}
 
 
-def observed_view(instrument, render, grid, index, n_views):
-    """``render(grid)`` -> planes (C, H, W) of view ``index`` on ``grid``; a training view of an instrument run is rendered
-    ``bin`` times finer over the same field of view and observed, the held-out view and a clean run are not."""
+def observed_view(instrument, render, grid, index, n_views, deconvolve=None):
+    """``(planes, grid of the planes)``: ``render(grid)`` -> planes (C, H, W) of view ``index`` on ``grid``; a training view of an
+    instrument run is rendered ``bin`` times finer over the same field of view and observed, the held-out view and a clean run
+    are not.  ``deconvolve`` (``iterations``, ``stop``, ``log``): the observed view is deconvolved and lies on the latent grid."""
     if instrument is None or index == hold_out_index(n_views):
-        return render(grid)
+        return render(grid), grid
     h, w = grid['shape']
     fine = resampled_grid(grid, (h * instrument.bin, w * instrument.bin))
-    return instrument.observe(render(fine).contiguous(), seed=index)['image']
+    image = instrument.observe(render(fine).contiguous(), seed=index)['image']
+    if deconvolve is None:
+        return image, grid
+    out = instrument.deconvolve(image, iterations=deconvolve['iterations'], stop=deconvolve['stop'])
+    deconvolve['log'].append({'view': index, 'iterations': out['iterations'].tolist(), 'deviance': out['deviance'].tolist(),
+                              'stopped': out['stopped'].tolist()})
+    return out['image'], instrument.latent_grid(grid)
 
 
-def density_temperature_problem(args, grid, poses, instrument=None, mode=None):
+def density_temperature_problem(args, grid, poses, instrument=None, mode=None, deconvolve=None):
     fx = np.load(os.path.join(R, 'tests', 'golden', 'g9_simple_star.npz'))
     table = (fx['aia_logte'], fx['aia_tresp'])
     cfg = dict(sampling_config={'type': 'stratified', 'n_samples': 64, 'perturb': True},
@@ -122,8 +136,8 @@ def density_temperature_problem(args, grid, poses, instrument=None, mode=None):
         if instrument is None:
             obs.add_rendered_view(truth, lat, lon, 0.0, wl=np.array(WL), scale=scale)
             continue
-        obs.add_view(observed_view(instrument, render_of(lat, lon), grid, index, len(poses)), lat, lon, time=0.0, grid=grid,
-                     wavelengths=np.array(WL))
+        planes, view_grid = observed_view(instrument, render_of(lat, lon), grid, index, len(poses), deconvolve)
+        obs.add_view(planes, lat, lon, time=0.0, grid=view_grid, wavelengths=np.array(WL))
     module = DensityTemperatureSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={}, model=NeRF_DT,
                                             pixel_intensity_factor=1e10, response_table=table,
                                             model_config={'d_filter': args.d_filter},
@@ -135,7 +149,7 @@ def density_temperature_problem(args, grid, poses, instrument=None, mode=None):
     return obs, module, render_of, np.array(WL)
 
 
-def emission_problem(args, grid, poses, instrument=None, mode=None):
+def emission_problem(args, grid, poses, instrument=None, mode=None, deconvolve=None):
     from sunerf.evaluation.loader import linear_plate_scale_axes
     from sunerf_hip.rays import grid_rays, pose_spherical
     obs = ObservationSet(Rs_per_ds=1.0, seconds_per_dt=1.0, device='cuda')
@@ -149,7 +163,8 @@ def emission_problem(args, grid, poses, instrument=None, mode=None):
             return image.reshape(1, *g['shape'])
         return render
     for index, (lat, lon) in enumerate(poses):
-        obs.add_view(observed_view(instrument, render_of(lat, lon), grid, index, len(poses))[0], lat, lon, time=0.0, grid=grid)
+        planes, view_grid = observed_view(instrument, render_of(lat, lon), grid, index, len(poses), deconvolve)
+        obs.add_view(planes[0], lat, lon, time=0.0, grid=view_grid)
     module = EmissionSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={'vmax': 1, 'a': 0.005},
                                   sampling_config={'type': 'stratified', 'n_samples': 64, 'perturb': True},
                                   hierarchical_sampling_config={'type': 'hierarchical', 'n_samples': 128, 'perturb': True},
@@ -191,6 +206,8 @@ def main():
                     help="the instrument runs train on the instrument's noise likelihood in place of the MSE")
     ap.add_argument('--lambda-ssim', type=float, default=0.0, help='weight of the structural (D-SSIM) term of the patch run')
     ap.add_argument('--ssim-window', type=int, default=7, help='side of the SSIM window in detector pixels (odd, 3 .. 11)')
+    ap.add_argument('--deconvolve', metavar='N|auto', default=None,
+                    help='a further run on Richardson-Lucy deconvolved views: N updates, or auto: the discrepancy rule')
     args = ap.parse_args()
     if args.lambda_ssim > 0 and not args.through_instrument:
         ap.error('--lambda-ssim needs --through-instrument: only patch batches have neighbouring pixels')
@@ -198,6 +215,14 @@ def main():
         ap.error('--likelihood needs --instrument SPEC')
     if args.through_instrument and args.instrument is None:
         ap.error('--through-instrument needs --instrument SPEC')
+    deconvolve = None
+    if args.deconvolve is not None:
+        if args.instrument is None:
+            ap.error('--deconvolve needs --instrument SPEC')
+        if args.deconvolve != 'auto' and not (args.deconvolve.isdigit() and int(args.deconvolve) <= 10000):
+            ap.error('--deconvolve takes a number of updates (at most 10000) or auto')
+        deconvolve = {'iterations': 200, 'stop': 'discrepancy', 'log': []} if args.deconvolve == 'auto' else \
+            {'iterations': int(args.deconvolve), 'stop': None, 'log': []}
     grid = {'shape': (args.size, args.size), 'cdelt': (2.2 * 960. / args.size, 2.2 * 960. / args.size),
             'meta': {'t_obs': '2022-01-01T00:00:00.000'}}
     poses = [(0.1 * (k % 3 - 1), 0.3 - 6.2832 / args.views * k) for k in range(args.views)]
@@ -220,13 +245,22 @@ def main():
                   f"of ray training ({seen['steps']} steps of {seen['rays_per_step']} rays)", file=sys.stderr)
             more = ('patch', 'patches', 'dropped', 'halo_overhead') + (('lambda_ssim', 'train_ssim') if args.lambda_ssim > 0 else ())
             report['through_instrument'] = {k: through[k] for k in keys + more}
+        if deconvolve is not None:
+            dec = run(args, grid, poses, Instrument.from_spec(args.instrument), deconvolve=deconvolve)
+            applied = [n for view in deconvolve['log'] for n in view['iterations']]
+            print(f"views deconvolved first ({args.deconvolve}: {min(applied)} .. {max(applied)} updates), {dec['steps']} steps of "
+                  f"{dec['rays_per_step']} rays: PSNR {dec['after']['validation.psnr']:.2f} dB, SSIM {dec['after']['validation.ssim']:.4f}; at "
+                  f"bin times the resolution {dec['after_fine']['validation.psnr']:.2f} dB against "
+                  f"{seen['after_fine']['validation.psnr']:.2f} dB of ray training on the observed views", file=sys.stderr)
+            report['deconvolved'] = {'deconvolve': args.deconvolve, 'views': deconvolve['log'], **{k: dec[k] for k in keys if k in dec}}
     print(json.dumps({'closed_loop': report}))
 
 
-def run(args, grid, poses, instrument, through=False):
+def run(args, grid, poses, instrument, through=False, deconvolve=None):
     torch.manual_seed(0)
     problem = density_temperature_problem if args.module == 'dt' else emission_problem
-    obs, module, render_of, wavelengths = problem(args, grid, poses, instrument, args.likelihood if instrument is not None else None)
+    mode = args.likelihood if instrument is not None and deconvolve is None else None
+    obs, module, render_of, wavelengths = problem(args, grid, poses, instrument, mode, deconvolve)
     obs.hold_out('reference')
     steps = args.steps
     if through:
