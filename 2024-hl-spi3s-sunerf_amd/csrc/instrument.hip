@@ -1,97 +1,35 @@
 // A rendered frame becomes a detector image: strided correlation with the PSF-and-bin kernel, photon and read noise,
 // digitisation, saturation (include/sunerf_hip_instrument.h).
 //
-// 1. Correlation.  A workgroup takes a tile of T x T detector pixels of one plane, T = min(32, (127 - max(kh, kw)) / bin + 1):
-//    all 256 threads stage the input tile with its halo, ((T - 1) bin + kh) x ((T - 1) bin + kw) fp32 words (at most 127 x 127 =
-//    63 KiB), in LDS -- the boundary rule is applied there, once per staged word -- and every thread then owns up to four output
-//    pixels (output t + 256 m of the tile, row-major) and walks the taps in the header's order, row by row.  The tap K[i][j] is
-//    the same for every lane: its address is built from blockIdx and the loop counters only, so it is fetched by a scalar load
-//    into SGPRs, once per wave, and the inner loop is one LDS read, one convert, one fp64 multiply and one fp64 add per output.
+// 1. Correlation.  The tile rule, the staging under the boundary rule and the tap loop are corr_bin.h's, which explains them; the
+//    kernel here is the loop over tiles and the store.
 // 2. Noise.  One thread per element; the generator is Philox4x32-10 keyed by the seed and counted by the element's index, so the
 //    value of an element does not depend on the launch geometry, on its neighbours or on how a frame is cut into calls.
 // No floating-point atomics; -ffp-contract=off and no explicit fma: every operation is rounded on its own, as the header says.
-#include "sunerf_common.h"
+#include "corr_bin.h"
 #include "../../include/sunerf_hip_instrument.h"
 
 namespace {
 
-constexpr int CB_THREADS = 256;
-constexpr int CB_MAX_WORDS = 127 * 127;        // LDS words of the largest input tile
-
-static_assert(SUNERF_INSTRUMENT_TILE * SUNERF_INSTRUMENT_TILE == 4 * CB_THREADS, "four outputs per thread at most");
-static_assert(SUNERF_INSTRUMENT_TILE - 1 + SUNERF_INSTRUMENT_MAX_KERNEL == 127, "the largest tile is 127 words wide");
-
-struct CorrArgs {
-  int n_planes, height, width, out_h, out_w;
-  int n_kernels, kh, kw, bin, ay, ax;
-  int tile, tiles_y, tiles_x;
-  double scale;
-};
-
-int corr_tile(int kh, int kw, int bin) {
-  const int k = kh > kw ? kh : kw;
-  const int t = (127 - k) / bin + 1;
-  return t < SUNERF_INSTRUMENT_TILE ? t : SUNERF_INSTRUMENT_TILE;
-}
-
 template <bool NEAREST, int NM>
 __global__ __launch_bounds__(CB_THREADS) void instrument_correlate_kernel(const float* __restrict__ in, const double* __restrict__ K,
-                                                                          float* __restrict__ out, CorrArgs a) {
+                                                                          float* __restrict__ out, CorrBinArgs a) {
   extern __shared__ float tile[];                // [lh][lw]
-  const int t = threadIdx.x;
-  const int T = a.tile;
-  const int lh = (T - 1) * a.bin + a.kh, lw = (T - 1) * a.bin + a.kw;
-  const int64_t in_px = (int64_t)a.height * a.width, out_px = (int64_t)a.out_h * a.out_w;
+  const int64_t out_px = (int64_t)a.out_h * a.out_w;
   const int64_t tiles_per_plane = (int64_t)a.tiles_y * a.tiles_x;
   const int64_t n_tiles = tiles_per_plane * a.n_planes;
   for (int64_t tile_id = blockIdx.x; tile_id < n_tiles; tile_id += gridDim.x) {
     const int64_t plane = tile_id / tiles_per_plane;
     const int in_plane = (int)(tile_id - plane * tiles_per_plane);
-    const int r0 = (in_plane / a.tiles_x) * T, c0 = (in_plane % a.tiles_x) * T;       // first output pixel of the tile
-    const int y0 = r0 * a.bin - a.ay, x0 = c0 * a.bin - a.ax;                         // input pixel of LDS word (0, 0)
-    const float* src = in + plane * in_px;
-    for (int i = t; i < lh * lw; i += CB_THREADS) {
-      const int ly = i / lw;
-      int y = y0 + ly, x = x0 + (i - ly * lw);
-      float v = 0.f;
-      if (NEAREST) {
-        y = y < 0 ? 0 : (y >= a.height ? a.height - 1 : y);
-        x = x < 0 ? 0 : (x >= a.width ? a.width - 1 : x);
-        v = src[(int64_t)y * a.width + x];
-      } else if (y >= 0 && y < a.height && x >= 0 && x < a.width) {
-        v = src[(int64_t)y * a.width + x];
-      }
-      tile[i] = v;
-    }
+    const int r0 = (in_plane / a.tiles_x) * a.tile, c0 = (in_plane % a.tiles_x) * a.tile;      // first output pixel of the tile
+    corr_stage_tile<NEAREST>(tile, in, a, plane, r0, c0);
     __syncthreads();
-    int base[NM];
-    bool live[NM];
     double acc[NM];
+    corr_sum_taps<NM>(tile, plane_taps(K, a, plane), a, r0, c0, acc);
 #pragma unroll
     for (int m = 0; m < NM; ++m) {
-      const int o = t + CB_THREADS * m;
-      const int r = o / T, c = o - r * T;
-      live[m] = o < T * T && r0 + r < a.out_h && c0 + c < a.out_w;
-      base[m] = live[m] ? (r * a.bin) * lw + c * a.bin : 0;          // a dead slot reads word (i, j): inside the tile
-      acc[m] = -0.0;                              // -0.0 + x == x for every x: the first product starts the sum
-    }
-    const double* taps = K + (a.n_kernels == 1 ? (int64_t)0 : plane) * a.kh * a.kw;      // wave-uniform
-    for (int i = 0; i < a.kh; ++i) {
-      const float* row = tile + i * lw;
-#pragma unroll 8
-      for (int j = 0; j < a.kw; ++j) {          // unrolled: eight taps per scalar load, eight LDS reads in flight per output
-        const double w = taps[i * a.kw + j];
-#pragma unroll
-        for (int m = 0; m < NM; ++m) acc[m] = acc[m] + w * (double)row[base[m] + j];
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < NM; ++m) {
-      if (live[m]) {
-        const int o = t + CB_THREADS * m;
-        const int r = o / T, c = o - r * T;
-        out[plane * out_px + (int64_t)(r0 + r) * a.out_w + c0 + c] = (float)(a.scale * acc[m]);
-      }
+      const CorrOutput o = corr_output(a, r0, c0, m);
+      if (o.live) out[plane * out_px + (int64_t)(r0 + o.r) * a.out_w + c0 + o.c] = (float)(a.scale * acc[m]);
     }
     __syncthreads();                             // the tile is overwritten by the next one
   }
@@ -208,13 +146,8 @@ __global__ __launch_bounds__(NZ_THREADS) void instrument_noise_kernel(const floa
   }
 }
 
-unsigned grid_of(int64_t work) {
-  const int64_t cap = (int64_t)1 << 20;
-  return (unsigned)(work < 1 ? 1 : (work < cap ? work : cap));
-}
-
 template <bool NEAREST>
-void launch_correlate(int nm, dim3 grid, size_t lds, hipStream_t st, const float* in, const double* K, float* out, const CorrArgs& a) {
+void launch_correlate(int nm, dim3 grid, size_t lds, hipStream_t st, const float* in, const double* K, float* out, const CorrBinArgs& a) {
   switch (nm) {
     case 1: hipLaunchKernelGGL((instrument_correlate_kernel<NEAREST, 1>), grid, dim3(CB_THREADS), lds, st, in, K, out, a); break;
     case 2: hipLaunchKernelGGL((instrument_correlate_kernel<NEAREST, 2>), grid, dim3(CB_THREADS), lds, st, in, K, out, a); break;
@@ -230,23 +163,14 @@ extern "C" int sunerf_instrument_abi_version(void) { return SUNERF_INSTRUMENT_AB
 extern "C" int sunerf_instrument_correlate_bin(const float* in, int n_planes, int height, int width, const double* K, int n_kernels,
                                                int kh, int kw, int bin, int anchor_y, int anchor_x, double scale, int boundary,
                                                float* out, void* stream) {
-  if (kh > SUNERF_INSTRUMENT_MAX_KERNEL || kw > SUNERF_INSTRUMENT_MAX_KERNEL || bin > SUNERF_INSTRUMENT_MAX_BIN) return SUNERF_E_UNSUPPORTED;
-  if (boundary != SUNERF_INSTRUMENT_BOUNDARY_ZERO && boundary != SUNERF_INSTRUMENT_BOUNDARY_NEAREST) return SUNERF_E_UNSUPPORTED;
-  const bool bad_count = n_planes < 0 || height < 0 || width < 0 || kh < 1 || kw < 1 || bin < 1;
-  if (!bad_count && (n_planes == 0 || height / bin == 0 || width / bin == 0)) return 0;
-  if (bad_count || (n_kernels != 1 && n_kernels != n_planes)) return SUNERF_E_BADARG;
-  if (anchor_y < 0 || anchor_y >= kh || anchor_x < 0 || anchor_x >= kw) return SUNERF_E_BADARG;
+  bool empty;
+  const int status = corr_bin_check(n_planes, height, width, n_kernels, kh, kw, bin, anchor_y, anchor_x, boundary, &empty);
+  if (status != 0 || empty) return status;
   if (!in || !K || !out || (uintptr_t)K % sizeof(double)) return SUNERF_E_BADARG;
-  CorrArgs a;
-  a.n_planes = n_planes; a.height = height; a.width = width; a.out_h = height / bin; a.out_w = width / bin;
-  a.n_kernels = n_kernels; a.kh = kh; a.kw = kw; a.bin = bin; a.ay = anchor_y; a.ax = anchor_x;
-  a.tile = corr_tile(kh, kw, bin);
-  a.tiles_y = (a.out_h + a.tile - 1) / a.tile; a.tiles_x = (a.out_w + a.tile - 1) / a.tile;
-  a.scale = scale;
-  const int lh = (a.tile - 1) * bin + kh, lw = (a.tile - 1) * bin + kw;
-  if (lh * lw > CB_MAX_WORDS) return SUNERF_E_UNSUPPORTED;          // cannot happen inside the limits above
-  const size_t lds = (size_t)lh * lw * sizeof(float);
-  const int nm = (a.tile * a.tile + CB_THREADS - 1) / CB_THREADS;
+  const CorrBinArgs a = corr_bin_args(n_planes, height, width, n_kernels, kh, kw, bin, anchor_y, anchor_x, scale);
+  if (corr_tile_words(a) > CB_MAX_WORDS) return SUNERF_E_UNSUPPORTED;          // cannot happen inside the limits above
+  const size_t lds = (size_t)corr_tile_words(a) * sizeof(float);
+  const int nm = corr_outputs_per_thread(a);
   const dim3 grid(grid_of((int64_t)a.tiles_y * a.tiles_x * n_planes));
   hipStream_t st = (hipStream_t)stream;
   SUNERF_CLEAR_ERROR();

@@ -271,11 +271,6 @@ size_t os_workspace(int n_planes, int64_t n_values, int n_ranks) {
   return (size_t)n_planes * n_ranks * sizeof(OsState) + (size_t)n_planes * g * ((size_t)n_ranks * 256 + 1) * sizeof(uint32_t);
 }
 
-unsigned grid_of(int64_t work) {
-  const int64_t cap = (int64_t)1 << 20;
-  return (unsigned)(work < 1 ? 1 : (work < cap ? work : cap));
-}
-
 template <bool ALONG_X>
 int launch_prefilter(const PrefilterArgs& a, hipStream_t st) {
   const size_t lds = (size_t)(PREP_SEGMENT + 2 * a.halo) * PF_LS * sizeof(double);

@@ -124,6 +124,12 @@ __host__ __device__ inline int kmap_encoding(int s, int h, int e) {
 // row of a 32x32 accumulator tile held by register g on lane half h
 __host__ __device__ inline int acc_row(int g, int h) { return (g & 3) + 8 * (g >> 2) + 4 * h; }
 
+// blocks of a grid-stride kernel over `work` items (host): at least one, at most 2^20
+static inline unsigned grid_of(int64_t work) {
+  const int64_t cap = (int64_t)1 << 20;
+  return (unsigned)(work < 1 ? 1 : (work < cap ? work : cap));
+}
+
 // hipGetLastError() reports the last error of ANY earlier runtime call on this thread (e.g. a probe made by the
 // caller's framework): clear it before a launch so that the check after the launch sees only our own.
 // Experiment knob (tools/experiments/overlap_probe.py): SUNERF_GRID_CAP_FWD / _DGRAD limit a persistent kernel's grid

@@ -1,6 +1,7 @@
 """Richardson-Lucy deconvolution on the device (include/sunerf_hip_deconvolve.h) against the fp64 restatement
 tests/deconvolve_reference.py: the iterates by bits, the deviance to 1e-12 of the size of its terms, masking, determinism,
-independence of the planes of a batch (their stops included), the call without an update, and ``Instrument.deconvolve``.
+independence of the planes of a batch (their stops included), the call without an update, one update against the adjoint entry
+by bits, and ``Instrument.deconvolve``.
 
 One reference run of five updates per (case, boundary) serves every test: pass k of it describes the iterate after k updates, so it
 holds the iterate and the state of every shorter call.  Gates: ``u`` is made of +, * and / in a pinned order -- bits.  The deviance
@@ -197,6 +198,29 @@ def test_no_iterations_leaves_u_untouched_and_fills_the_state(case, boundary):
     assert np.array_equal(u.view(np.uint32), u0.view(np.uint32))
     assert np.isfinite(state).all() and np.isfinite(ratio).all() and (ratio >= 0).all() and ratio.any()
     assert state[:, 2].tolist() == [0.0] * case[0] and state[:, 1].tolist() == [h[0][1] for h in history]
+
+
+@pytest.mark.parametrize('boundary', dr.BOUNDARIES)
+@pytest.mark.parametrize('case', [dr.CASES[1], dr.CASES[3], dr.CASES[4], dr.CASES[7]], ids=_IDS)
+def test_one_update_from_ones_is_the_adjoint_entry_on_the_ratio_by_bits(case, boundary):
+    """The update kernel and ``sunerf_patch_correlate_bin_adjoint`` share their sums (csrc/corr_bin.h): tied together directly, not
+    through the restatement.  With u0 = 1, a caller's norm = 1 and no stop, the call without an update returns the ratio of the
+    start, and one update from the same start is u = (float)((1.0 * (scale acc)) / 1.0) = (float)(scale acc) -- products and
+    quotients by 1.0 are exact in fp64 -- which is what the adjoint entry stores for the same ratio.  Per-plane kernels, bin 3, a
+    plane in which every tap clamps, partial last tiles of both tilings; the data's NaN and ``bad`` pixel put zeros into the ratio."""
+    from sunerf_hip.instrument import BOUNDARY, correlate_bin_adjoint
+    (K, _, d, bad, c, v), _, _, _ = _reference(case, boundary)
+    ones = np.ones((case[0], case[1], case[2]), dtype=np.float32)
+    u, state, ratio = _rl(ones, d, bad, ones, K, c, v, case, boundary, 0)
+    assert np.array_equal(u.view(np.uint32), ones.view(np.uint32)) and state[:, 2].tolist() == [0.0] * case[0]
+    assert (ratio == 0).any() and (ratio > 0).any() and np.isfinite(ratio).all()
+    u, state, _ = _rl(ones, d, bad, ones, K, c, v, case, boundary, 1)
+    assert state[:, 2].tolist() == [1.0] * case[0] and state[:, 3].tolist() == [0.0] * case[0]
+    taps = torch.tensor(K, dtype=torch.float64).to(DEV)
+    want = correlate_bin_adjoint(torch.tensor(ratio).to(DEV), case[1], case[2], taps, K.shape[0], K.shape[1], K.shape[2], case[5],
+                                 case[6][0], case[6][1], _scale(case), BOUNDARY[boundary])
+    _same_bits(u, want.cpu().numpy(), f'{case} {boundary}: one update from ones against the adjoint of the ratio')
+    assert (u != ones).any()
 
 
 # ---- 4. the Python level ----------------------------------------------------------------------------------------------------------
