@@ -19,6 +19,8 @@
 //    forward: the plane's kernel is staged in LDS (fp64, regrouped by j mod bin so that a pixel's taps lie side by side) beside
 //    the slice of g_out that the tile's taps reach (fp32).  Every range lies inside that slice by construction; the loops clamp
 //    to it all the same, so no LDS address depends on that argument.
+// 3. Tap gradient (psf_grad.hip).  It takes the correlation's tiles, its argument check and corr_stage_tile from
+//    here and keeps its own loop (threads own taps, not outputs) in its file.
 // No floating-point atomics; -ffp-contract=off and no explicit fma: every operation is rounded on its own, as the headers say.
 #pragma once
 #include "sunerf_common.h"
@@ -58,10 +60,11 @@ static inline bool corr_bin_within_limits(int kh, int kw, int bin) {
   return kh <= SUNERF_INSTRUMENT_MAX_KERNEL && kw <= SUNERF_INSTRUMENT_MAX_KERNEL && bin <= SUNERF_INSTRUMENT_MAX_BIN;
 }
 
-// The check the three entry points share, in the order their headers state: limits and an unknown boundary, then the empty call
+// The check the four entry points share, in the order their headers state: limits and an unknown boundary, then the empty call
 // (*empty is set: the caller returns 0), then counts, n_kernels and anchors.  The caller's own checks follow a 0 with *empty false.
+// `any_divisor`: n_kernels may be any divisor of n_planes (psf_grad.hip: plane p takes kernel p % n_kernels), not 1 or n_planes only.
 static inline int corr_bin_check(int n_planes, int height, int width, int n_kernels, int kh, int kw, int bin, int anchor_y, int anchor_x,
-                                 int boundary, bool* empty) {
+                                 int boundary, bool* empty, bool any_divisor = false) {
   *empty = false;
   if (!corr_bin_within_limits(kh, kw, bin)) return SUNERF_E_UNSUPPORTED;
   if (boundary != SUNERF_INSTRUMENT_BOUNDARY_ZERO && boundary != SUNERF_INSTRUMENT_BOUNDARY_NEAREST) return SUNERF_E_UNSUPPORTED;
@@ -70,7 +73,8 @@ static inline int corr_bin_check(int n_planes, int height, int width, int n_kern
     *empty = true;
     return 0;
   }
-  if (bad_count || (n_kernels != 1 && n_kernels != n_planes)) return SUNERF_E_BADARG;
+  if (bad_count) return SUNERF_E_BADARG;
+  if (any_divisor ? (n_kernels < 1 || n_planes % n_kernels != 0) : (n_kernels != 1 && n_kernels != n_planes)) return SUNERF_E_BADARG;
   if (anchor_y < 0 || anchor_y >= kh || anchor_x < 0 || anchor_x >= kw) return SUNERF_E_BADARG;
   return 0;
 }

@@ -36,7 +36,7 @@ class BaseSuNeRFModule(LightningModule):
     """sunerf.py:15-59."""
 
     def __init__(self, Rs_per_ds, seconds_per_dt, rendering: SuNeRFRendering, validation_dataset_mapping=None,
-                 lr_config=None, likelihood=None):
+                 lr_config=None, likelihood=None, psf_models=None):
         super().__init__()
         self.Rs_per_ds = Rs_per_ds
         self.seconds_per_dt = seconds_per_dt
@@ -47,6 +47,13 @@ class BaseSuNeRFModule(LightningModule):
         # a sunerf_hip.likelihood.NoiseLikelihood replaces the MSE of training_step by the detector model's
         # noise likelihood; a child module, so that checkpoints carry its log_gain.  None: the reference's loss.
         self.likelihood = likelihood
+        # sunerf_hip.psf_fit.TrainablePSF models, one or a sequence: the PSFs of the FittedInstruments the patch
+        # batches observe through, trained beside the network; a child ModuleList, so that checkpoints carry them.  None: nothing
+        # is registered.
+        if psf_models is None:
+            self.psf_models = None
+        else:
+            self.psf_models = nn.ModuleList([psf_models] if isinstance(psf_models, nn.Module) else list(psf_models))
         self.last_channel_stats = None
         self._init_ssim()
 
@@ -95,10 +102,13 @@ class BaseSuNeRFModule(LightningModule):
         return loss + (self.lambda_ssim * term).to(loss.dtype)
 
     def _trainable_parameters(self):
-        """What the optimiser updates: the rendering's parameters and, when any gain of the likelihood is free, its log_gain."""
+        """What the optimiser updates: the rendering's parameters, when any gain of the likelihood is free its log_gain, and the
+        parameters of the psf_models that require a gradient."""
         params = list(self.rendering.parameters())
         if self.likelihood is not None and any(p.requires_grad for p in self.likelihood.parameters()):
             params += list(self.likelihood.parameters())
+        if self.psf_models is not None:
+            params += [p for p in self.psf_models.parameters() if p.requires_grad]
         return params
 
     def _likelihood_step(self, coarse, fine, target, codes, outputs, ssim_spec=None):

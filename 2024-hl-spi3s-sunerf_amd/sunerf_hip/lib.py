@@ -289,6 +289,18 @@ _DECONVOLVE_SIGNATURES = {
 DECONVOLVE_SYMBOLS = tuple(_DECONVOLVE_SIGNATURES)
 DECONVOLVE_ABI_VERSION = 1
 
+# The PSF-gradient table (include/sunerf_hip_psf_grad.h): the derivative of the PSF-and-bin correlation with respect to its taps.
+# A tenth table beside the nine above, which stay as they are and keep their versions.
+_PSF_GRAD_SIGNATURES = {
+    'sunerf_psf_grad_abi_version': (ctypes.c_int, []),
+    'sunerf_psf_grad_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 7),
+    'sunerf_psf_grad_taps': (ctypes.c_int, [c_f32p, c_f32p] + [ctypes.c_int] * 9 + [ctypes.c_double, ctypes.c_int, c_void, c_void,
+                                                                                     c_void]),
+}
+
+PSF_GRAD_SYMBOLS = tuple(_PSF_GRAD_SIGNATURES)
+PSF_GRAD_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -357,6 +369,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_deconvolve_abi_version() != DECONVOLVE_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so deconvolution ABI version mismatch')
+        for name, (res, args) in _PSF_GRAD_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_psf_grad_abi_version() != PSF_GRAD_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so PSF-gradient ABI version mismatch')
         _lib = lib
     return _lib
 

@@ -44,13 +44,23 @@ rule -- added on the ``bin`` times finer frame ``Instrument.latent_grid`` descri
 deconvolved pixel no longer follows the detector's noise model, so ``--likelihood`` does not apply to this run).  Its report
 carries the updates applied and the deviance per valid pixel of every view and channel.
 
+``--fit-psf FWHM0`` (with ``--through-instrument``; a Gaussian ``--instrument``): the PSF as a trainable part of the model
+(DESIGN.md 8t).  Three patch runs on the same observed views, one seed each: the right PSF (the ``through_instrument`` run above),
+a wrong PSF held fixed (a Gaussian of ``FWHM0`` in place of the instrument's own width), and the wrong PSF fitted -- a
+``FittedInstrument`` over ``TrainablePSF.gaussian(FWHM0, rate=--psf-rate)`` handed to the module as ``psf_models``, so that the
+optimiser of the network moves ``log_fwhm`` too.  The report (``fit_psf``) carries the fitted ``fwhm`` per step count and the
+held-out scores of the two runs beside those of the right PSF.
+
     python tools/closed_loop.py [--module dt|emission] [--views 8] [--size 64] [--steps 300] [--batch 2048] [--d-filter 256] [--baseline]
                                 [--instrument SPEC [--through-instrument] [--patch 16] [--patches-per-batch N] [--through-steps K]]
                                 [--likelihood observed|model] [--lambda-ssim L [--ssim-window 7]] [--deconvolve N|auto] [--skip-clean]
+                                [--fit-psf FWHM0 [--psf-rate 20]]
 """
 import argparse
 import json
+import math
 import os
+import re
 import sys
 import time
 
@@ -110,7 +120,7 @@ def observed_view(instrument, render, grid, index, n_views, deconvolve=None):
     return out['image'], instrument.latent_grid(grid)
 
 
-def density_temperature_problem(args, grid, poses, instrument=None, mode=None, deconvolve=None):
+def density_temperature_problem(args, grid, poses, instrument=None, mode=None, deconvolve=None, psf_models=None):
     fx = np.load(os.path.join(R, 'tests', 'golden', 'g9_simple_star.npz'))
     table = (fx['aia_logte'], fx['aia_tresp'])
     cfg = dict(sampling_config={'type': 'stratified', 'n_samples': 64, 'perturb': True},
@@ -144,12 +154,12 @@ def density_temperature_problem(args, grid, poses, instrument=None, mode=None, d
                                             lr_config={'start': 5e-4, 'end': 5e-5, 'iterations': args.steps},
                                             likelihood=None if mode is None else NoiseLikelihood(instrument, codes=[int(w) for w in WL], mode=mode),
                                             lambda_ssim=args.lambda_ssim, ssim_window=args.ssim_window,
-                                            ssim_data_range=1.0 if args.lambda_ssim > 0 else None,
+                                            ssim_data_range=1.0 if args.lambda_ssim > 0 else None, psf_models=psf_models,
                                             **{k: dict(v) for k, v in cfg.items()}).cuda()
     return obs, module, render_of, np.array(WL)
 
 
-def emission_problem(args, grid, poses, instrument=None, mode=None, deconvolve=None):
+def emission_problem(args, grid, poses, instrument=None, mode=None, deconvolve=None, psf_models=None):
     from sunerf.evaluation.loader import linear_plate_scale_axes
     from sunerf_hip.rays import grid_rays, pose_spherical
     obs = ObservationSet(Rs_per_ds=1.0, seconds_per_dt=1.0, device='cuda')
@@ -171,7 +181,7 @@ def emission_problem(args, grid, poses, instrument=None, mode=None, deconvolve=N
                                   model_config={'d_filter': args.d_filter},
                                   lr_config={'start': 5e-4, 'end': 5e-5, 'iterations': args.steps},
                                   likelihood=None if mode is None else NoiseLikelihood(instrument, mode=mode),
-                                  lambda_ssim=args.lambda_ssim, ssim_window=args.ssim_window).cuda()
+                                  lambda_ssim=args.lambda_ssim, ssim_window=args.ssim_window, psf_models=psf_models).cuda()
     return obs, module, render_of, None
 
 
@@ -208,7 +218,14 @@ def main():
     ap.add_argument('--ssim-window', type=int, default=7, help='side of the SSIM window in detector pixels (odd, 3 .. 11)')
     ap.add_argument('--deconvolve', metavar='N|auto', default=None,
                     help='a further run on Richardson-Lucy deconvolved views: N updates, or auto: the discrepancy rule')
+    ap.add_argument('--fit-psf', type=float, metavar='FWHM0', default=None,
+                    help='two further patch runs from a Gaussian PSF of this width: held fixed, and fitted beside the network')
+    ap.add_argument('--psf-rate', type=float, default=20.0, help='rate of the TrainablePSF: its log_fwhm moves at rate x the learning rate')
     args = ap.parse_args()
+    if args.fit_psf is not None and not args.through_instrument:
+        ap.error('--fit-psf needs --through-instrument')
+    if args.fit_psf is not None and (not args.fit_psf > 0 or 'fwhm=' not in args.instrument or 'beta=' in args.instrument):
+        ap.error('--fit-psf takes a width > 0 and needs a Gaussian --instrument SPEC (fwhm=..., no beta=)')
     if args.lambda_ssim > 0 and not args.through_instrument:
         ap.error('--lambda-ssim needs --through-instrument: only patch batches have neighbouring pixels')
     if args.likelihood is not None and args.instrument is None:
@@ -245,6 +262,8 @@ def main():
                   f"of ray training ({seen['steps']} steps of {seen['rays_per_step']} rays)", file=sys.stderr)
             more = ('patch', 'patches', 'dropped', 'halo_overhead') + (('lambda_ssim', 'train_ssim') if args.lambda_ssim > 0 else ())
             report['through_instrument'] = {k: through[k] for k in keys + more}
+            if args.fit_psf is not None:
+                report['fit_psf'] = fit_psf_runs(args, grid, poses, through, keys)
         if deconvolve is not None:
             dec = run(args, grid, poses, Instrument.from_spec(args.instrument), deconvolve=deconvolve)
             applied = [n for view in deconvolve['log'] for n in view['iterations']]
@@ -256,16 +275,56 @@ def main():
     print(json.dumps({'closed_loop': report}))
 
 
-def run(args, grid, poses, instrument, through=False, deconvolve=None):
+def fit_psf_runs(args, grid, poses, right, keys):
+    """The two further patch runs of ``--fit-psf``: the views are those the true instrument observed; the patches are seen through
+    a Gaussian of ``FWHM0``, held fixed in one run and fitted in the other."""
+    from sunerf_hip.psf_fit import FittedInstrument, TrainablePSF
+    true = Instrument.from_spec(args.instrument)
+    true_fwhm = float(re.search(r'fwhm=([^,]+)', args.instrument).group(1))
+    wrong_spec = re.sub(r'fwhm=[^,]+', f'fwhm={args.fit_psf}', args.instrument)
+    wrong = run(args, grid, poses, true, through=True, model_instrument=Instrument.from_spec(wrong_spec))
+    radius = re.search(r'radius=([^,]+)', args.instrument)
+    psf = TrainablePSF.gaussian(args.fit_psf, int(radius.group(1)) if radius else math.ceil(3 * max(args.fit_psf, true_fwhm)),
+                                rate=args.psf_rate).cuda()
+    scalars = {name: getattr(true, name) for name in ('unit', 'exposure', 'dn_per_photon', 'read_noise', 'pedestal', 'saturation')}
+    fitted_instrument = FittedInstrument(psf, bin=true.bin, bin_mode=true.bin_mode, boundary=true.boundary, quantise=true.quantise, **scalars)
+    fitted = run(args, grid, poses, true, through=True, model_instrument=fitted_instrument, psf_model=psf)
+    out = {'true_fwhm': true_fwhm, 'start_fwhm': args.fit_psf, 'psf_rate': args.psf_rate,
+           'right_psf': {k: right[k] for k in ('after', 'after_fine')},
+           'wrong_psf_fixed': {k: wrong[k] for k in keys},
+           'wrong_psf_fitted': {**{k: fitted[k] for k in keys}, 'fwhm_by_step': fitted['fwhm_by_step']}}
+    for name in ('right_psf', 'wrong_psf_fixed', 'wrong_psf_fitted'):
+        print(f"fit-psf, {name}: PSNR {out[name]['after']['validation.psnr']:.2f} dB, SSIM {out[name]['after']['validation.ssim']:.4f}; at bin "
+              f"times the resolution {out[name]['after_fine']['validation.psnr']:.2f} dB", file=sys.stderr)
+    print(f"fit-psf: FWHM {args.fit_psf} -> {fitted['fwhm_by_step'][-1][1]:.4f} (the instrument's: {true_fwhm})", file=sys.stderr)
+    return out
+
+
+def _recording_fwhm(batches, psf_model, steps, record):
+    """``batches`` as they are; ``record`` takes (steps done, fwhm on the device) at eight step counts and at the end."""
+    every = max(1, steps // 8)
+    done = 0
+    for batch in batches:
+        if done % every == 0:
+            record.append((done, psf_model.fwhm[0].clone()))
+        yield batch
+        done += 1
+    record.append((done, psf_model.fwhm[0].clone()))
+
+
+def run(args, grid, poses, instrument, through=False, deconvolve=None, model_instrument=None, psf_model=None):
+    """``instrument`` observes the views; ``model_instrument`` (default: the same) is what a patch run sees its renders through;
+    ``psf_model``: the TrainablePSF of a FittedInstrument, trained beside the network."""
     torch.manual_seed(0)
     problem = density_temperature_problem if args.module == 'dt' else emission_problem
     mode = args.likelihood if instrument is not None and deconvolve is None else None
-    obs, module, render_of, wavelengths = problem(args, grid, poses, instrument, mode, deconvolve)
+    obs, module, render_of, wavelengths = problem(args, grid, poses, instrument, mode, deconvolve, psf_models=psf_model)
     obs.hold_out('reference')
     steps = args.steps
     if through:
         steps = args.steps if args.through_steps is None else args.through_steps
-        pool = obs.patch_pool(instrument, patch=args.patch, patches_per_batch=args.patches_per_batch, seed=0)
+        pool = obs.patch_pool(instrument if model_instrument is None else model_instrument, patch=args.patch,
+                              patches_per_batch=args.patches_per_batch, seed=0)
         rays_per_step = pool.rays_per_batch
     else:
         pool = obs.pool(batch_size=args.batch, seed=0, reshuffle='rays')
@@ -274,7 +333,10 @@ def run(args, grid, poses, instrument, through=False, deconvolve=None):
     before = held_out_scores(module, obs, 1 << 14)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    losses = torch.stack(fit_steps(module, training_batches(pool, steps)))
+    batches, fwhm_record = training_batches(pool, steps), []
+    if psf_model is not None:
+        batches = _recording_fwhm(batches, psf_model, steps, fwhm_record)
+    losses = torch.stack(fit_steps(module, batches))
     torch.cuda.synchronize()
     seconds = time.perf_counter() - t0
     module.check_finite(module.optimizer)
@@ -289,6 +351,8 @@ def run(args, grid, poses, instrument, through=False, deconvolve=None):
         extra.update(patch=pool.patch, patches=pool.n_patches, dropped=pool.dropped, halo_overhead=pool.halo_overhead)
         if module.last_ssim is not None:
             extra.update(lambda_ssim=module.lambda_ssim, train_ssim=(1.0 - module.last_ssim[:2]).cpu().tolist())
+        if psf_model is not None:
+            extra['fwhm_by_step'] = [[done, float(fwhm)] for done, fwhm in fwhm_record]
         return {'held_out': obs.held_out, 'steps': steps, 'rays_per_step': rays_per_step,
                 'loss_first_10': losses[:10].mean().item(), 'loss_last_10': losses[-10:].mean().item(), 'train_seconds': seconds,
                 'before': before, 'after': after, **extra}
