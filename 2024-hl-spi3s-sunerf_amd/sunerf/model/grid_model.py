@@ -47,15 +47,6 @@ def _initial_values(init, shape, d_output):
     raise ValueError(f'init has shape {tuple(init.shape)}; expected a number, {d_output} numbers or {tuple(shape)}')
 
 
-def _add_dt_head(field, channels=None):
-    """The density-temperature head of ``MHDModel`` (mhd_model.py:11-24) on a grid field; ``channels``: see
-    ``sunerf.model.model.absorption_scalars``."""
-    field.log_absortpion = absorption_scalars(channels)
-    field.volumetric_constant = nn.Parameter(torch.tensor(1.0, dtype=torch.float32, requires_grad=True))
-    field.base_log_density = 0.0
-    field.base_log_temperature = 0.0
-
-
 class GridField(nn.Module):
     """``values (n0, n1, n2, C)`` on the nodes of ``grid`` (a ``CartesianGrid`` or ``SphericalGrid`` of
     :mod:`sunerf_hip.volume`; C order over its axes, the layout of ``sample_volume``'s ``inferences``), interpolated
@@ -183,17 +174,19 @@ class GridField(nn.Module):
         return state
 
 
-class GridFieldDT(GridField):
-    """A grid of ``(ln rho, log10 T)`` with the density-temperature head exactly as ``MHDModel`` carries it (mhd_model.py:11-24):
-    the ``log_absortpion`` scalars over the AIA channels, ``volumetric_constant`` and zero base offsets, so that
-    ``DensityTemperatureRadiativeTransfer(model=GridFieldDT)`` renders and fits it.  Default ``fill``: ``(ln 1e-10, log10
-    1e-10)``, ``MHDModel``'s ``FILL_VALUE`` outside its cube."""
+class _DTHead:
+    """The density-temperature head of ``MHDModel`` (mhd_model.py:11-24) in front of a grid field of ``(ln rho, log10 T)``:
+    the ``log_absortpion`` scalars (``channels``: see ``sunerf.model.model.absorption_scalars``), ``volumetric_constant`` and
+    zero base offsets.  Default ``fill``: ``(ln 1e-10, log10 1e-10)``, ``MHDModel``'s ``FILL_VALUE`` outside its cube."""
 
     def __init__(self, grid, d_output=2, channels=None, **kwargs):
         if d_output != 2:
             raise ValueError(f'a density-temperature grid holds (ln rho, log10 T): d_output must be 2, got {d_output!r}')
         super().__init__(grid, d_output=2, **kwargs)
-        _add_dt_head(self, channels)
+        self.log_absortpion = absorption_scalars(channels)
+        self.volumetric_constant = nn.Parameter(torch.tensor(1.0, dtype=torch.float32, requires_grad=True))
+        self.base_log_density = 0.0
+        self.base_log_temperature = 0.0
 
     def _default_fill(self):
         return (math.log(1e-10), -10.0)
@@ -201,6 +194,13 @@ class GridFieldDT(GridField):
     def forward(self, query_points):
         """``{'inferences': (M, 2), 'log_abs', 'vol_c'}``, as ``NeRF_DT`` / ``MHDModel`` answer."""
         return {'inferences': self.inferences(query_points), 'log_abs': self.log_absortpion, 'vol_c': self.volumetric_constant}
+
+
+class GridFieldDT(_DTHead, GridField):
+    """A grid of ``(ln rho, log10 T)`` with the density-temperature head exactly as ``MHDModel`` carries it (mhd_model.py:11-24):
+    the ``log_absortpion`` scalars over the AIA channels, ``volumetric_constant`` and zero base offsets, so that
+    ``DensityTemperatureRadiativeTransfer(model=GridFieldDT)`` renders and fits it.  Default ``fill``: ``(ln 1e-10, log10
+    1e-10)``, ``MHDModel``'s ``FILL_VALUE`` outside its cube."""
 
 
 class DynamicGridField(GridField):
@@ -303,19 +303,6 @@ class DynamicGridField(GridField):
         return ((v[1:] - v[:-1]) / step.view(-1, 1, 1, 1, 1)).pow(2).mean()
 
 
-class DynamicGridFieldDT(DynamicGridField):
+class DynamicGridFieldDT(_DTHead, DynamicGridField):
     """:class:`DynamicGridField` of ``(ln rho, log10 T)`` with the density-temperature head exactly as :class:`GridFieldDT`
     carries it, so that ``DensityTemperatureRadiativeTransfer(model=DynamicGridFieldDT)`` renders and fits it."""
-
-    def __init__(self, grid, d_output=2, channels=None, **kwargs):
-        if d_output != 2:
-            raise ValueError(f'a density-temperature grid holds (ln rho, log10 T): d_output must be 2, got {d_output!r}')
-        super().__init__(grid, d_output=2, **kwargs)
-        _add_dt_head(self, channels)
-
-    def _default_fill(self):
-        return (math.log(1e-10), -10.0)
-
-    def forward(self, query_points):
-        """``{'inferences': (M, 2), 'log_abs', 'vol_c'}``, as ``NeRF_DT`` / ``MHDModel`` answer."""
-        return {'inferences': self.inferences(query_points), 'log_abs': self.log_absortpion, 'vol_c': self.volumetric_constant}

@@ -6,10 +6,13 @@ to any grid and channel count and gives it the gradient a fit needs.
 The backward uses no floating-point atomics: the forward leaves every sample's flattened cell id, a stable ``torch.sort`` of
 the ids gives the inverted index (permutation + segment starts), and one thread per node adds the segments of its adjacent
 cells in a fixed order -- bit-identical from run to run.
+
+The call of the forward, the backward with its sort and the autograd node are written once, for a :class:`Kind`; the field
+with a time axis (:mod:`sunerf_hip.dynamic_grid`, section 8l) is the second kind.
 """
 import ctypes
 import math
-from typing import Optional, Sequence
+from typing import Callable, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -96,7 +99,8 @@ class GridDescriptor:
             raise ValueError(f'fill has {len(fill)} values for {n_channels} channels')
         self.device = torch.device(device)
         self.grid, self.n_channels, self.lon_mode = grid, int(n_channels), int(lon_mode)
-        self.n_cells = n_cells(grid, lon_mode)
+        self.n_ids = self.n_cells = n_cells(grid, lon_mode)                           # n_ids: the sentinel of the forward
+        self.shape = (*grid._shape3, self.n_channels)                                 # of `values`
         self.axes = tuple(a.to(self.device).contiguous() for a in grid.axes)          # fp64, kept alive here
         d = GridFieldDesc()
         for k in range(3):
@@ -130,62 +134,56 @@ def affine_inverse(grid: CartesianGrid) -> torch.Tensor:
 
 
 # ---- wrappers ----------------------------------------------------------------------------------------------------------------
-def _values(desc: GridDescriptor, values: torch.Tensor) -> torch.Tensor:
-    values = _dev(values, 'values', (*desc.grid._shape3, desc.n_channels))
+class Kind(NamedTuple):
+    """What tells the static field from the one with a time axis (:mod:`sunerf_hip.dynamic_grid`) in the shared code below.  The
+    descriptors carry the rest: ``shape``, of the values, and ``n_ids``, the sentinel of the forward."""
+    label: str                  # the entry points are sunerf_<label>_fwd, _bwd and _bwd_workspace_bytes
+    width: int                  # weights per sample: 4 + 2 x the frames a sample touches
+    fwd_lead: Callable          # desc -> the arguments of _fwd between the descriptor and `values`
+    bwd_lead: Callable          # desc -> the arguments of _bwd between the descriptor and `g_raw`
+
+
+STATIC = Kind('grid_field', 6, lambda desc: (), lambda desc: ())
+
+
+def _values(desc, values: torch.Tensor) -> torch.Tensor:
+    values = _dev(values, 'values', desc.shape)
     if values.device.type != desc.device.type or (desc.device.index is not None and values.device.index != desc.device.index):
         raise ValueError(f'values are on {values.device}, the descriptor on {desc.device}')
     return values
 
 
-def _index(total: int, want_index: bool, dev):
-    if not want_index:
-        return None, None
-    return torch.empty(total, dtype=torch.int32, device=dev), torch.empty(total, 6, dtype=torch.float32, device=dev)
+def _index(total: int, width: int, dev):
+    return torch.empty(total, dtype=torch.int32, device=dev), torch.empty(total, width, dtype=torch.float32, device=dev)
 
 
-def grid_field_rays(desc: GridDescriptor, values, rays_o, rays_d, z_vals, want_index: bool = False):
-    """``raw (N, S, C)`` of the field at the samples ``o + d z``; with ``want_index`` also ``(cells (N S,) int32, weights
-    (N S, 6))`` for :func:`grid_field_bwd`."""
-    n, s = z_vals.shape
-    values = _values(desc, values)
-    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3)); z_vals = _dev(z_vals, 'z_vals', (n, s))
+def _gather(kind: Kind, desc, values, rays, points, dims, want_index: bool):
+    """One forward of checked device tensors.  ``rays``: what the entry point takes between ``values`` and the sizes, all None
+    in points mode; ``dims``: ``(N, S)``, or ``(M,)`` with ``points (M, stride)``.  Returns ``raw (*dims, C)``, with
+    ``want_index`` also ``(cells, weights)``."""
     dev = values.device
-    raw = torch.empty(n, s, desc.n_channels, dtype=torch.float32, device=dev)
-    cells, weights = _index(n * s, want_index, dev)
-    _l.call(dev, 'sunerf_grid_field_fwd', desc.ref(), _ptr(values), _ptr(rays_o), _ptr(rays_d), _ptr(z_vals), n, s, None, 0,
-            _ptr(raw), _ptr(cells), _ptr(weights), _stream(dev))
+    n, s = dims if points is None else (dims[0], 1)
+    raw = torch.empty(*dims, desc.n_channels, dtype=torch.float32, device=dev)
+    cells, weights = _index(n * s, kind.width, dev) if want_index else (None, None)
+    _l.call(dev, f'sunerf_{kind.label}_fwd', desc.ref(), *kind.fwd_lead(desc), _ptr(values), *(_ptr(r) for r in rays), n, s,
+            _ptr(points), 0 if points is None else points.shape[1], _ptr(raw), _ptr(cells), _ptr(weights), _stream(dev))
     return (raw, (cells, weights)) if want_index else raw
 
 
-def grid_field_points(desc: GridDescriptor, values, points, want_index: bool = False):
-    """``raw (M, C)`` of the field at ``points (M, 3 | 4)`` (a time column is ignored: the field is static)."""
-    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] not in (3, 4):
-        raise ValueError('points must be (M, 3) or (M, 4)')
-    values = _values(desc, values)
-    points = _dev(points, 'points')
-    m, stride = points.shape
-    dev = values.device
-    raw = torch.empty(m, desc.n_channels, dtype=torch.float32, device=dev)
-    cells, weights = _index(m, want_index, dev)
-    _l.call(dev, 'sunerf_grid_field_fwd', desc.ref(), _ptr(values), None, None, None, m, 1, _ptr(points), stride, _ptr(raw),
-            _ptr(cells), _ptr(weights), _stream(dev))
-    return (raw, (cells, weights)) if want_index else raw
+_bwd_workspaces = {}            # per entry point, then per device and stream: the two kinds share no buffer
 
 
-_bwd_workspaces = {}
-
-
-def grid_field_bwd(desc: GridDescriptor, g_raw, index, out: Optional[torch.Tensor] = None, accumulate: bool = False):
-    """The adjoint of the gather: ``g_values (n0, n1, n2, C)`` from ``g_raw (..., C)`` and the ``index = (cells, weights)`` the
-    forward left.  ``out``: a contiguous fp32 tensor of that shape to write into, or with ``accumulate`` to add onto."""
+def _scatter(kind: Kind, desc, g_raw, index, out, accumulate):
+    """The adjoint of :func:`_gather`: ``g_values`` of ``desc.shape``.  A stable sort of the ids is the permutation,
+    ``searchsorted`` of the sorted ids the start of every id's segment in it."""
     cells, weights = index
     total = cells.shape[0]
     dev = cells.device
-    shape = (*desc.grid._shape3, desc.n_channels)
+    shape = desc.shape
     g_raw = _dev(g_raw.reshape(-1, g_raw.shape[-1]), 'g_raw', (total, desc.n_channels))
     if out is None:
         if accumulate:
-            raise ValueError('grid_field_bwd: accumulate needs out=')
+            raise ValueError(f'{kind.label}_bwd: accumulate needs out=')
         out = torch.empty(shape, dtype=torch.float32, device=dev)
     elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
         raise ValueError(f'out must be a contiguous float32 tensor of shape {shape} on {dev}')
@@ -194,74 +192,86 @@ def grid_field_bwd(desc: GridDescriptor, g_raw, index, out: Optional[torch.Tenso
         nbytes = 0
     else:
         ids, perm = torch.sort(cells, stable=True)
-        seg = torch.searchsorted(ids, torch.arange(desc.n_cells + 1, dtype=torch.int32, device=dev))
-        nbytes = _l.load().sunerf_grid_field_bwd_workspace_bytes(total, desc.n_channels)
-        ws = _workspace(_bwd_workspaces, dev, nbytes)
-    _l.call(dev, 'sunerf_grid_field_bwd', desc.ref(), _ptr(g_raw), _ptr(cells), _ptr(weights), _ptr(perm), _ptr(seg), total,
-            _ptr(ws), nbytes, _ptr(out), 1 if accumulate else 0, _stream(dev))
+        seg = torch.searchsorted(ids, torch.arange(desc.n_ids + 1, dtype=torch.int32, device=dev))
+        nbytes = getattr(_l.load(), f'sunerf_{kind.label}_bwd_workspace_bytes')(total, desc.n_channels)
+        ws = _workspace(_bwd_workspaces.setdefault(kind.label, {}), dev, nbytes)
+    _l.call(dev, f'sunerf_{kind.label}_bwd', desc.ref(), *kind.bwd_lead(desc), _ptr(g_raw), _ptr(cells), _ptr(weights),
+            _ptr(perm), _ptr(seg), total, _ptr(ws), nbytes, _ptr(out), 1 if accumulate else 0, _stream(dev))
     return out
 
 
+def grid_field_rays(desc: GridDescriptor, values, rays_o, rays_d, z_vals, want_index: bool = False):
+    """``raw (N, S, C)`` of the field at the samples ``o + d z``; with ``want_index`` also ``(cells (N S,) int32, weights
+    (N S, 6))`` for :func:`grid_field_bwd`."""
+    n, s = z_vals.shape
+    values = _values(desc, values)
+    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3)); z_vals = _dev(z_vals, 'z_vals', (n, s))
+    return _gather(STATIC, desc, values, (rays_o, rays_d, z_vals), None, (n, s), want_index)
+
+
+def grid_field_points(desc: GridDescriptor, values, points, want_index: bool = False):
+    """``raw (M, C)`` of the field at ``points (M, 3 | 4)`` (a time column is ignored: the field is static)."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] not in (3, 4):
+        raise ValueError('points must be (M, 3) or (M, 4)')
+    values = _values(desc, values)
+    points = _dev(points, 'points')
+    return _gather(STATIC, desc, values, (None,) * 3, points, points.shape[:1], want_index)
+
+
+def grid_field_bwd(desc: GridDescriptor, g_raw, index, out: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """The adjoint of the gather: ``g_values (n0, n1, n2, C)`` from ``g_raw (..., C)`` and the ``index = (cells, weights)`` the
+    forward left.  ``out``: a contiguous fp32 tensor of that shape to write into, or with ``accumulate`` to add onto."""
+    return _scatter(STATIC, desc, g_raw, index, out, accumulate)
+
+
 # ---- autograd ----------------------------------------------------------------------------------------------------------------
-def _values_grad(ctx, values, g_raw):
-    """The gradient of a node's ``values`` input: added straight into a contiguous fp32 ``.grad`` the parameter already owns
+class _FieldGather(torch.autograd.Function):
+    """A grid field of either kind, on rays or at points, as an autograd node: ``gather(desc, values, *where)``, differentiable
+    w.r.t. ``values`` only through ``scatter`` (not the rays or z: the resampled z is detached in the reference,
+    sampling.py:120).  No index and no extra work when nothing needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, gather, scatter, desc, values, *where):
+        ctx.set_materialize_grads(False)
+        ctx.n_inputs = 4 + len(where)
+        if not ctx.needs_input_grad[3]:
+            return gather(desc, values.detach(), *where)
+        raw, ctx.index = gather(desc, values.detach(), *where, want_index=True)
+        ctx.scatter, ctx.desc, ctx.values = scatter, desc, values
+        return raw
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        grads = [None] * ctx.n_inputs
+        if g_raw is not None and ctx.needs_input_grad[3]:
+            grads[3] = _values_grad(ctx, g_raw.contiguous().float())
+        return tuple(grads)
+
+
+def _values_grad(ctx, g_raw):
+    """The gradient of the node's ``values`` input: added straight into a contiguous fp32 ``.grad`` the parameter already owns
     (``ClipAdam`` keeps them as views of one flat buffer; autograd then gets None), else a fresh tensor."""
+    values = ctx.values
     grad = values.grad
     if values.is_leaf and grad is not None and grad.dtype == torch.float32 and grad.is_contiguous() and \
             grad.shape == values.shape and grad.device == values.device:
-        grid_field_bwd(ctx.desc, g_raw, ctx.index, out=grad, accumulate=True)
+        ctx.scatter(ctx.desc, g_raw, ctx.index, out=grad, accumulate=True)
         return None
-    return grid_field_bwd(ctx.desc, g_raw, ctx.index)
+    return ctx.scatter(ctx.desc, g_raw, ctx.index)
 
 
-class _GridFieldOnRays(torch.autograd.Function):
-    """The grid field at the samples ``o + d z`` of a ray batch as an autograd node: ``raw (N, S, C)``, differentiable w.r.t.
-    ``values`` only (not the rays or z: the resampled z is detached in the reference, sampling.py:120)."""
-
-    @staticmethod
-    def forward(ctx, desc, values, rays_o, rays_d, z_vals):
-        ctx.set_materialize_grads(False)
-        if not ctx.needs_input_grad[1]:
-            return grid_field_rays(desc, values.detach(), rays_o, rays_d, z_vals)
-        raw, ctx.index = grid_field_rays(desc, values.detach(), rays_o, rays_d, z_vals, want_index=True)
-        ctx.desc, ctx.values = desc, values
-        return raw
-
-    @staticmethod
-    def backward(ctx, g_raw):
-        if g_raw is None or not ctx.needs_input_grad[1]:
-            return (None,) * 5
-        return (None, _values_grad(ctx, ctx.values, g_raw.contiguous().float()), None, None, None)
-
-
-class _GridFieldOnPoints(torch.autograd.Function):
-    """The points twin of :class:`_GridFieldOnRays`: ``raw (M, C)`` at ``points (M, 3 | 4)``."""
-
-    @staticmethod
-    def forward(ctx, desc, values, points):
-        ctx.set_materialize_grads(False)
-        if not ctx.needs_input_grad[1]:
-            return grid_field_points(desc, values.detach(), points)
-        raw, ctx.index = grid_field_points(desc, values.detach(), points, want_index=True)
-        ctx.desc, ctx.values = desc, values
-        return raw
-
-    @staticmethod
-    def backward(ctx, g_raw):
-        if g_raw is None or not ctx.needs_input_grad[1]:
-            return (None,) * 3
-        return (None, _values_grad(ctx, ctx.values, g_raw.contiguous().float()), None)
+def _field(gather, scatter, desc, values, *where) -> torch.Tensor:
+    """``gather(desc, values, *where)``; through autograd when gradients are enabled and ``values`` requires one."""
+    if torch.is_grad_enabled() and values.requires_grad:
+        return _FieldGather.apply(gather, scatter, desc, values, *(w.detach() for w in where))
+    return gather(desc, values.detach(), *where)
 
 
 def field_on_rays(desc: GridDescriptor, values, rays_o, rays_d, z_vals) -> torch.Tensor:
     """``raw (N, S, C)``; through autograd when gradients are enabled and ``values`` requires one."""
-    if torch.is_grad_enabled() and values.requires_grad:
-        return _GridFieldOnRays.apply(desc, values, rays_o.detach(), rays_d.detach(), z_vals.detach())
-    return grid_field_rays(desc, values.detach(), rays_o, rays_d, z_vals)
+    return _field(grid_field_rays, grid_field_bwd, desc, values, rays_o, rays_d, z_vals)
 
 
 def field_on_points(desc: GridDescriptor, values, points) -> torch.Tensor:
     """``raw (M, C)``; through autograd when gradients are enabled and ``values`` requires one."""
-    if torch.is_grad_enabled() and values.requires_grad:
-        return _GridFieldOnPoints.apply(desc, values, points.detach())
-    return grid_field_points(desc, values.detach(), points)
+    return _field(grid_field_points, grid_field_bwd, desc, values, points)

@@ -883,7 +883,7 @@ GF_FWD_SHAPES = [(n, s, ch, mode, idx) for (n, s), ch in zip(((1, 1), (5, 51), (
                  for mode in ('rays', 'points3', 'points4') for idx in (0, 1)]
 
 
-@case('sunerf_grid_field_fwd', GF_FWD_SHAPES, 'grid_field.hip GF_THREADS 256: one sample per thread (1, 255, 257 and 804 samples)')
+@case('sunerf_grid_field_fwd', GF_FWD_SHAPES, 'grid_field.hip GF_THREADS 256 (grid_gather.h): one sample per thread (1, 255, 257 and 804 samples)')
 def grid_field_fwd(shape, device):
     n, s, ch, mode, want_index = shape
     c = Ctx(device)
@@ -918,7 +918,7 @@ def grid_field_fwd(shape, device):
 
 
 @case('sunerf_grid_field_bwd', [(total, ch, acc) for total, ch in ((63, 1), (64, 3), (65, 4), (129, 2), (804, 3)) for acc in (0, 1)],
-      'grid_field.hip GF_CHUNK 64: sorted positions per piece of a long segment; totals up to 129: every sample in the one cell of a '
+      'grid_gather.h GF_CHUNK 64: sorted positions per piece of a long segment; totals up to 129: every sample in the one cell of a '
       '2 x 2 x 2 grid (8 nodes: less than one block), so that the long-segment path and its `part` workspace run')
 def grid_field_bwd(shape, device):
     total, ch, acc = shape

@@ -28,7 +28,7 @@ import grid_field_reference as sref
 import test_gpu_dynamic_grid as dynamic
 import test_gpu_grid_field as static
 
-CHUNK = 64                                   # sorted positions per piece: GF_CHUNK, DG_CHUNK
+CHUNK = 64                                   # sorted positions per piece: GF_CHUNK of csrc/grid_gather.h
 EPS = 2.0 ** -24
 STATIC_SLACK, DYNAMIC_SLACK = 8, 10          # the bound per node: (n + slack) 2^-24 A
 FILL = static.FILL

@@ -206,6 +206,49 @@ def test_backward_of_long_segments(which, c):
     assert torch.equal(got.view(torch.int32), again.view(torch.int32))
 
 
+# ---- 3a. the backward at a frame time: the static backward, by bits ------------------------------------------------------------
+def _backward_at_every_frame_time(grid, tau, mode, values, g_raw, o, d, z):
+    """With every ray at ``tau[f]`` (dyadic: exact in fp32), frame ``f`` of the gradient is the static field's on the same grid,
+    rays and ``g_raw`` as int32 words, and every other frame is 0.  The temporal weights are (1, 0) in interval 0 at ``tau[0]``
+    and (0, 1) in interval ``f - 1`` after it; the ids are the static ones plus a constant with the sentinel still the largest,
+    so the stable sort gives the same permutation and pieces; ``((w0 w1) w2) * 1`` is the static weight, and the node thread
+    walks its one non-empty interval in the static order."""
+    from sunerf.model.grid_model import DynamicGridField, GridField
+    from sunerf_hip import dynamic_grid as dg, grid_field as gf
+    c = values.shape[-1]
+    field = DynamicGridField(grid, d_output=c, init=values, fill=FILL[:c], frame_times=tau, time_mode=mode).cuda()
+    frame = GridField(grid, d_output=c, init=values[0], fill=FILL[:c]).cuda()
+    o, d, z, g_raw = (x.cuda() for x in (o, d, z, g_raw))
+    _, index = gf.grid_field_rays(frame.descriptor(), frame.values.detach(), o, d, z, want_index=True)
+    want = gf.grid_field_bwd(frame.descriptor(), g_raw, index)                 # linear: the same whatever the frame holds
+    assert float(want.abs().max()) > 0
+    for f, tau_f in enumerate(tau):
+        t = torch.full((o.shape[0], 1), tau_f, dtype=_F32, device='cuda')
+        assert float(t[0, 0]) == tau_f
+        _, index = dg.dynamic_grid_rays(field.descriptor(), field.values.detach(), o, d, z, t, want_index=True)
+        got = dg.dynamic_grid_bwd(field.descriptor(), g_raw, index)
+        assert torch.equal(got[f].view(torch.int32), want.view(torch.int32)), (f, tau_f)
+        assert bool((got[[k for k in range(len(tau)) if k != f]] == 0).all()), (f, tau_f)
+
+
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('name,c,n_frames', CASES)
+def test_backward_at_a_frame_time_is_the_static_backward(name, c, n_frames, mode):
+    cs = case(name, c, n_frames, mode)
+    _backward_at_every_frame_time(cs['grid'], cs['tau'], mode, cs['values'], cs['g_raw'], cs['o'], cs['d'], cs['z'])
+
+
+@pytest.mark.parametrize('c', [1, 4])
+@pytest.mark.parametrize('n_frames', [2, 5])
+def test_backward_at_a_frame_time_is_the_static_backward_of_a_long_segment(n_frames, c):
+    """The input of :func:`test_backward_of_long_segments`: all 257 x 67 samples in the one cell, 270 pieces."""
+    grid = static.make_grid('cell')
+    o, d, z = static.make_rays('cell', seed=31, inside_only=True)
+    gen = torch.Generator().manual_seed(3)
+    values, g_raw = torch.randn(n_frames, 2, 2, 2, c, generator=gen), torch.randn(N_RAYS, N_SAMPLES, c, generator=gen)
+    _backward_at_every_frame_time(grid, FRAME_TIMES[n_frames], 'clamp', values, g_raw, o, d, z)
+
+
 # ---- 4. through the renderings ----------------------------------------------------------------------------------------------
 TAU3 = (0.0, 0.5, 1.0)
 sampling, _cube, _z = static.sampling, static._cube, static._z

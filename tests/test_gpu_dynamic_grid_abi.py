@@ -42,7 +42,7 @@ def _times(n):
 
 FWD_SHAPES = [(n, s, ch, mode, idx) for (n, s), ch in zip(((1, 1), (5, 51), (257, 1), (12, 67)), (1, 3, 4, 2))
               for mode in ('rays', 'points4') for idx in (0, 1)]
-FWD_TILES = 'dynamic_grid.hip DG_THREADS 256: one sample per thread (1, 255, 257 and 804 samples)'
+FWD_TILES = 'dynamic_grid.hip GF_THREADS 256 (grid_gather.h): one sample per thread (1, 255, 257 and 804 samples)'
 
 
 def dynamic_grid_fwd(shape, device):
@@ -81,7 +81,7 @@ def dynamic_grid_fwd(shape, device):
 
 
 BWD_SHAPES = [(total, ch, acc) for total, ch in ((63, 1), (64, 3), (65, 4), (129, 2), (804, 3)) for acc in (0, 1)]
-BWD_TILES = ('dynamic_grid.hip DG_CHUNK 64: sorted positions per piece of a long segment; totals up to 129: every sample in the one '
+BWD_TILES = ('grid_gather.h GF_CHUNK 64: sorted positions per piece of a long segment; totals up to 129: every sample in the one '
              'cell and the one interval of a 2 x 2 x 2 grid with two frames (16 nodes: less than one block), so that the '
              'long-segment path and its `part` workspace run; 804 samples on the open spherical grid with three frames')
 
