@@ -313,6 +313,18 @@ class Instrument:
         from .deconvolve import richardson_lucy
         return richardson_lucy(image, self, **kw)
 
+    def despike(self, image: torch.Tensor, **kw) -> dict:
+        """Cosmic-ray hits and hot pixels of an observed ``image`` [C, h, w] found against this instrument's noise model and
+        filled: :func:`sunerf_hip.despike.despike` with ``a``, ``b`` and ``floor`` of :func:`sunerf_hip.despike.despike_params`
+        (``mode``, ``window``, ``n_sigma``, ``grow_sigma``, ``min_valid``, ``iterations``, ``two_sided``, ``fill``, ``bad``)."""
+        from .despike import despike, despike_params
+        if not isinstance(image, torch.Tensor) or image.dim() not in (2, 3):
+            raise ValueError('Instrument.despike: image must be a tensor [C, h, w] or [h, w]')
+        p = despike_params(self, 1 if image.dim() == 2 else image.shape[0])
+        for k, name in enumerate(('a', 'b', 'floor')):
+            kw.setdefault(name, p[:, k])
+        return despike(image, **kw)
+
 
 def _correlate_bin(planes, taps, n_kernels, kh, kw, bin_factor, ay, ax, scale, boundary):
     from .ops import _ptr, _stream

@@ -301,6 +301,18 @@ _PSF_GRAD_SIGNATURES = {
 PSF_GRAD_SYMBOLS = tuple(_PSF_GRAD_SIGNATURES)
 PSF_GRAD_ABI_VERSION = 1
 
+# The despiking table (include/sunerf_hip_despike.h): cosmic-ray hits and hot pixels found by an iterated masked median and filled.
+# An eleventh table beside the ten above, which stay as they are and keep their versions.
+_DESPIKE_SIGNATURES = {
+    'sunerf_despike_abi_version': (ctypes.c_int, []),
+    'sunerf_despike_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
+    'sunerf_despike': (ctypes.c_int, [c_f32p, c_void, c_void] + [ctypes.c_int] * 6 + [ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                      ctypes.c_int, c_f32p, c_void, c_void, c_void, c_void]),
+}
+
+DESPIKE_SYMBOLS = tuple(_DESPIKE_SIGNATURES)
+DESPIKE_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -375,6 +387,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_psf_grad_abi_version() != PSF_GRAD_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so PSF-gradient ABI version mismatch')
+        for name, (res, args) in _DESPIKE_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_despike_abi_version() != DESPIKE_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so despiking ABI version mismatch')
         _lib = lib
     return _lib
 

@@ -44,6 +44,12 @@ rule -- added on the ``bin`` times finer frame ``Instrument.latent_grid`` descri
 deconvolved pixel no longer follows the detector's noise model, so ``--likelihood`` does not apply to this run).  Its report
 carries the updates applied and the deviance per valid pixel of every view and channel.
 
+``--cosmic-rays RATE,AMP [--despike median|nan]`` (with ``--instrument``): a further ray run on the same observed training views
+with particle hits (``sunerf_hip.despike.add_cosmic_rays``: tracks of 1 to 4 pixels on ``RATE`` of the pixels, ``AMP`` times the
+pixel's sigma each, seeded by the view).  Without ``--despike`` the views are trained on as they are; with it they go through
+``Instrument.despike`` first -- ``median`` inpaints the flagged pixels, ``nan`` drops their rays from the pool.  Its
+report (``cosmic_rays``) carries the pixels hit, flagged and rightly flagged of every view.
+
 ``--fit-psf FWHM0`` (with ``--through-instrument``; a Gaussian ``--instrument``): the PSF as a trainable part of the model
 (DESIGN.md 8t).  Three patch runs on the same observed views, one seed each: the right PSF (the ``through_instrument`` run above),
 a wrong PSF held fixed (a Gaussian of ``FWHM0`` in place of the instrument's own width), and the wrong PSF fitted -- a
@@ -54,6 +60,7 @@ held-out scores of the two runs beside those of the right PSF.
     python tools/closed_loop.py [--module dt|emission] [--views 8] [--size 64] [--steps 300] [--batch 2048] [--d-filter 256] [--baseline]
                                 [--instrument SPEC [--through-instrument] [--patch 16] [--patches-per-batch N] [--through-steps K]]
                                 [--likelihood observed|model] [--lambda-ssim L [--ssim-window 7]] [--deconvolve N|auto] [--skip-clean]
+                                [--cosmic-rays RATE,AMP [--despike median|nan]]
                                 [--fit-psf FWHM0 [--psf-rate 20]]
 """
 import argparse
@@ -103,15 +110,28 @@ def baseline_scores(module, obs):
     return {'baseline.loss': loss.item(), 'baseline.ssim': scores['ssim'][0].item(), 'baseline.psnr': (-10. * torch.log10(loss)).item()}
 
 
-def observed_view(instrument, render, grid, index, n_views, deconvolve=None):
+def observed_view(instrument, render, grid, index, n_views, deconvolve=None, cosmic=None):
     """``(planes, grid of the planes)``: ``render(grid)`` -> planes (C, H, W) of view ``index`` on ``grid``; a training view of an
     instrument run is rendered ``bin`` times finer over the same field of view and observed, the held-out view and a clean run
-    are not.  ``deconvolve`` (``iterations``, ``stop``, ``log``): the observed view is deconvolved and lies on the latent grid."""
+    are not.  ``deconvolve`` (``iterations``, ``stop``, ``log``): the observed view is deconvolved and lies on the latent grid.
+    ``cosmic`` (``rate``, ``amplitude``, ``despike``, ``log``): the observed view takes particle hits of ``amplitude`` sigma on
+    ``rate`` of its pixels and is, with ``despike`` 'median' or 'nan', cleaned by ``Instrument.despike`` before it is used."""
     if instrument is None or index == hold_out_index(n_views):
         return render(grid), grid
     h, w = grid['shape']
     fine = resampled_grid(grid, (h * instrument.bin, w * instrument.bin))
     image = instrument.observe(render(fine).contiguous(), seed=index)['image']
+    if cosmic is not None:
+        from sunerf_hip.despike import add_cosmic_rays
+        image, truth = add_cosmic_rays(image, cosmic['rate'], cosmic['amplitude'], sigma=instrument.errors(image, channel_axis=0), seed=index)
+        entry = {'view': index, 'hit': int(truth.sum())}
+        if cosmic['despike'] is not None:
+            out = instrument.despike(image, fill=cosmic['despike'])
+            flagged = (out['mask'] & 1) != 0
+            entry.update(flagged=int(flagged.sum()), hits_flagged=int((flagged & truth).sum()), passes=out['passes'].tolist(),
+                         converged=out['converged'].tolist(), unfilled=out['n_unfilled'].tolist())
+            image = out['image']
+        cosmic['log'].append(entry)
     if deconvolve is None:
         return image, grid
     out = instrument.deconvolve(image, iterations=deconvolve['iterations'], stop=deconvolve['stop'])
@@ -120,7 +140,7 @@ def observed_view(instrument, render, grid, index, n_views, deconvolve=None):
     return out['image'], instrument.latent_grid(grid)
 
 
-def density_temperature_problem(args, grid, poses, instrument=None, mode=None, deconvolve=None, psf_models=None):
+def density_temperature_problem(args, grid, poses, instrument=None, mode=None, deconvolve=None, psf_models=None, cosmic=None):
     fx = np.load(os.path.join(R, 'tests', 'golden', 'g9_simple_star.npz'))
     table = (fx['aia_logte'], fx['aia_tresp'])
     cfg = dict(sampling_config={'type': 'stratified', 'n_samples': 64, 'perturb': True},
@@ -146,7 +166,7 @@ def density_temperature_problem(args, grid, poses, instrument=None, mode=None, d
         if instrument is None:
             obs.add_rendered_view(truth, lat, lon, 0.0, wl=np.array(WL), scale=scale)
             continue
-        planes, view_grid = observed_view(instrument, render_of(lat, lon), grid, index, len(poses), deconvolve)
+        planes, view_grid = observed_view(instrument, render_of(lat, lon), grid, index, len(poses), deconvolve, cosmic)
         obs.add_view(planes, lat, lon, time=0.0, grid=view_grid, wavelengths=np.array(WL))
     module = DensityTemperatureSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={}, model=NeRF_DT,
                                             pixel_intensity_factor=1e10, response_table=table,
@@ -159,7 +179,7 @@ def density_temperature_problem(args, grid, poses, instrument=None, mode=None, d
     return obs, module, render_of, np.array(WL)
 
 
-def emission_problem(args, grid, poses, instrument=None, mode=None, deconvolve=None, psf_models=None):
+def emission_problem(args, grid, poses, instrument=None, mode=None, deconvolve=None, psf_models=None, cosmic=None):
     from sunerf.evaluation.loader import linear_plate_scale_axes
     from sunerf_hip.rays import grid_rays, pose_spherical
     obs = ObservationSet(Rs_per_ds=1.0, seconds_per_dt=1.0, device='cuda')
@@ -173,7 +193,7 @@ def emission_problem(args, grid, poses, instrument=None, mode=None, deconvolve=N
             return image.reshape(1, *g['shape'])
         return render
     for index, (lat, lon) in enumerate(poses):
-        planes, view_grid = observed_view(instrument, render_of(lat, lon), grid, index, len(poses), deconvolve)
+        planes, view_grid = observed_view(instrument, render_of(lat, lon), grid, index, len(poses), deconvolve, cosmic)
         obs.add_view(planes[0], lat, lon, time=0.0, grid=view_grid)
     module = EmissionSuNeRFModule(Rs_per_ds=1.0, seconds_per_dt=1.0, image_scaling_config={'vmax': 1, 'a': 0.005},
                                   sampling_config={'type': 'stratified', 'n_samples': 64, 'perturb': True},
@@ -220,6 +240,9 @@ def main():
                     help='a further run on Richardson-Lucy deconvolved views: N updates, or auto: the discrepancy rule')
     ap.add_argument('--fit-psf', type=float, metavar='FWHM0', default=None,
                     help='two further patch runs from a Gaussian PSF of this width: held fixed, and fitted beside the network')
+    ap.add_argument('--cosmic-rays', metavar='RATE,AMP', default=None,
+                    help='a further ray run on observed views with particle hits: RATE of the pixels, AMP sigma each')
+    ap.add_argument('--despike', choices=('median', 'nan'), default=None, help='with --cosmic-rays: Instrument.despike the views first')
     ap.add_argument('--psf-rate', type=float, default=20.0, help='rate of the TrainablePSF: its log_fwhm moves at rate x the learning rate')
     args = ap.parse_args()
     if args.fit_psf is not None and not args.through_instrument:
@@ -232,6 +255,19 @@ def main():
         ap.error('--likelihood needs --instrument SPEC')
     if args.through_instrument and args.instrument is None:
         ap.error('--through-instrument needs --instrument SPEC')
+    cosmic = None
+    if args.cosmic_rays is not None:
+        if args.instrument is None:
+            ap.error('--cosmic-rays needs --instrument SPEC')
+        try:
+            rate, amplitude = (float(v) for v in args.cosmic_rays.split(','))
+        except ValueError:
+            ap.error('--cosmic-rays takes RATE,AMP: the fraction of pixels hit and the amplitude in sigma')
+        if not 0 <= rate <= 1 or not amplitude > 0:
+            ap.error('--cosmic-rays takes a RATE in [0, 1] and an AMP above 0')
+        cosmic = {'rate': rate, 'amplitude': amplitude, 'despike': args.despike, 'log': []}
+    elif args.despike is not None:
+        ap.error('--despike needs --cosmic-rays RATE,AMP')
     deconvolve = None
     if args.deconvolve is not None:
         if args.instrument is None:
@@ -272,6 +308,15 @@ def main():
                   f"bin times the resolution {dec['after_fine']['validation.psnr']:.2f} dB against "
                   f"{seen['after_fine']['validation.psnr']:.2f} dB of ray training on the observed views", file=sys.stderr)
             report['deconvolved'] = {'deconvolve': args.deconvolve, 'views': deconvolve['log'], **{k: dec[k] for k in keys if k in dec}}
+        if cosmic is not None:
+            hit = run(args, grid, poses, Instrument.from_spec(args.instrument), cosmic=cosmic)
+            n_hit, n_found = sum(v['hit'] for v in cosmic['log']), sum(v.get('hits_flagged', 0) for v in cosmic['log'])
+            cleaned = 'as they are' if args.despike is None else f"despiked (fill='{args.despike}', {n_found} of {n_hit} hit pixels flagged)"
+            print(f"views with particle hits ({args.cosmic_rays}: {n_hit} pixels hit), {cleaned}: PSNR {hit['after']['validation.psnr']:.2f} dB, "
+                  f"SSIM {hit['after']['validation.ssim']:.4f} against {seen['after']['validation.psnr']:.2f} dB, "
+                  f"{seen['after']['validation.ssim']:.4f} without hits", file=sys.stderr)
+            report['cosmic_rays'] = {'cosmic_rays': args.cosmic_rays, 'despike': args.despike, 'views': cosmic['log'],
+                                     **{k: hit[k] for k in keys if k in hit}}
     print(json.dumps({'closed_loop': report}))
 
 
@@ -312,13 +357,13 @@ def _recording_fwhm(batches, psf_model, steps, record):
     record.append((done, psf_model.fwhm[0].clone()))
 
 
-def run(args, grid, poses, instrument, through=False, deconvolve=None, model_instrument=None, psf_model=None):
+def run(args, grid, poses, instrument, through=False, deconvolve=None, model_instrument=None, psf_model=None, cosmic=None):
     """``instrument`` observes the views; ``model_instrument`` (default: the same) is what a patch run sees its renders through;
-    ``psf_model``: the TrainablePSF of a FittedInstrument, trained beside the network."""
+    ``psf_model``: the TrainablePSF of a FittedInstrument, trained beside the network; ``cosmic``: see ``observed_view``."""
     torch.manual_seed(0)
     problem = density_temperature_problem if args.module == 'dt' else emission_problem
     mode = args.likelihood if instrument is not None and deconvolve is None else None
-    obs, module, render_of, wavelengths = problem(args, grid, poses, instrument, mode, deconvolve, psf_models=psf_model)
+    obs, module, render_of, wavelengths = problem(args, grid, poses, instrument, mode, deconvolve, psf_models=psf_model, cosmic=cosmic)
     obs.hold_out('reference')
     steps = args.steps
     if through:
