@@ -1,7 +1,7 @@
 // Line-of-sight differential emission measure of the density / temperature model: DEM(log T) per ray on a caller-given
 // log T grid, total emission measure, emission-measure-weighted log T and column density.
 //
-// Restates the forward of the DT integral (dt.hip forward_sweep; density_temperature.py:237-265) with the response folded
+// Restates the forward of the DT integral (dt_sweep.h forward_sweep; density_temperature.py:237-265) with the response folded
 // out: with rho = exp(relu(raw0 + base_rho)), logT = relu(raw1 + base_T) and, for the quadrature points j = 0..S-2,
 //   q_j = trapezoid weight of z_j on the grid z_0..z_{S-2}
 //   t_j = exp(-A_{j+1}),  A = cumulative_trapezoid(rho relu(log_abs), z)            (the render's own index shift, :261-263)
@@ -19,6 +19,7 @@
 // lane adds a triple's halves when it owns node i / i + 1: no atomics, no LDS per sample, one fixed summation order, so
 // reruns and any position of a ray in a batch give the same bits.  The nodes (K <= 128) sit in LDS for the binary search.
 #include "sunerf_common.h"
+#include "ray_scan.h"
 #include "../../include/sunerf_hip.h"
 
 namespace {
@@ -43,20 +44,6 @@ struct DemArgs {
   float* logt_mean;       // (N,) or null
   float* column;          // (N,) or null
 };
-
-__device__ __forceinline__ float scan_up32(float v, int n) {      // inclusive prefix sum over the 32 lanes of a ray
-#pragma unroll
-  for (int d = 1; d < 32; d <<= 1) {
-    const float o = __shfl_up(v, d, 32);
-    if (n >= d) v += o;
-  }
-  return v;
-}
-__device__ __forceinline__ float sum32(float v) {
-#pragma unroll
-  for (int d = 16; d >= 1; d >>= 1) v += __shfl_xor(v, d, 32);
-  return v;
-}
 
 __global__ __launch_bounds__(DEM_THREADS) void dem_integral_kernel(DemArgs a) {
   __shared__ float nodes[DEM_MAX_NODES];

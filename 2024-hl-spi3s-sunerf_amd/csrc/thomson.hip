@@ -30,6 +30,7 @@
 // per-ray sums over the ray's own lanes (butterfly), no float atomics: reruns are bit-identical.  The backward also writes
 // the bit pattern of max |g_raw| (one integer atomic max per workgroup) that the MLP backward takes as its gradient scale.
 #include "sunerf_common.h"
+#include "ray_scan.h"
 #include "../../include/sunerf_hip.h"
 
 namespace {
@@ -70,12 +71,6 @@ struct ThomsonArgs {
   float* g_raw;              // (N,S,C)
   unsigned* g_absmax_bits;   // (1,) or null
 };
-
-__device__ __forceinline__ float sum32(float v) {
-#pragma unroll
-  for (int d = 16; d >= 1; d >>= 1) v += __shfl_xor(v, d, 32);
-  return v;
-}
 
 // lane-uniform quantities of one ray
 struct Ray {

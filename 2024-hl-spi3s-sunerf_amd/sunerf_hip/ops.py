@@ -983,29 +983,64 @@ def mlp_input_backward(packed: PackedMLP, g_raw, query, grad_weights=None, grad_
 AIA_WAVELENGTHS = (94, 131, 171, 193, 211, 304, 335)
 
 
-def dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_resp, log_abs, vol_c, base_log_density,
-                    base_log_temperature, pixel_intensity_factor, reg_radius, want_epilogues=False):
-    """DT radiative-transfer integral on the raw MLP output (density_temperature.py:192-274)."""
+def _dt_fwd(entry, table, m, raw, z_vals, rays_o, rays_d, wavelengths, log_abs, vol_c, base_log_density, base_log_temperature,
+            pixel_intensity_factor, reg_radius, want_epilogues):
+    """Forward of the DT integral through ``entry``.  ``table(dev)``: the entry point's table arguments, checked (the AIA pair, or
+    those of a response set); ``m``: the channels of ``log_abs``."""
     n, s = z_vals.shape
     dev = z_vals.device
     w = wavelengths.shape[1]
     raw = _dev(raw, 'raw', (n, s, 2)); z_vals = _dev(z_vals, 'z_vals', (n, s))
     rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3))
     wavelengths = _dev(wavelengths.to(torch.float32), 'wavelengths', (n, w))
-    table_logt = _dev(table_logt, 'table_logt', (7, 101)); table_resp = _dev(table_resp, 'table_resp', (7, 101))
-    log_abs = _dev(log_abs.detach(), 'log_abs', (7,)); vol_c = _dev(vol_c.detach().reshape(1), 'vol_c', (1,))
+    table = table(dev)
+    log_abs = _dev(log_abs.detach(), 'log_abs', (m,)); vol_c = _dev(vol_c.detach().reshape(1), 'vol_c', (1,))
     f32 = dict(dtype=torch.float32, device=dev)
     out = {'image': torch.empty(n, w, **f32), 'weights': torch.empty(n, s, **f32), 'reg_q': torch.empty(n, s, **f32)}
     hm = am = reg = None
     if want_epilogues:
         hm, am, reg = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, s, **f32)
-    _l.call(dev, 'sunerf_dt_integral_fwd', _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(wavelengths), w,
-            _ptr(table_logt), _ptr(table_resp), _ptr(log_abs), _ptr(vol_c), float(base_log_density),
-            float(base_log_temperature), float(pixel_intensity_factor), float(reg_radius), n, s, _ptr(out['image']),
-            _ptr(out['weights']), _ptr(out['reg_q']), _ptr(hm), _ptr(am), _ptr(reg), _stream(dev))
+    _l.call(dev, entry, _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(wavelengths), w, *table, _ptr(log_abs),
+            _ptr(vol_c), float(base_log_density), float(base_log_temperature), float(pixel_intensity_factor), float(reg_radius),
+            n, s, _ptr(out['image']), _ptr(out['weights']), _ptr(out['reg_q']), _ptr(hm), _ptr(am), _ptr(reg), _stream(dev))
     if want_epilogues:
         out.update(height_map=hm, absorption_map=am, regularization=reg)
     return out
+
+
+def _dt_bwd(entry, table, m, raw, z_vals, rays_o, rays_d, wavelengths, log_abs, vol_c, base_log_density, base_log_temperature,
+            pixel_intensity_factor, reg_radius, g_image, per_sample, fits=None):
+    """Launches DT integral backward ``entry`` with the (N,S) output gradients ``per_sample`` ((name, tensor or None) pairs,
+    in the entry point's order) -> (g_raw, g_log_abs (m,), g_vol_c, absmax).  ``table(dev)`` / ``m``: as :func:`_dt_fwd`;
+    ``fits(n, s, w)``: raises for a shape the entry point would refuse."""
+    n, s = z_vals.shape
+    dev = z_vals.device
+    w = wavelengths.shape[1]
+    raw = _dev(raw, 'raw', (n, s, 2)); z_vals = _dev(z_vals, 'z_vals', (n, s))
+    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3))
+    wavelengths = _dev(wavelengths.to(torch.float32), 'wavelengths', (n, w))
+    log_abs = _dev(log_abs.detach(), 'log_abs', (m,)); vol_c = _dev(vol_c.detach().reshape(1), 'vol_c', (1,))
+    g_image = _dev(g_image, 'g_image', (n, w))
+    per_sample = [None if g is None else _dev(g, name, (n, s)) for name, g in per_sample]
+    if fits is not None:
+        fits(n, s, w)
+    f32 = dict(dtype=torch.float32, device=dev)
+    g_raw = torch.empty(n, s, 2, **f32)
+    small = torch.empty(m + 2, **f32)
+    g_la, g_vc, absmax = small[:m], small[m:m + 1], small[m + 1:m + 2].view(torch.int32)
+    _l.call(dev, entry, _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(wavelengths), w, *table(dev), _ptr(log_abs),
+            _ptr(vol_c), float(base_log_density), float(base_log_temperature), float(pixel_intensity_factor), float(reg_radius),
+            n, s, _ptr(g_image), *[_ptr(g) for g in per_sample], _ptr(g_raw), _ptr(g_la), _ptr(g_vc), _ptr(absmax), _stream(dev))
+    return g_raw, g_la, g_vc, absmax
+
+
+def dt_integral_fwd(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_resp, log_abs, vol_c, base_log_density,
+                    base_log_temperature, pixel_intensity_factor, reg_radius, want_epilogues=False):
+    """DT radiative-transfer integral on the raw MLP output (density_temperature.py:192-274)."""
+    def table(dev):
+        return _ptr(_dev(table_logt, 'table_logt', (7, 101))), _ptr(_dev(table_resp, 'table_resp', (7, 101)))
+    return _dt_fwd('sunerf_dt_integral_fwd', table, 7, raw, z_vals, rays_o, rays_d, wavelengths, log_abs, vol_c, base_log_density,
+                   base_log_temperature, pixel_intensity_factor, reg_radius, want_epilogues)
 
 
 def simple_star_field(rays_o, rays_d, z_vals, rho_0: float, h0: float, T0: float, Rs: float, t_photosphere: float):
@@ -1022,24 +1057,8 @@ def _dt_integral_bwd(entry, raw, z_vals, rays_o, rays_d, wavelengths, table_logt
                      base_log_density, base_log_temperature, pixel_intensity_factor, reg_radius, g_image, per_sample):
     """Launches DT integral backward ``entry`` with the (N,S) output gradients ``per_sample`` ((name, tensor or None) pairs,
     in the entry point's order) -> (g_raw, g_log_abs, g_vol_c, absmax)."""
-    n, s = z_vals.shape
-    dev = z_vals.device
-    w = wavelengths.shape[1]
-    raw = _dev(raw, 'raw', (n, s, 2)); z_vals = _dev(z_vals, 'z_vals', (n, s))
-    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3))
-    wavelengths = _dev(wavelengths.to(torch.float32), 'wavelengths', (n, w))
-    log_abs = _dev(log_abs.detach(), 'log_abs', (7,)); vol_c = _dev(vol_c.detach().reshape(1), 'vol_c', (1,))
-    g_image = _dev(g_image, 'g_image', (n, w))
-    per_sample = [None if g is None else _dev(g, name, (n, s)) for name, g in per_sample]
-    f32 = dict(dtype=torch.float32, device=dev)
-    g_raw = torch.empty(n, s, 2, **f32)
-    small = torch.empty(9, **f32)
-    g_la, g_vc, absmax = small[:7], small[7:8], small[8:9].view(torch.int32)
-    _l.call(dev, entry, _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(wavelengths), w,
-            _ptr(table_logt), _ptr(table_resp), _ptr(log_abs), _ptr(vol_c), float(base_log_density),
-            float(base_log_temperature), float(pixel_intensity_factor), float(reg_radius), n, s, _ptr(g_image),
-            *[_ptr(g) for g in per_sample], _ptr(g_raw), _ptr(g_la), _ptr(g_vc), _ptr(absmax), _stream(dev))
-    return g_raw, g_la, g_vc, absmax
+    return _dt_bwd(entry, lambda dev: (_ptr(table_logt), _ptr(table_resp)), 7, raw, z_vals, rays_o, rays_d, wavelengths, log_abs,
+                   vol_c, base_log_density, base_log_temperature, pixel_intensity_factor, reg_radius, g_image, per_sample)
 
 
 def dt_integral_bwd(raw, z_vals, rays_o, rays_d, wavelengths, table_logt, table_resp, log_abs, vol_c, base_log_density,
@@ -1077,53 +1096,21 @@ def dt_response_fwd(raw, z_vals, rays_o, rays_d, wavelengths, response_set, log_
                     base_log_temperature, pixel_intensity_factor, reg_radius, want_epilogues=False):
     """:func:`dt_integral_fwd` against ``response_set`` (a ``sunerf_hip.response.ResponseSet``): ``wavelengths`` (N, W <= 8) holds
     the set's channel codes, ``log_abs`` is (M,) in set order."""
-    n, s = z_vals.shape
-    dev = z_vals.device
-    w = wavelengths.shape[1]
-    m = response_set.n_channels
-    raw = _dev(raw, 'raw', (n, s, 2)); z_vals = _dev(z_vals, 'z_vals', (n, s))
-    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3))
-    wavelengths = _dev(wavelengths.to(torch.float32), 'wavelengths', (n, w))
-    log_abs = _dev(log_abs.detach(), 'log_abs', (m,)); vol_c = _dev(vol_c.detach().reshape(1), 'vol_c', (1,))
-    f32 = dict(dtype=torch.float32, device=dev)
-    out = {'image': torch.empty(n, w, **f32), 'weights': torch.empty(n, s, **f32), 'reg_q': torch.empty(n, s, **f32)}
-    hm = am = reg = None
-    if want_epilogues:
-        hm, am, reg = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, s, **f32)
-    _l.call(dev, 'sunerf_dt_response_fwd', _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(wavelengths), w,
-            *_response_set_args(response_set, dev), _ptr(log_abs), _ptr(vol_c), float(base_log_density),
-            float(base_log_temperature), float(pixel_intensity_factor), float(reg_radius), n, s, _ptr(out['image']),
-            _ptr(out['weights']), _ptr(out['reg_q']), _ptr(hm), _ptr(am), _ptr(reg), _stream(dev))
-    if want_epilogues:
-        out.update(height_map=hm, absorption_map=am, regularization=reg)
-    return out
+    return _dt_fwd('sunerf_dt_response_fwd', lambda dev: _response_set_args(response_set, dev), response_set.n_channels, raw, z_vals,
+                   rays_o, rays_d, wavelengths, log_abs, vol_c, base_log_density, base_log_temperature, pixel_intensity_factor,
+                   reg_radius, want_epilogues)
 
 
 def _dt_response_bwd(entry, raw, z_vals, rays_o, rays_d, wavelengths, response_set, log_abs, vol_c, base_log_density,
                      base_log_temperature, pixel_intensity_factor, reg_radius, g_image, per_sample):
     """:func:`_dt_integral_bwd` for the response-set entry points -> (g_raw, g_log_abs (M,), g_vol_c, absmax)."""
-    n, s = z_vals.shape
-    dev = z_vals.device
-    w = wavelengths.shape[1]
-    m = response_set.n_channels
-    raw = _dev(raw, 'raw', (n, s, 2)); z_vals = _dev(z_vals, 'z_vals', (n, s))
-    rays_o = _dev(rays_o, 'rays_o', (n, 3)); rays_d = _dev(rays_d, 'rays_d', (n, 3))
-    wavelengths = _dev(wavelengths.to(torch.float32), 'wavelengths', (n, w))
-    log_abs = _dev(log_abs.detach(), 'log_abs', (m,)); vol_c = _dev(vol_c.detach().reshape(1), 'vol_c', (1,))
-    g_image = _dev(g_image, 'g_image', (n, w))
-    per_sample = [None if g is None else _dev(g, name, (n, s)) for name, g in per_sample]
-    if n > 0 and dt_response_bwd_lds_bytes(s, w, response_set.n_nodes) > 160 * 1024:
-        raise ValueError(f'{entry}: {s} samples x {w} columns with {response_set.n_nodes} response nodes need more than the 160 KiB '
-                         f'of LDS of a compute unit (at most {response_set.max_samples(w)} samples at this width)')
-    f32 = dict(dtype=torch.float32, device=dev)
-    g_raw = torch.empty(n, s, 2, **f32)
-    small = torch.empty(m + 2, **f32)
-    g_la, g_vc, absmax = small[:m], small[m:m + 1], small[m + 1:m + 2].view(torch.int32)
-    _l.call(dev, entry, _ptr(raw), _ptr(z_vals), _ptr(rays_o), _ptr(rays_d), _ptr(wavelengths), w,
-            *_response_set_args(response_set, dev), _ptr(log_abs), _ptr(vol_c), float(base_log_density),
-            float(base_log_temperature), float(pixel_intensity_factor), float(reg_radius), n, s, _ptr(g_image),
-            *[_ptr(g) for g in per_sample], _ptr(g_raw), _ptr(g_la), _ptr(g_vc), _ptr(absmax), _stream(dev))
-    return g_raw, g_la, g_vc, absmax
+    def fits(n, s, w):
+        if n > 0 and dt_response_bwd_lds_bytes(s, w, response_set.n_nodes) > 160 * 1024:
+            raise ValueError(f'{entry}: {s} samples x {w} columns with {response_set.n_nodes} response nodes need more than the 160 KiB '
+                             f'of LDS of a compute unit (at most {response_set.max_samples(w)} samples at this width)')
+    return _dt_bwd(entry, lambda dev: _response_set_args(response_set, dev), response_set.n_channels, raw, z_vals, rays_o, rays_d,
+                   wavelengths, log_abs, vol_c, base_log_density, base_log_temperature, pixel_intensity_factor, reg_radius, g_image,
+                   per_sample, fits)
 
 
 def dt_response_bwd(raw, z_vals, rays_o, rays_d, wavelengths, response_set, log_abs, vol_c, base_log_density,

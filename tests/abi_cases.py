@@ -303,8 +303,9 @@ def emission_integral_bwd(shape, device):
                 empty_effect=lambda: {'g_absmax': torch.zeros(1, dtype=I32)})          # header: an empty batch clears the word
 
 
-# dt.hip:341-352: every ray adds its g_log_abs / g_vol_c terms to the workgroup's LDS sums with atomicAdd, and every workgroup
-# adds those to the outputs with atomicAdd: from three terms on the order of the float adds is free (two terms commute)
+# dt_sweep.h, the end of dt_bwd_kernel ("parameter gradients" and the final atomics): every ray adds its g_log_abs / g_vol_c
+# terms to the workgroup's LDS sums with atomicAdd, and every workgroup adds those to the outputs with atomicAdd: from three
+# terms on the order of the float adds is free (two terms commute)
 DT_ORDERED_RAYS = 2
 DT_SHAPES = [(n, s, w, epi) for n, s in RAY_SHAPES_S3 for w, epi in ((1, 0), (7, 1))]
 
@@ -324,7 +325,7 @@ def _dt_wrapper_args(b, e, n, s, w):
             b['lt'].t.view(7, 101), b['resp'].t.view(7, 101), b['la'].t, b['vc'].t, 10.0, 5.0, float(e['pixel']), 1.25)
 
 
-@case('sunerf_dt_integral_fwd', DT_SHAPES, 'dt.hip DT_THREADS 256: one wave per ray, 64 samples per pass')
+@case('sunerf_dt_integral_fwd', DT_SHAPES, 'dt_sweep.h DT_THREADS 256: one wave per ray, 64 samples per pass')
 def dt_integral_fwd(shape, device):
     n, s, w, epi = shape
     c = Ctx(device)
@@ -372,12 +373,12 @@ def _dt_bwd(name, shape, device, full):
                 empty_effect=effect, reproducible=n <= DT_ORDERED_RAYS, tolerance=tolerance)
 
 
-@case('sunerf_dt_integral_bwd', DT_SHAPES, 'dt.hip DT_THREADS 256: one wave per ray, 64 samples per pass')
+@case('sunerf_dt_integral_bwd', DT_SHAPES, 'dt_sweep.h DT_THREADS 256: one wave per ray, 64 samples per pass')
 def dt_integral_bwd(shape, device):
     return _dt_bwd('sunerf_dt_integral_bwd', shape, device, False)
 
 
-@case('sunerf_dt_integral_bwd_full', DT_SHAPES, 'dt.hip DT_THREADS 256: one wave per ray, 64 samples per pass')
+@case('sunerf_dt_integral_bwd_full', DT_SHAPES, 'dt_sweep.h DT_THREADS 256: one wave per ray, 64 samples per pass')
 def dt_integral_bwd_full(shape, device):
     return _dt_bwd('sunerf_dt_integral_bwd_full', shape, device, True)
 
