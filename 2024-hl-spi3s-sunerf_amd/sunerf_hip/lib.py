@@ -313,6 +313,17 @@ _DESPIKE_SIGNATURES = {
 DESPIKE_SYMBOLS = tuple(_DESPIKE_SIGNATURES)
 DESPIKE_ABI_VERSION = 1
 
+# The co-alignment table (include/sunerf_hip_coalign.h): the six sums of a masked zero-mean normalised cross-correlation for every
+# integer shift of a window.  A twelfth table beside the eleven above, which stay as they are and keep their versions.
+_COALIGN_SIGNATURES = {
+    'sunerf_coalign_abi_version': (ctypes.c_int, []),
+    'sunerf_coalign_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 5),
+    'sunerf_coalign_shift_sums': (ctypes.c_int, [c_f32p, c_f32p, c_void, c_void] + [ctypes.c_int] * 5 + [c_void, c_void, c_void]),
+}
+
+COALIGN_SYMBOLS = tuple(_COALIGN_SIGNATURES)
+COALIGN_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -393,6 +404,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_despike_abi_version() != DESPIKE_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so despiking ABI version mismatch')
+        for name, (res, args) in _COALIGN_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_coalign_abi_version() != COALIGN_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so co-alignment ABI version mismatch')
         _lib = lib
     return _lib
 

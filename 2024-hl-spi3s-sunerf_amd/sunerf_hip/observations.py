@@ -445,6 +445,116 @@ class ObservationSet:
             pred, target = normalize(pred), normalize(target)
         return image_metrics(pred.contiguous(), target.contiguous(), data_range)
 
+    # ---------------------------------------------------------------- co-alignment
+    def _pixel_sizes(self, view: View):
+        """Refuses a view whose pointing cannot be moved by a shift of its axes, as ``patch_pool`` refuses; for a view without
+        a plate-scale dict the pixel sizes ``(delta_x, delta_y)`` of its uniform axes (read on the host), else None."""
+        from .patch import UNIFORM_TOLERANCE
+        if view.per_pixel:
+            raise ValueError(f'{view.name}: co-alignment needs a view with 1-d pixel axes (per-pixel angles are not supported)')
+        if view.grid is not None:
+            return None
+        deltas = []
+        for axis in (view.tx, view.ty):
+            a = axis.detach().cpu().numpy()
+            if a.shape[0] < 2:
+                raise ValueError(f'{view.name}: an axis of one pixel has no pixel size')
+            delta = (a[-1] - a[0]) / (a.shape[0] - 1)
+            if delta == 0 or np.abs(a - (a[0] + np.arange(a.shape[0]) * delta)).max() > UNIFORM_TOLERANCE * abs(delta):
+                raise ValueError(f'{view.name}: co-alignment needs a uniform pixel axis')
+            deltas.append(float(delta))
+        return tuple(deltas)
+
+    def _move_pointing(self, view: View, dy: float, dx: float, deltas) -> None:
+        from sunerf.evaluation.loader import linear_plate_scale_axes
+        from .coalign import shifted_grid
+        if view.grid is not None:
+            view.grid = shifted_grid(view.grid, dy, dx)
+            view.tx, view.ty = linear_plate_scale_axes(view.grid, None, self.device)
+        else:          # new[c + dx] = old[c] on a uniform axis: every angle moves by -dx pixel sizes
+            view.tx = (view.tx - dx * deltas[0]).contiguous()
+            view.ty = (view.ty - dy * deltas[1]).contiguous()
+        self._tables = {}
+
+    def coalign_view(self, index: int, reference='baseline', max_shift=8, min_overlap: float = 0.5, measure: str = 'zncc',
+                     combine: str = 'shared', apply: bool = True, **baseline_kw) -> dict:
+        """Finds the pointing offset of view ``index`` against a prediction of it and, with ``apply``, moves the view's pixel
+        grid by it (``sunerf_hip.coalign``).  The image itself is never resampled.
+
+        The view's image (the mean over its ``downscale`` blocks, as :meth:`baseline_metrics` forms it) is correlated with
+        ``reference`` over the shifts ``|dy|, |dx| <= max_shift``: ``'baseline'``, :meth:`baseline_view` of the view on its
+        present channels -- without that view; its off-disk NaN takes no part (``baseline_kw`` go to it) -- or a tensor
+        ``[C_present, H, W]`` on the view's grid, e.g. a model's render of that view.  ``min_overlap``, ``measure`` and
+        ``combine`` as ``coalign.coalign`` takes them.
+
+        With ``apply`` (it needs ``combine='shared'``: a view has one pointing) and a status free of ``NO_PEAK``, the view's
+        ``grid`` becomes ``shifted_grid(grid, dy, dx)``, its ``tx`` / ``ty`` are rebuilt and the cached pools' tables are dropped;
+        a view added with uniform 1-d ``tx`` / ``ty`` and no ``grid`` has its axes moved by the same rule.  A view with per-pixel
+        angles or a non-uniform axis is refused.  Returns the dict of ``coalign.coalign`` plus ``applied``.  The one host wait is
+        reading the shift in order to apply it."""
+        from .coalign import NO_PEAK, coalign
+        index = self._baseline_index(int(index))
+        view = self.views[index]
+        if apply and combine != 'shared':
+            raise ValueError("apply needs combine='shared': a view has one pointing")
+        deltas = self._pixel_sizes(view)
+        present = torch.as_tensor(np.nonzero(view.plane >= 0)[0], device=self.device)
+        target = view.image
+        if view.downscale > 1:
+            f = view.downscale
+            target = (target.double().view(-1, view.height, f, view.width, f).sum((2, 4)) / float(f * f)).float()
+        if isinstance(reference, str):
+            if reference != 'baseline':
+                raise ValueError(f"reference must be 'baseline' or a tensor [C_present, H, W], got {reference!r}")
+            template = self.baseline_view(index, **baseline_kw).permute(2, 0, 1).index_select(0, present)
+        else:
+            template = torch.as_tensor(reference)
+            template = template[None] if template.dim() == 2 else template
+            if tuple(template.shape) != tuple(target.shape):
+                raise ValueError(f'{view.name}: reference must be {tuple(target.shape)} (the view\'s present channels on its grid), '
+                                 f'got {tuple(template.shape)}')
+            template = template.to(device=self.device, dtype=torch.float32)
+        out = coalign(target.contiguous(), template.contiguous(), max_shift, measure=measure, min_overlap=min_overlap, combine=combine)
+        out['applied'] = False
+        if apply:
+            dy, dx, status = torch.cat([out['shift'], out['status'].double()[None]]).tolist()          # the one host wait
+            if not int(status) & NO_PEAK:
+                self._move_pointing(view, dy, dx, deltas)
+                out['applied'] = True
+        return out
+
+    def coalign_views(self, indices: Optional[Sequence[int]] = None, anchor: Optional[int] = None, passes: int = 1, **kw) -> List[dict]:
+        """Co-aligns the training views (or ``indices``) with each other: each pass estimates every one of them except
+        ``anchor`` against the reprojection baseline of the OTHER training views as they stand (:meth:`coalign_view` with
+        ``apply=False``) and then applies all shifts together -- those whose status is free of ``NO_PEAK`` and of ``EDGE``: a peak
+        on the border of the window is no located maximum (a view of a bland part of the scene gives such peaks), and moving a
+        view by it would spoil the baselines of the next pass.  Returns one dict per pass, view index -> ``{'shift': (dy, dx),
+        'status', 'score', 'applied'}`` as Python numbers.
+
+        A shift common to all views cannot be observed -- every baseline moves with it -- so the mean pointing of the set stays
+        what the headers said; ``anchor`` names a view whose pointing is trusted and fixes it: that view is never moved, and
+        further passes pull the others towards it.  ``kw``: as :meth:`coalign_view` takes them (``apply`` is not among them)."""
+        from .coalign import EDGE, NO_PEAK
+        if 'apply' in kw or 'reference' in kw:
+            raise ValueError('coalign_views estimates against the baseline and applies all shifts of a pass together')
+        indices = self.training_views if indices is None else [int(i) for i in indices]
+        indices = [i for i in indices if anchor is None or i != int(anchor)]
+        history = []
+        for _ in range(int(passes)):
+            found = [self.coalign_view(i, apply=False, **kw) for i in indices]
+            if not found:
+                history.append({})
+                continue
+            rows = torch.stack([torch.cat([f['shift'], f['status'].double()[None], f['score'][None]]) for f in found]).tolist()
+            result = {}
+            for i, (dy, dx, status, score) in zip(indices, rows):          # one host wait per pass, then every view moves
+                applied = not int(status) & (NO_PEAK | EDGE)
+                if applied:
+                    self._move_pointing(self.views[i], dy, dx, self._pixel_sizes(self.views[i]))
+                result[i] = {'shift': (dy, dx), 'status': int(status), 'score': score, 'applied': applied}
+            history.append(result)
+        return history
+
     @property
     def config(self) -> dict:
         """What ``save_state`` stores as ``data_config`` (single_channel.py:82-84, multi_thermal_loader.py:88-90), with ``wcs``

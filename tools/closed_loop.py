@@ -57,11 +57,19 @@ a wrong PSF held fixed (a Gaussian of ``FWHM0`` in place of the instrument's own
 optimiser of the network moves ``log_fwhm`` too.  The report (``fit_psf``) carries the fitted ``fwhm`` per step count and the
 held-out scores of the two runs beside those of the right PSF.
 
+``--pointing-error PX [--coalign]``: the pointing of the views taken on trust, and what co-alignment does about it.
+Every training view's ``crpix`` is displaced by a uniform draw in +-``PX`` pixels per axis (``default_rng(0)``) -- the images stay
+what the true pointing sees.  A further ray run trains on the wrong pointing; with ``--coalign`` one more trains after
+``ObservationSet.coalign_views`` (``--coalign-passes`` passes against the reprojection baseline, no anchor) has moved the grids.
+The report (``pointing``) carries the held-out scores of each run beside the true pointing's and the RMS residual pointing error
+in pixels before and after ``coalign_views``.  One seed each.
+
     python tools/closed_loop.py [--module dt|emission] [--views 8] [--size 64] [--steps 300] [--batch 2048] [--d-filter 256] [--baseline]
                                 [--instrument SPEC [--through-instrument] [--patch 16] [--patches-per-batch N] [--through-steps K]]
                                 [--likelihood observed|model] [--lambda-ssim L [--ssim-window 7]] [--deconvolve N|auto] [--skip-clean]
                                 [--cosmic-rays RATE,AMP [--despike median|nan]]
                                 [--fit-psf FWHM0 [--psf-rate 20]]
+                                [--pointing-error PX [--coalign [--coalign-passes 2] [--max-shift 8]]]
 """
 import argparse
 import json
@@ -244,7 +252,16 @@ def main():
                     help='a further ray run on observed views with particle hits: RATE of the pixels, AMP sigma each')
     ap.add_argument('--despike', choices=('median', 'nan'), default=None, help='with --cosmic-rays: Instrument.despike the views first')
     ap.add_argument('--psf-rate', type=float, default=20.0, help='rate of the TrainablePSF: its log_fwhm moves at rate x the learning rate')
+    ap.add_argument('--pointing-error', type=float, metavar='PX', default=None,
+                    help="a further run with every training view's crpix displaced by a uniform draw in +-PX pixels")
+    ap.add_argument('--coalign', action='store_true', help='with --pointing-error: one more run after ObservationSet.coalign_views')
+    ap.add_argument('--coalign-passes', type=int, default=2)
+    ap.add_argument('--max-shift', type=int, default=8, help='the window of coalign_views in pixels')
     args = ap.parse_args()
+    if args.coalign and args.pointing_error is None:
+        ap.error('--coalign needs --pointing-error PX')
+    if args.pointing_error is not None and not args.pointing_error >= 0:
+        ap.error('--pointing-error takes a number of pixels >= 0')
     if args.fit_psf is not None and not args.through_instrument:
         ap.error('--fit-psf needs --through-instrument')
     if args.fit_psf is not None and (not args.fit_psf > 0 or 'fwhm=' not in args.instrument or 'beta=' in args.instrument):
@@ -280,6 +297,8 @@ def main():
             'meta': {'t_obs': '2022-01-01T00:00:00.000'}}
     poses = [(0.1 * (k % 3 - 1), 0.3 - 6.2832 / args.views * k) for k in range(args.views)]
     report = {} if args.skip_clean else run(args, grid, poses, None)
+    if args.pointing_error is not None:
+        report['pointing'] = pointing_runs(args, grid, poses, report)
     if args.instrument is not None:
         keys = ('steps', 'rays_per_step', 'loss_first_10', 'loss_last_10', 'train_seconds', 'before', 'after', 'after_fine')
         if args.likelihood is not None:
@@ -320,6 +339,47 @@ def main():
     print(json.dumps({'closed_loop': report}))
 
 
+def pointing_runs(args, grid, poses, true_run):
+    """The runs of ``--pointing-error``: wrong pointing as it is and, with ``--coalign``, after ``coalign_views``."""
+    keys = ('steps', 'loss_first_10', 'loss_last_10', 'train_seconds', 'before', 'after')
+    out = {'pointing_error_px': args.pointing_error}
+    if true_run:
+        out['true_pointing'] = {'after': true_run['after']}
+    for name, coalign in (('wrong_pointing', False),) + ((('coaligned', True),) if args.coalign else ()):
+        pointing = {'px': args.pointing_error, 'coalign': coalign, 'passes': args.coalign_passes, 'max_shift': args.max_shift}
+        result = run(args, grid, poses, None, pointing=pointing)
+        out[name] = {**{k: result[k] for k in keys}, **pointing['log']}
+        rms = pointing['log']['rms_error_px_before'] if not coalign else pointing['log']['rms_error_px_after']
+        print(f"pointing error +-{args.pointing_error} px, {name}: RMS pointing error {rms:.3f} px; PSNR "
+              f"{result['after']['validation.psnr']:.2f} dB, SSIM {result['after']['validation.ssim']:.4f}"
+              + (f" (true pointing: {true_run['after']['validation.psnr']:.2f} dB, {true_run['after']['validation.ssim']:.4f})" if true_run else ''),
+              file=sys.stderr)
+    return out
+
+
+def displace_pointing(obs, pointing):
+    """Moves the crpix of every training view by a seeded draw in +-px (the images stay); with ``coalign`` the set then co-aligns
+    itself.  ``pointing['log']`` takes the RMS distance of crpix from the truth, in pixels, before and after."""
+    from sunerf.evaluation.loader import linear_plate_scale_axes
+    from sunerf_hip.coalign import shifted_grid
+    rng = np.random.default_rng(0)
+    truth = {i: obs.views[i].grid['crpix'] for i in obs.training_views}
+
+    def rms():
+        d = np.array([[obs.views[i].grid['crpix'][k] - truth[i][k] for k in (0, 1)] for i in truth])
+        return float(np.sqrt((d ** 2).sum(axis=1).mean()))
+    for i in truth:
+        ex, ey = rng.uniform(-pointing['px'], pointing['px'], 2)
+        view = obs.views[i]
+        view.grid = shifted_grid(view.grid, ey, ex)
+        view.tx, view.ty = linear_plate_scale_axes(view.grid, None, obs.device)
+    log = pointing['log'] = {'rms_error_px_before': rms()}
+    if pointing['coalign']:
+        history = obs.coalign_views(passes=pointing['passes'], max_shift=pointing['max_shift'])
+        log['rms_error_px_after'] = rms()
+        log['passes'] = [{str(i): {'shift': list(r['shift']), 'status': r['status'], 'score': r['score']} for i, r in h.items()} for h in history]
+
+
 def fit_psf_runs(args, grid, poses, right, keys):
     """The two further patch runs of ``--fit-psf``: the views are those the true instrument observed; the patches are seen through
     a Gaussian of ``FWHM0``, held fixed in one run and fitted in the other."""
@@ -357,14 +417,17 @@ def _recording_fwhm(batches, psf_model, steps, record):
     record.append((done, psf_model.fwhm[0].clone()))
 
 
-def run(args, grid, poses, instrument, through=False, deconvolve=None, model_instrument=None, psf_model=None, cosmic=None):
+def run(args, grid, poses, instrument, through=False, deconvolve=None, model_instrument=None, psf_model=None, cosmic=None, pointing=None):
     """``instrument`` observes the views; ``model_instrument`` (default: the same) is what a patch run sees its renders through;
-    ``psf_model``: the TrainablePSF of a FittedInstrument, trained beside the network; ``cosmic``: see ``observed_view``."""
+    ``psf_model``: the TrainablePSF of a FittedInstrument, trained beside the network; ``cosmic``: see ``observed_view``;
+    ``pointing``: see ``displace_pointing``."""
     torch.manual_seed(0)
     problem = density_temperature_problem if args.module == 'dt' else emission_problem
     mode = args.likelihood if instrument is not None and deconvolve is None else None
     obs, module, render_of, wavelengths = problem(args, grid, poses, instrument, mode, deconvolve, psf_models=psf_model, cosmic=cosmic)
     obs.hold_out('reference')
+    if pointing is not None:
+        displace_pointing(obs, pointing)
     steps = args.steps
     if through:
         steps = args.steps if args.through_steps is None else args.through_steps
