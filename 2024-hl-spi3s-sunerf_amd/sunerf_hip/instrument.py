@@ -325,6 +325,20 @@ class Instrument:
             kw.setdefault(name, p[:, k])
         return despike(image, **kw)
 
+    def combine(self, frames: torch.Tensor, **kw) -> dict:
+        """A stack of observed ``frames`` [T, C, h, w] combined per pixel with this instrument's noise model behind the clipping:
+        :func:`sunerf_hip.stack.combine` with ``a``, ``b`` and ``floor`` of :func:`sunerf_hip.despike.despike_params` (``method``,
+        ``q``, ``rank``, ``mode``, ``n_sigma``, ``iterations``, ``clip_min``, ``min_valid``, ``two_sided``, ``bad``,
+        ``return_mask``)."""
+        from .despike import despike_params
+        from .stack import combine
+        if not isinstance(frames, torch.Tensor) or frames.dim() not in (3, 4):
+            raise ValueError('Instrument.combine: frames must be a tensor [T, C, h, w] or [T, h, w]')
+        p = despike_params(self, 1 if frames.dim() == 3 else frames.shape[1])
+        for k, name in enumerate(('a', 'b', 'floor')):
+            kw.setdefault(name, p[:, k])
+        return combine(frames, **kw)
+
 
 def _correlate_bin(planes, taps, n_kernels, kh, kw, bin_factor, ay, ax, scale, boundary):
     from .ops import _ptr, _stream

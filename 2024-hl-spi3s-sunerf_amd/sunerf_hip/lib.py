@@ -324,6 +324,18 @@ _COALIGN_SIGNATURES = {
 COALIGN_SYMBOLS = tuple(_COALIGN_SIGNATURES)
 COALIGN_ABI_VERSION = 1
 
+# The stacking table (include/sunerf_hip_stack.h): an order statistic or the mean of every pixel over a stack of frames, after an
+# optional clipping against the pixel's own median.  A thirteenth table beside the twelve above, which stay as they are and keep
+# their versions.
+_STACK_SIGNATURES = {
+    'sunerf_stack_abi_version': (ctypes.c_int, []),
+    'sunerf_stack_combine': (ctypes.c_int, [c_f32p, c_void, c_void] + [ctypes.c_int] * 5 + [ctypes.c_double] + [ctypes.c_int] * 3
+                             + [ctypes.c_double] + [ctypes.c_int] * 3 + [c_f32p, c_void, c_void, c_void, c_void]),
+}
+
+STACK_SYMBOLS = tuple(_STACK_SIGNATURES)
+STACK_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -410,6 +422,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_coalign_abi_version() != COALIGN_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so co-alignment ABI version mismatch')
+        for name, (res, args) in _STACK_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_stack_abi_version() != STACK_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so stacking ABI version mismatch')
         _lib = lib
     return _lib
 

@@ -1,0 +1,367 @@
+"""CPU-only checks of the stacking step (no GPU): the thirteenth entry-point table (declared, bound, versioned, its
+argument checks in their documented order), the wrapper's refusals, the NumPy restatement tests/stack_reference.py against NumPy's
+own order statistics and against stacks small enough to check by hand, the interval property of the clipping rule, the closed scene
+of hits on Poisson and read noise, and the background of a sequence whose moving term leaves every pixel.  Every figure is printed."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import stack_reference as sr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ('sunerf_stack_abi_version', 'sunerf_stack_combine')
+
+
+@pytest.fixture(scope='session')
+def lib():
+    import sunerf_hip
+    if not os.path.exists(sunerf_hip.LIB_PATH):
+        import subprocess
+        subprocess.check_call(['bash', os.path.join(ROOT, '2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh')])
+    return sunerf_hip.load()
+
+
+# ---- the thirteenth table ---------------------------------------------------------------------------------------------------------
+def test_entry_points_are_declared_and_bound(lib):
+    import hashlib
+
+    import sunerf_hip
+    from sunerf_hip import lib as binding
+    from test_ssim_loss_host import EXPORTED_SHA256, N_EXPORTED
+    read = lambda *p: open(os.path.join(ROOT, *p)).read()          # noqa: E731
+    header = read('include', 'sunerf_hip_stack.h')
+    declared = set(re.findall(r'\b(sunerf_\w+)\s*\(', header))
+    assert declared == set(NEW_SYMBOLS) == set(sunerf_hip.STACK_SYMBOLS) == set(binding._STACK_SIGNATURES)
+    assert binding.STACK_SYMBOLS == tuple(binding._STACK_SIGNATURES)
+    taken = (sunerf_hip.EXPORTED_SYMBOLS + sunerf_hip.EXTENSION_SYMBOLS + sunerf_hip.RESPONSE_SYMBOLS + sunerf_hip.PREP_SYMBOLS
+             + sunerf_hip.INSTRUMENT_SYMBOLS + sunerf_hip.PATCH_SYMBOLS + sunerf_hip.LIKELIHOOD_SYMBOLS + sunerf_hip.SSIM_LOSS_SYMBOLS
+             + sunerf_hip.DECONVOLVE_SYMBOLS + sunerf_hip.PSF_GRAD_SYMBOLS + sunerf_hip.DESPIKE_SYMBOLS + sunerf_hip.COALIGN_SYMBOLS)
+    for name in NEW_SYMBOLS:
+        fn = getattr(lib, name)
+        assert name not in taken
+        assert fn.restype is binding._STACK_SIGNATURES[name][0] and list(fn.argtypes) == binding._STACK_SIGNATURES[name][1]
+    assert lib.sunerf_stack_abi_version() == binding.STACK_ABI_VERSION == 1
+    assert '#define SUNERF_STACK_ABI_VERSION 1' in header
+    for define in ('SUNERF_STACK_MAX_FRAMES 64', 'SUNERF_STACK_MAX_ITERATIONS 16', 'SUNERF_STACK_STATE 4', 'SUNERF_STACK_REJECTED 1',
+                   'SUNERF_STACK_INVALID 2', 'SUNERF_STACK_MEAN 0', 'SUNERF_STACK_MEDIAN 1', 'SUNERF_STACK_PERCENTILE 2',
+                   'SUNERF_STACK_RANK 3', 'SUNERF_STACK_MODE_MODEL 0', 'SUNERF_STACK_MODE_MAD 1', 'SUNERF_STACK_TWO_SIDED 1'):
+        assert f'#define {define}' in header, define
+    assert len(re.findall(r'\bstack\b', read('2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh'))) == 2
+    assert 'STACK_SYMBOLS' in read('__graft_entry__.py')
+    assert len(binding.EXPORTED_SYMBOLS) == N_EXPORTED
+    assert hashlib.sha256('\n'.join(binding.EXPORTED_SYMBOLS).encode()).hexdigest() == EXPORTED_SHA256
+    from sunerf_hip import despike, stack as wrapper
+    assert (wrapper.REJECTED, wrapper.INVALID) == (sr.REJECTED, sr.INVALID) == (despike.SPIKE, despike.INVALID) == (1, 2)
+    assert wrapper.METHODS == {'mean': sr.MEAN, 'median': sr.MEDIAN, 'percentile': sr.PERCENTILE, 'rank': sr.RANK, 'min': sr.RANK,
+                               'max': sr.RANK}
+    assert wrapper.MAX_FRAMES == 64 and wrapper.MAX_ITERATIONS == 16 and wrapper.N_STATE == 4
+
+
+def check_argument_order(lib):
+    """Limits and enumerations (-2) first, then the empty call (0), then counts, the scalars, null pointers, alignment and the
+    overlap of image with frames (-1): all before anything touches a device, so this runs without one.  ``Q`` stands for any
+    non-null aligned pointer: no call here reaches a launch."""
+    fn = lib.sunerf_stack_combine
+    names = ('frames', 'params', 'image', 'count', 'state')
+    Q = {k: ctypes.c_void_p(4096 + (1 << 20) * i) for i, k in enumerate(names)}
+
+    def call(t=8, c=2, h=9, w=11, method=1, q=0.0, rank=0, mode=0, flags=0, n_sigma=5.0, iterations=2, clip_min=3, min_valid=1,
+             bad=None, mask=None, **ptrs):
+        p = dict(Q)
+        p.update(ptrs)
+        return fn(p['frames'], bad, p['params'], t, c, h, w, method, q, rank, mode, flags, n_sigma, iterations, clip_min, min_valid,
+                  p['image'], p['count'], mask, p['state'], None)
+    none = {k: None for k in names}
+    for limit in (dict(t=65), dict(iterations=17), dict(method=4), dict(method=-1), dict(mode=2), dict(mode=-1), dict(flags=2)):
+        assert call(**limit, **none) == -2, limit
+        assert call(**limit, c=0, **none) == -2 and call(**limit, h=-1, **none) == -2, limit          # the limits come first
+    for empty in (dict(c=0), dict(h=0), dict(w=0), dict(h=0, w=0), dict(c=0, t=64, iterations=16)):
+        assert call(**empty, **none) == 0, empty                                                       # then the empty call
+    assert call(c=0, n_sigma=float('nan'), clip_min=0, min_valid=0, iterations=-1, **none) == 0     # ... before the scalars
+    assert call(c=-1) == -1 and call(h=-1) == -1 and call(w=-1) == -1 and call(c=-1, h=0) == -1
+    assert call(t=0) == -1 and call(t=-1) == -1 and call(t=0, c=0) == -1
+    assert call(iterations=-1) == -1 and call(clip_min=1) == -1 and call(min_valid=0) == -1
+    for bad_sigma in (0.0, -1.0, float('nan'), float('inf')):
+        assert call(n_sigma=bad_sigma) == -1, bad_sigma
+    for bad_q in (-0.5, 100.5, float('nan')):
+        assert call(method=2, q=bad_q) == -1 and call(method=1, q=bad_q, **none) == -1, bad_q          # q counts for PERCENTILE only
+    for k in names:
+        assert call(**{k: None}) == -1, k
+    for k in ('params', 'state'):
+        assert call(**{k: ctypes.c_void_p(Q[k].value + 4)}) == -1, k
+    # image may not overlap frames: 8 x 2 x 9 x 11 floats are 6336 bytes, the image is 792
+    assert call(image=Q['frames']) == -1 and call(image=ctypes.c_void_p(Q['frames'].value + 6332)) == -1
+    assert call(image=ctypes.c_void_p(Q['frames'].value - 788)) == -1
+    # ... nor count (198 bytes) or mask (1584 bytes), nor any of the three bad (1584 bytes), which the kernel reads beside frames
+    far = ctypes.c_void_p(Q['state'].value + (1 << 20))
+    assert call(count=Q['frames']) == -1 and call(count=ctypes.c_void_p(Q['frames'].value + 6335)) == -1
+    assert call(count=ctypes.c_void_p(Q['frames'].value - 197)) == -1
+    assert call(mask=Q['frames']) == -1 and call(mask=ctypes.c_void_p(Q['frames'].value + 6335)) == -1
+    assert call(mask=ctypes.c_void_p(Q['frames'].value - 1583)) == -1
+    for k, nbytes in (('image', 792), ('count', 198)):
+        assert call(bad=far, **{k: far}) == -1 and call(bad=far, **{k: ctypes.c_void_p(far.value + 1583)}) == -1, k
+        assert call(bad=far, **{k: ctypes.c_void_p(far.value - nbytes + 1)}) == -1, k
+    assert call(bad=far, mask=far) == -1 and call(bad=far, mask=ctypes.c_void_p(far.value + 1583)) == -1
+    assert call(bad=far, mask=ctypes.c_void_p(far.value - 1583)) == -1
+    assert call(bad=far, mask=ctypes.c_void_p(far.value + 4096), **none) == -1          # masks alone change nothing about the pointers' refusal
+    # with every pointer null the next refusal is the pointers': all the scalar checks before them pass at the limits
+    assert all(call(t=t, iterations=i, clip_min=k, min_valid=m, method=2, q=q, rank=r, mode=1, flags=1, **none) == -1
+               for t, i, k, m, q, r in ((1, 0, 2, 1, 0.0, 0), (64, 16, 64, 64, 100.0, -70), (33, 4, 3, 2, 99.9, 70)))
+
+
+def test_argument_checks_come_in_the_documented_order(lib):
+    check_argument_order(lib)
+
+
+# ---- the wrapper ------------------------------------------------------------------------------------------------------------------
+def test_the_wrapper_refuses_what_it_cannot_run():
+    from sunerf_hip import SunerfHipError
+    from sunerf_hip.stack import background, combine
+    x = torch.zeros(8, 2, 9, 11)
+    for kw in (dict(method='mode'), dict(method='percentile'), dict(method='percentile', q=-1), dict(method='percentile', q=100.5),
+               dict(method='median', q=50), dict(method='rank'), dict(method='rank', rank=1.5), dict(method='rank', rank=True),
+               dict(method='min', rank=0), dict(mode='sigma'), dict(n_sigma=0), dict(n_sigma=float('inf')), dict(iterations=17),
+               dict(iterations=-1), dict(iterations=1.5), dict(clip_min=1), dict(min_valid=0), dict(min_valid=65),
+               dict(iterations=1), dict(iterations=1, a=1.0), dict(iterations=1, a=-1.0, b=1.0), dict(iterations=1, a=[1.0] * 3, b=1.0),
+               dict(floor=-1.0)):
+        with pytest.raises(ValueError):
+            combine(x, **kw)
+        print('refused:', kw)
+    for t in (0, 65):
+        with pytest.raises(ValueError, match='frames'):
+            combine(torch.zeros(t, 1, 3, 5))
+    with pytest.raises(ValueError, match='float32'):
+        combine(x.double())
+    with pytest.raises(ValueError, match='float32'):
+        combine(x[0, 0])
+    with pytest.raises(ValueError, match='bad must have'):
+        combine(x, bad=torch.zeros(8, 2, 9, 10))
+    with pytest.raises(ValueError, match='bad must have'):
+        combine(x[:, 0], bad=torch.zeros(8, 2, 9, 11))
+    for t in (1, 3, 7):
+        with pytest.raises(ValueError, match='MAD'):
+            combine(x[:t], mode='mad', iterations=1)
+    with pytest.raises(TypeError):
+        combine(x.numpy())
+    # every argument is in order: only the device is missing
+    for kw in (dict(), dict(method='mean', iterations=2, a=1.0, b=[1.0, 2.0], bad=torch.zeros(8, 2, 9, 11, dtype=torch.bool)),
+               dict(mode='mad', iterations=16, floor=0.1, two_sided=True, return_mask=True), dict(method='rank', rank=-70),
+               dict(method='percentile', q=99.9), dict(method='max')):
+        with pytest.raises(SunerfHipError, match='no CPU path'):
+            combine(x, **kw)
+    with pytest.raises(SunerfHipError, match='no CPU path'):
+        combine(x[:7], mode='mad')          # without a pass the MAD is never formed
+    with pytest.raises(SunerfHipError, match='no CPU path'):
+        background(x[:, 0])
+    with pytest.raises(ValueError):
+        background(x, q=101)
+    assert 'F-corona' in background.__doc__ and 'stray light' in background.__doc__
+
+
+def test_instrument_combine_passes_the_noise_model(monkeypatch):
+    """``Instrument.combine`` fills ``a``, ``b`` and ``floor`` from ``despike_params`` exactly as ``Instrument.despike`` does, and
+    leaves alone what the caller gives."""
+    from sunerf_hip import stack
+    from sunerf_hip.despike import despike_params
+    from sunerf_hip.instrument import Instrument
+    seen = []
+    monkeypatch.setattr(stack, 'combine', lambda frames, **kw: seen.append((frames, kw)) or 'result')
+    inst = Instrument(unit=[100.0, 40.0, 7.5], exposure=[2.9, 1.0, 12.0], dn_per_photon=[1.2, 0.8, 3.0], read_noise=[1.2, 0.0, 5.0])
+    frames = torch.zeros(5, 3, 4, 6)
+    assert inst.combine(frames, method='mean', iterations=2) == 'result'
+    got, kw = seen[-1]
+    p = despike_params(inst, 3)
+    assert got is frames and set(kw) == {'method', 'iterations', 'a', 'b', 'floor'}
+    assert np.array_equal(kw['a'], p[:, 0]) and np.array_equal(kw['b'], p[:, 1]) and np.array_equal(kw['floor'], p[:, 2])
+    single = Instrument(unit=100.0, exposure=2.9, dn_per_photon=1.2, read_noise=1.2)
+    single.combine(frames[:, 0], a=7.0)
+    kw = seen[-1][1]
+    assert kw['a'] == 7.0 and np.array_equal(kw['b'], despike_params(single, 1)[:, 1])
+    with pytest.raises(ValueError):
+        inst.combine(frames[0, 0])
+
+
+# ---- the restatement --------------------------------------------------------------------------------------------------------------
+def columns(n_frames, n_px, seed):
+    """``[n_frames, 1, 1, n_px]`` float32 with NaN, +-inf and flagged samples, and the flags.  Pixel 0 has no valid sample, pixels
+    1 to 4 nothing but valid ones (n = n_frames: over the frame counts 1 .. 64 every n occurs), pixels 5 to 8 one sample that is not
+    valid, the rest one in three."""
+    rng = np.random.default_rng(seed)
+    frames = rng.normal(10.0, 3.0, (n_frames, 1, 1, n_px)).astype(np.float32)
+    kind = rng.integers(0, 12, frames.shape)
+    kind[..., 1:9] = 11
+    kind[rng.integers(0, n_frames, 4), 0, 0, np.arange(5, 9)] = np.arange(4)          # NaN, +inf, -inf, flagged
+    frames[kind == 0] = np.nan
+    frames[kind == 1] = np.inf
+    frames[kind == 2] = -np.inf
+    bad = (kind == 3).astype(np.uint8)
+    frames[..., 0] = np.nan          # one pixel without a valid sample
+    return frames, bad
+
+
+def test_the_restatement_is_numpys_median_sort_and_percentile():
+    """``np.nanmedian`` and ``np.sort`` of the valid samples by value; ``np.nanpercentile`` within one float32 ulp (NumPy
+    interpolates as ``lo + (hi - lo) * f`` or from the upper end, the header as ``r_l + (p - l) * (r_[l+1] - r_l)``)."""
+    differing = compared = 0
+    seen = np.zeros(65, dtype=np.int64)          # pixels compared per n
+    for n_frames in range(1, 65):
+        frames, bad = columns(n_frames, 24, n_frames)
+        work = np.where(np.isfinite(frames) & (bad == 0), frames, np.nan).astype(np.float64)[:, 0, 0]
+        n = np.sum(~np.isnan(work), axis=0)
+        assert (n[1:5] == n_frames).all() and (n[5:9] == n_frames - 1).all() and n[0] == 0
+        seen += np.bincount(n, minlength=65)
+        some = n > 0
+        image, count, mask, state = sr.combine(frames, bad, method=sr.MEDIAN)
+        assert np.array_equal(count[0, 0], n)
+        assert np.array_equal(mask == sr.INVALID, np.isnan(work)[:, None, None]) and not (mask == sr.REJECTED).any()
+        assert state[0].tolist() == [0, int(np.isnan(work).sum()), int((~some).sum()), 0]
+        with np.errstate(all='ignore'), pytest.warns(RuntimeWarning) if not some.all() else _no_warning():
+            want = np.nanmedian(work, axis=0).astype(np.float32)
+        assert np.array_equal(image[0, 0], want, equal_nan=True)
+        ordered = np.sort(work, axis=0)          # NaN last
+        for rank in (0, 1, 5, 70, -1, -2, -70):
+            got = sr.combine(frames, bad, method=sr.RANK, rank=rank)[0][0, 0]
+            idx = np.minimum(rank, n - 1) if rank >= 0 else np.maximum(n + rank, 0)
+            want = np.where(some, ordered[np.clip(idx, 0, n_frames - 1), np.arange(len(n))], np.nan).astype(np.float32)
+            assert np.array_equal(got, want, equal_nan=True), (n_frames, rank)
+        for q in (0.0, 5.0, 50.0, 99.9, 100.0):
+            got = sr.combine(frames, bad, method=sr.PERCENTILE, q=q)[0][0, 0]
+            with np.errstate(all='ignore'), pytest.warns(RuntimeWarning) if not some.all() else _no_warning():
+                want = np.nanpercentile(work, q, axis=0).astype(np.float32)
+            assert np.array_equal(np.isnan(got), np.isnan(want))
+            ulp = np.spacing(np.abs(want[some]))
+            assert np.all(np.abs(got[some].astype(np.float64) - want[some]) <= ulp), (n_frames, q)
+            differing += int(np.sum(got[some] != want[some]))
+            compared += int(some.sum())
+    print(f'percentile: {differing} of {compared} pixels differ from np.nanpercentile, each by at most one float32 ulp')
+    print('pixels compared per n = 0 .. 64:', seen.tolist())
+    assert (seen >= 4).all(), 'every n from 0 to 64 is compared, the full stack of every frame count included'
+
+
+class _no_warning:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+
+def test_the_restatement_follows_the_rules_on_stacks_small_enough_to_check_by_hand():
+    frames = np.array([4.0, 1.0, 8.0, 2.0], dtype=np.float32).reshape(4, 1, 1, 1)
+    one = lambda **kw: float(sr.combine(frames, **kw)[0][0, 0, 0])          # noqa: E731
+    assert one(method=sr.MEAN) == 3.75 and one(method=sr.MEDIAN) == 3.0
+    assert one(method=sr.PERCENTILE, q=0.0) == 1.0 and one(method=sr.PERCENTILE, q=100.0) == 8.0
+    assert one(method=sr.PERCENTILE, q=50.0) == 3.0 and one(method=sr.PERCENTILE, q=25.0) == 1.75          # p = 0.75: 1 + 0.75 (2 - 1)
+    assert [one(method=sr.RANK, rank=k) for k in (0, 1, 3, 70, -1, -2, -4, -70)] == [1.0, 2.0, 8.0, 8.0, 8.0, 4.0, 1.0, 1.0]
+    # model: m = 3, limit 1^2 (0.5 + 0.5 * 3) = 2: d^2 of 1, 2, 4, 8 is 4, 1, 1, 25 -- 8 fails above, and 1 below when two-sided
+    model = dict(params=[[0.5, 0.5, 0.0, 0.0]], n_sigma=1.0, iterations=1)
+    image, count, mask, state = sr.combine(frames, method=sr.MEAN, **model)
+    assert image[0, 0, 0] == np.float32(7.0 / 3.0) and count[0, 0, 0] == 3 and mask[:, 0, 0, 0].tolist() == [0, 0, 1, 0]
+    assert state[0].tolist() == [1, 0, 0, 1]
+    image, count, mask, state = sr.combine(frames, method=sr.MEAN, two_sided=True, **model)
+    assert image[0, 0, 0] == 3.0 and count[0, 0, 0] == 2 and mask[:, 0, 0, 0].tolist() == [0, 1, 1, 0]
+    # the second pass: survivors 1, 2, 4 with m = 2 and limit 1.5: 4 fails (d^2 = 4); the third: 1, 2 is below clip_min = 3
+    image, count, mask, state = sr.combine(frames, method=sr.MEAN, **dict(model, iterations=4))
+    assert image[0, 0, 0] == 1.5 and count[0, 0, 0] == 2 and mask[:, 0, 0, 0].tolist() == [1, 0, 1, 0] and state[0].tolist() == [2, 0, 0, 2]
+    # mad: deviations from m = 3 are 2, 1, 1, 5 -> MAD 1.5, scale 2.2239, 2 sigma = 4.4478: only 8 (d = 5) fails
+    image, count, mask, state = sr.combine(frames, method=sr.RANK, rank=-1, mode=sr.MAD, n_sigma=2.0, iterations=1)
+    assert image[0, 0, 0] == 4.0 and count[0, 0, 0] == 3 and mask[:, 0, 0, 0].tolist() == [0, 0, 1, 0]
+    # ... and with a floor of 3 the scale is the floor: 2 x 3 = 6 > 5, nothing fails
+    assert sr.combine(frames, params=[[0, 0, 3.0, 0]], method=sr.RANK, rank=-1, mode=sr.MAD, n_sigma=2.0, iterations=1)[0][0, 0, 0] == 8.0
+    # min_valid, flags and ties: 2, 2, NaN, flagged -> n = 2 < 3
+    frames = np.array([2.0, 2.0, np.nan, 5.0], dtype=np.float32).reshape(4, 1, 1, 1)
+    bad = np.array([0, 0, 0, 9], dtype=np.uint8).reshape(4, 1, 1, 1)
+    image, count, mask, state = sr.combine(frames, bad, min_valid=3)
+    assert np.isnan(image[0, 0, 0]) and count[0, 0, 0] == 2 and mask[:, 0, 0, 0].tolist() == [0, 0, 2, 2] and state[0].tolist() == [0, 2, 1, 0]
+    assert sr.combine(frames, bad, min_valid=2)[0][0, 0, 0] == 2.0
+
+
+@pytest.mark.parametrize('mode', [sr.MODEL, sr.MAD])
+@pytest.mark.parametrize('two_sided', [False, True])
+def test_survivors_are_one_run_of_the_sorted_samples_and_ties_share_a_fate(mode, two_sided):
+    """The rule is a function of the value alone: whatever the passes do, what is left is a contiguous run of the sorted valid
+    samples, and no value is both kept and rejected -- on samples quantised so that ties are everywhere."""
+    rng = np.random.default_rng(11 + mode + 2 * two_sided)
+    clipped = most = 0
+    for trial in range(400):
+        n = int(rng.integers(1, 65))
+        s = np.sort(np.round(rng.normal(0.0, 2.0, n)) + np.where(rng.random(n) < 0.15, rng.integers(-40, 40, n), 0)).astype(np.float64)
+        a, b, floor = rng.choice([0.0, 0.5, 4.0]), rng.choice([0.0, 1.0]), rng.choice([0.0, 1.0])
+        for iterations in (1, 2, 16):
+            keep, passes = sr.clip_pixel(s, a, b, floor, mode, float(rng.choice([0.5, 2.0, 5.0])), iterations, int(rng.integers(2, 6)),
+                                         two_sided)
+            assert sr.is_run(s, keep), (trial, s, keep)
+            assert passes <= iterations and (passes > 0) == (not keep.all())
+            clipped += int(not keep.all())
+            most = max(most, passes)
+    print(f'{clipped} of 1200 columns were clipped, {most} passes at most: every survivor set is a run')
+    assert clipped > 300 and most >= 2          # the trials do clip, and more than once
+
+
+# ---- the closed scene -------------------------------------------------------------------------------------------------------------
+SCENE_SEED = 1
+
+
+def closed_scene(n_frames=8, size=64, seed=SCENE_SEED):
+    """A burst of ``n_frames`` exposures of one 64 x 64 detector in DN: a smooth signal of 20 to 220 photons per pixel, Poisson
+    noise, Gaussian read noise of 3 DN (variance ``a + b * signal`` with ``a = 9``, ``b = 1``), and in 1 % of the samples a hit of
+    10 to 30 standard deviations.  Returns ``(frames, hit, params)``; generated on the CPU from ``seed``."""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:size, 0:size] / float(size)
+    signal = 120.0 + 100.0 * np.sin(2.0 * np.pi * x) * np.cos(3.0 * y)
+    a, b = 9.0, 1.0
+    frames = rng.poisson(signal, (n_frames, 1, size, size)) + rng.normal(0.0, np.sqrt(a), (n_frames, 1, size, size))
+    hit = rng.random(frames.shape) < 0.01
+    frames = frames + hit * rng.uniform(10.0, 30.0, frames.shape) * np.sqrt(a + b * signal)
+    return frames.astype(np.float32), hit, np.array([[a, b, np.sqrt(a), 0.0]])
+
+
+SCENE_CALL = dict(method=sr.MEAN, mode=sr.MODEL, n_sigma=5.0, iterations=4)
+
+
+@pytest.fixture(scope='session')
+def scene_result():
+    frames, hit, params = closed_scene()
+    return frames, hit, sr.combine(frames, params=params, **SCENE_CALL)
+
+
+def test_the_rule_finds_every_hit_of_the_closed_scene_and_leaves_the_clean_samples(scene_result):
+    frames, hit, (image, count, mask, state) = scene_result
+    missed = int(np.sum(hit & (mask != sr.REJECTED)))
+    flagged = int(np.sum(~hit & (mask == sr.REJECTED)))
+    clean = int(np.sum(~hit))
+    print(f'T = 8, 64 x 64, model, 5 sigma: {missed} of {int(hit.sum())} hits missed, {flagged} of {clean} clean samples flagged '
+          f'({flagged / clean:.1e}; bound 1e-4), {int(state[0, 3])} passes at most')
+    assert hit.sum() > 250 and missed == 0 and flagged <= 1e-4 * clean
+    assert state[0].tolist() == [int((mask == sr.REJECTED).sum()), 0, 0, int(state[0, 3])] and 1 <= state[0, 3] <= 4
+    assert np.array_equal(count[0], 8 - (mask == sr.REJECTED).sum(axis=0)[0])
+    # what the clipped mean is for: the plain mean carries the hits, the clipped one is within the noise of 8 frames everywhere
+    plain = sr.combine(frames, method=sr.MEAN)[0]
+    y, x = np.mgrid[0:64, 0:64] / 64.0
+    signal = 120.0 + 100.0 * np.sin(2.0 * np.pi * x) * np.cos(3.0 * y)
+    worst = lambda img: float(np.max(np.abs(img[0] - signal) / np.sqrt((9.0 + signal) / 8.0)))          # noqa: E731
+    print(f'largest error in units of the noise of the mean of 8 frames: plain {worst(plain):.1f}, clipped {worst(image):.1f}')
+    assert worst(plain) > 10.0 and worst(image) < 6.0
+
+
+def moving_sequence(n_frames=12, size=(1, 9, 20)):
+    """A static background plus a term that moves across the frame and is exactly 0 in at least two frames of every pixel:
+    ``(frames, static)``, without noise."""
+    c, h, w = size
+    y, x = np.mgrid[0:h, 0:w]
+    static = (50.0 / (1.0 + np.hypot(y - h / 2.0, x - w / 2.0)) ** 1.5)[None].repeat(c, 0).astype(np.float32)
+    moving = np.stack([np.clip(3.0 - np.abs(((x + 2 * y) % n_frames) - t), 0.0, None) for t in range(n_frames)])      # 5 of every 12 frames
+    assert ((moving == 0).sum(axis=0) >= 2).all() and (moving.max(axis=0) == 3.0).all()
+    return static[None] + moving.astype(np.float32)[:, None], static
+
+
+def test_the_minimum_of_a_sequence_whose_moving_term_leaves_every_pixel_is_the_static_term():
+    frames, static = moving_sequence()
+    image, count, _, state = sr.combine(frames, method=sr.PERCENTILE, q=0.0)
+    assert np.array_equal(image, static) and (count == 12).all() and state[0].tolist() == [0, 0, 0, 0]
+    assert np.array_equal(sr.combine(frames, method=sr.RANK, rank=1)[0], static)          # zero in two frames: the second smallest too
+    assert np.array_equal(sr.combine(frames, method=sr.RANK, rank=-1)[0], static + np.float32(3.0))          # every pixel saw the streamer
