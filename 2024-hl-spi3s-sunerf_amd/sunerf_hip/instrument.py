@@ -339,6 +339,19 @@ class Instrument:
             kw.setdefault(name, p[:, k])
         return combine(frames, **kw)
 
+    def noise_gate(self, frames: torch.Tensor, **kw) -> dict:
+        """A sequence of observed ``frames`` [T, C, h, w] noise-gated with this instrument's noise model as the expected noise
+        power: :func:`sunerf_hip.noise_gate.noise_gate` with ``a`` and ``b`` of :func:`sunerf_hip.despike.despike_params`
+        (``block_t``, ``mode``, ``n_sigma``, ``spectrum``, ``bad``, ``fill_invalid``)."""
+        from .despike import despike_params
+        from .noise_gate import noise_gate
+        if not isinstance(frames, torch.Tensor) or frames.dim() not in (3, 4):
+            raise ValueError('Instrument.noise_gate: frames must be a tensor [T, C, h, w] or [T, h, w]')
+        p = despike_params(self, 1 if frames.dim() == 3 else frames.shape[1])
+        for k, name in enumerate(('a', 'b')):
+            kw.setdefault(name, p[:, k])
+        return noise_gate(frames, **kw)
+
 
 def _correlate_bin(planes, taps, n_kernels, kh, kw, bin_factor, ay, ax, scale, boundary):
     from .ops import _ptr, _stream

@@ -336,6 +336,18 @@ _STACK_SIGNATURES = {
 STACK_SYMBOLS = tuple(_STACK_SIGNATURES)
 STACK_ABI_VERSION = 1
 
+# The noise-gating table (include/sunerf_hip_noise_gate.h): an image sequence in overlapping apodised blocks, every Fourier
+# coefficient of a block kept, dropped or attenuated by the block's own expected noise power.  A fourteenth table beside the
+# thirteen above, which stay as they are and keep their versions.
+_NOISE_GATE_SIGNATURES = {
+    'sunerf_noise_gate_abi_version': (ctypes.c_int, []),
+    'sunerf_noise_gate': (ctypes.c_int, [c_f32p, c_void, c_void, c_void] + [ctypes.c_int] * 7 + [ctypes.c_double]
+                          + [c_f32p, c_void, c_void]),
+}
+
+NOISE_GATE_SYMBOLS = tuple(_NOISE_GATE_SIGNATURES)
+NOISE_GATE_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -428,6 +440,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_stack_abi_version() != STACK_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so stacking ABI version mismatch')
+        for name, (res, args) in _NOISE_GATE_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_noise_gate_abi_version() != NOISE_GATE_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so noise-gating ABI version mismatch')
         _lib = lib
     return _lib
 
