@@ -51,7 +51,8 @@ constexpr int WG_PRE = 256;             // prologue kernel
 constexpr int NBUF = 4;                 // staging buffers of the in-layer stage and of the prologue (chunks in flight: NBUF - 1)
 constexpr int NBUF_H = 5;               // ... of a hidden stage: chunk it + 4 is being fetched, chunk it + 1's phases are decoded, chunk it is consumed
 #ifndef PIPE_DMA_ON_WEIGHT
-#define PIPE_DMA_ON_WEIGHT 2            // who issues the LDS-DMA pieces of a hidden stage: see "WHO ISSUES THE PIECES" below (0: 11.48, 1: 11.38, 2: 11.04 ms, r4_pipe_ab11).
+#define PIPE_DMA_ON_WEIGHT 2            // who issues the LDS-DMA pieces of a hidden stage: see "WHO ISSUES THE PIECES" below (0: 11.48, 1: 11.38, 2: 11.04 ms, r4_pipe_ab11;
+                                        // with the decoder under the matrix chain, where the pieces of modes 0 and 1 compete with it: 0: 11.10, 1: 10.85, 2: 10.75, profiles/r5_ab/).
                                         // Three more variants (3 / 7 / 7 / 7 pieces, protocol split over two waves, the data waves' tile in VGPRs) were measured slower
                                         // and removed again: commit cafd360 has them, tools/experiments/README.md the numbers
 #endif
@@ -196,6 +197,13 @@ __device__ __forceinline__ void dz_tile(const f32x16& acc, const float* c0, cons
 #define PIPE_FP16_OVFL 1  // 1: MODE.FP16_OVFL set in the data-gradient waves (an overflowing f16 conversion clamps to +-65504, true infinities stay: probed,
                           // tools/probes/probe_fp16_ovfl.hip) instead of 16 v_med3 per chunk: kernel 10.90 -> 10.76 ms (r4_pipe_ab20)
 #endif
+#ifndef PIPE_DECODE_UNDER_CHAIN
+#define PIPE_DECODE_UNDER_CHAIN 1   // 1: the data-gradient waves decode the NEXT chunk's phases behind the matrix instructions of their k-steps (the chain is
+                                    // dependent: the wave's vector issue slot idles ~900 clocks per chunk there) instead of behind the epilogue; 0: the old placement
+#endif
+#if PIPE_DECODE_UNDER_CHAIN && !PIPE_TRIM
+#error "PIPE_DECODE_UNDER_CHAIN is written on the register pairs of PIPE_TRIM"
+#endif
 typedef float v2f __attribute__((ext_vector_type(2)));
 // dz_tile on register pairs: p = acc * cos pairwise, fp32 bias sums, (saturating) fp16
 __device__ __forceinline__ void dz_tile_pairs(const f32x16& acc, const v2f* cs2, half8& d0, half8& d1, v2f* bs2) {
@@ -221,6 +229,25 @@ __device__ __forceinline__ half8 decode_phases_pairs(const v4u& p, v2f* cs2) {
     cs2[q] = (v2f){__builtin_amdgcn_cosf(r.x), __builtin_amdgcn_cosf(r.y)};
   }
   return h;
+}
+// decode_phases_pairs in two halves per phase pair (one dword of a fragment), for dealing out over two k-steps: the same
+// instructions on the same operands -- convert, packed scale, sin, cos | sin, cos, pack
+__device__ __forceinline__ void decode_pair_first(unsigned w, v2f& r, v2f& c, float& s0) {
+  r = (v2f){(float)(w & 0xffffu), (float)(w >> 16)};
+  r = r * (v2f){SUNERF_PHASE_SCALE, SUNERF_PHASE_SCALE};
+  s0 = __builtin_amdgcn_sinf(r.x);
+  c.x = __builtin_amdgcn_cosf(r.x);
+  // (anchors: without them hipcc sinks the whole decoder behind the chain again, next to the conditional LDS writes)
+  asm volatile("" : "+v"(s0), "+v"(c.x), "+v"(r));
+}
+__device__ __forceinline__ void decode_pair_second(const v2f& r, v2f& c, float s0, half8& h, int q) {
+  typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+  const float s1 = __builtin_amdgcn_sinf(r.y);
+  c.y = __builtin_amdgcn_cosf(r.y);
+  half2v pk = {(_Float16)s0, (_Float16)s1};
+  asm volatile("" : "+v"(pk), "+v"(c.y));
+  h[2 * q] = pk.x;
+  h[2 * q + 1] = pk.y;
 }
 // the 32 bias sums of a tile from the 16 x 64 per-lane sums: register g on lane half h is fragment-order index
 // 16 (g >> 3) + 8 h + (g & 7) of the tile (grad_common.h: reduce_grads_kernel reads bias slot `lane` as that index)
@@ -299,10 +326,25 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
   // w fetches the two phase fragments of its own output tile itself, and one iteration before the chunk is consumed it decodes
   // them: sin -> fp16, written back IN PLACE (the LDS image the weight-gradient waves read with ds_read_b64_tr_b16 is the same as
   // before), cos -> 16 registers for its own epilogue of the next iteration.  That work (2 LDS reads, 48 vector instructions
-  // 16 of them transcendental, 2 LDS writes) sits where these waves used to wait at the barrier; the weight-gradient waves -- the
-  // workgroup's critical path once W^T is a single fp16 image -- issue no DMA at all any more.
-  // Per iteration `it`: chunk it + NBUF_H - 1 is requested, chunk it + 1's phases (requested three iterations ago by this very
-  // wave: its own counted wait covers them) are decoded, chunk it is consumed.
+  // 16 of them transcendental, 2 LDS writes) sat behind the epilogue until round 5 (PIPE_DECODE_UNDER_CHAIN = 0), ~650 clocks on
+  // the waves that had become the workgroup's long ones.  It depends on nothing the matrix chain produces, and that chain is 16
+  // DEPENDENT matrix instructions with an LDS wait in front of each: the wave's vector issue slot idles there.
+  // Per iteration `it`: chunk it + NBUF_H - 1 is requested, chunk it + 1's phases (requested three iterations ago; the requesting
+  // wave's counted wait in front of the barrier at the top of `it` covers them, whoever that wave is) are decoded, chunk it is
+  // consumed.  ORDER OF A DATA-GRADIENT WAVE'S ITERATION [r5]:
+  //   counted wait, barrier;
+  //   2 LDS reads: the phase fragments of chunk it + 1 -- in front of the first B fragment, so that the in-order lgkmcnt waits of
+  //     the k-steps count past them;
+  //   16 k-steps: B fragment read PF ahead, wait, matrix instruction, and behind it ONE phase of the decoder (even k-step 2 q:
+  //     convert and scale pair q, sin and cos of its first phase; odd k-step 2 q + 1: sin and cos of the second, fp16 packing) --
+  //     cos into the set `cosn2`, which nothing reads before the next iteration;
+  //   the two fp16 sine fragments written back in place behind the LAST matrix instruction (the weight-gradient waves read them
+  //     behind the next barrier; nobody else touches this wave's 2 KiB of buffer it + 1 in between);
+  //   epilogue on the OTHER cos set `cosc2` (copied from `cosn2` at the top of the iteration: two sets live, 16 VGPRs more --
+  //     the branch stays within 128), products, fp16, two stores.
+  // Arithmetic and rounding are those of decode_phases_pairs (the scaling comes out as two v_mul_f32 instead of one
+  // v_pk_mul_f32: the same IEEE product); the gradients are bit-identical to the old placement's.  Measured (profiles/r5_ab/):
+  // kernel 11.05 -> 10.60 ms, data-wave k-steps 1500 -> 1705 clocks, epilogue + decoder 1030 -> 375 (stamped run).
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n_act = a.n_linear - 1, n_links = n_act - 1;
@@ -421,11 +463,15 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
     char* scratch = a.rings + (size_t)a.NP * n_links * RING * SLOT + ((size_t)blockIdx.x * 4 + wave) * 2048;
     // cos of this wave's tile for the chunk consumed NEXT (decoded one iteration ahead), and the decoder: the two phase fragments
     // of the tile (this wave's OWN DMA pieces: its counted wait covers them) -> fp16 sin in place (the H image of the
-    // weight-gradient waves, who see it behind the next barrier) + cos here.  It runs behind the epilogue, where these waves used
-    // to wait ~900 clocks at the barrier once W^T is a single fp16 image; the LDS reads are issued a few k-steps earlier.
-    // Measured alternatives (tools/experiments/README.md, round 4; this one: kernel 12.0 ms): decoding dealt out over the k-steps
-    // 12.2 (k-steps 1050 -> 2120 clocks), the sin half on the weight-gradient waves 12.9 (900 clocks there for half the work), all
-    // DMA on the weight-gradient waves 13.5 (seven pieces in a row cost them 250 clocks each).
+    // weight-gradient waves, who see it behind the next barrier) + cos here.  `decode` is the whole decoder in one block: the
+    // prologue iteration that decodes chunk 0, and every iteration of the old placement (behind the epilogue).  The main loop
+    // deals the same work out over its k-steps (PIPE_DECODE_UNDER_CHAIN, see the order of an iteration above).
+    // Measured alternatives (tools/experiments/README.md).  Round 4, when the data-gradient waves still issued DMA pieces between
+    // their matrix instructions (behind the epilogue: kernel 12.0 ms): dealt out over the k-steps 12.2 (k-steps 1050 -> 2120
+    // clocks), the sin half on the weight-gradient waves 12.9, all DMA on the weight-gradient waves 13.5.  Round 5, k-step loop free
+    // of vector-memory operations (behind the epilogue: 11.05): one phase per k-step 10.60; the 16 register moves cosn2 -> cosc2
+    // dealt out as well 10.57 against 10.58 in that call (noise: not kept); two phases per k-step on the last eight k-steps only
+    // 11.17 against 11.04 in that call (a slower box: parent 11.46).
     float cosn[16];
     v2f cosn2[8];      // (PIPE_TRIM) the same as pairs (g, g + 1)
     typedef __attribute__((address_space(3))) v4u lds_v4u;
@@ -504,6 +550,15 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
       for (int g = 0; g < 16; ++g) cosc[g] = cosn[g];
 #pragma unroll
       for (int q = 0; q < 8; ++q) cosc2[q] = cosn2[q];
+#if PIPE_DECODE_UNDER_CHAIN
+      // the next chunk's two phase fragments, in front of the first B fragment: the loop's lgkmcnt(PF - 1) waits count past them.
+      // (Unconditional: in the last iteration the buffer holds stale bytes of this wave's own region, the results are not stored.)
+      read_phases(nbuf);
+      __builtin_amdgcn_sched_barrier(0);      // (or hipcc issues them behind the first matrix instruction, among the B reads)
+      half8 hn[2];         // fp16 sin of the two fragments, written back behind the last matrix instruction
+      v2f dr = {0.f, 0.f};  // the scaled phase pair in flight between an even k-step and the odd one behind it
+      float ds0 = 0.f;
+#endif
 #pragma unroll
       for (int s = 0; s < PF; ++s) bf[s] = *(const half8*)(B + s * 1024 + lane * 16);
 #pragma unroll
@@ -521,9 +576,23 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
           if (ks == 8) piece_p(2 * wave);
           if (ks == 10) piece_p(2 * wave + 1);
         }
+#if PIPE_DECODE_UNDER_CHAIN
+        // one phase per k-step behind its matrix instruction(s): k-steps 2 q, 2 q + 1 decode dword q & 3 of fragment q >> 2
+        __builtin_amdgcn_sched_barrier(0);
+        if ((ks & 1) == 0) decode_pair_first(dp[ks >> 3][(ks >> 1) & 3], dr, cosn2[ks >> 1], ds0);
+        else decode_pair_second(dr, cosn2[ks >> 1], ds0, hn[ks >> 3], (ks >> 1) & 3);
+#else
         if (ks == 12 && decode_next) read_phases(nbuf);      // the next chunk's phases, decoded behind the epilogue
+#endif
         __builtin_amdgcn_sched_barrier(0);
       }
+#if PIPE_DECODE_UNDER_CHAIN
+      if (decode_next) {
+        const unsigned at = lds0 + nbuf * BUF_HID + (16 + 2 * wave) * 1024 + voff;
+        *(lds_half8*)(uintptr_t)at = hn[0];
+        *(lds_half8*)(uintptr_t)(at + 1024) = hn[1];
+      }
+#endif
       if (stamp) { asm volatile("" :: "v"(dacc)); s3 = __builtin_amdgcn_s_memtime(); }
       // dZ_{l-1} = dH * cos (fp16, saturating) -> ring slot, fragments 2 U, 2 U + 1 of the chunk
       half8 d0, d1;
@@ -538,7 +607,9 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
       out_slot = out_slot + 1 == RING ? 0 : out_slot + 1;
       out_z = out_slot == 0 ? ring_out : out_z + SLOT;
       buf = nbuf;
+#if !PIPE_DECODE_UNDER_CHAIN
       if (decode_next) decode(buf);
+#endif
       if (stamp) {
         const unsigned long long s4 = __builtin_amdgcn_s_memtime();
         ph[0] += s1 - s0; ph[1] += s2 - s1; ph[2] += s3 - s2; ph[3] += s4 - s3; ph[4] += s3a - s3; ph[5] += s3b - s3;

@@ -79,7 +79,7 @@ def run(n_side, S, reps, d_filter=256, n_layers=8):
             names_w = ['top', 'landed', 'barrier', 'published', 'reads+DMA+gate', 'matrix']
             for b in range(16):
                 t = tl[b]
-                if int(t.max()) == 0:
+                if not bool((t > 0).any()):      # (the in-layer stage's workgroups leave no stamps)
                     continue
                 t0 = int(t[t > 0].min())
                 print(f'   workgroup {b} (layer {7 - b // 2 if b < 14 else 0}, half {b % 2}) at iteration n/2, clocks since its first stamp:')
