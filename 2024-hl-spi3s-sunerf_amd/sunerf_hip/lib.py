@@ -348,6 +348,20 @@ _NOISE_GATE_SIGNATURES = {
 NOISE_GATE_SYMBOLS = tuple(_NOISE_GATE_SIGNATURES)
 NOISE_GATE_ABI_VERSION = 1
 
+# The registration table (include/sunerf_hip_register.h): the frames of a sequence, each with its own observer, grid and time,
+# resampled onto one reference observer, grid and time through the sphere and a differential rotation law.  A fifteenth table
+# beside the fourteen above, which stay as they are and keep their versions.
+_REGISTER_SIGNATURES = {
+    'sunerf_register_abi_version': (ctypes.c_int, []),
+    'sunerf_register_frame_desc_bytes': (ctypes.c_size_t, []),
+    'sunerf_register_frames': (ctypes.c_int, [c_void] + [ctypes.c_int] * 3 + [c_f32p, c_void, c_void] + [ctypes.c_int] * 2
+                               + [ctypes.c_double] * 4 + [ctypes.c_int, ctypes.c_float, ctypes.c_int]
+                               + [c_f32p, c_void, c_void, c_void, c_void]),
+}
+
+REGISTER_SYMBOLS = tuple(_REGISTER_SIGNATURES)
+REGISTER_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -446,6 +460,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_noise_gate_abi_version() != NOISE_GATE_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so noise-gating ABI version mismatch')
+        for name, (res, args) in _REGISTER_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_register_abi_version() != REGISTER_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so registration ABI version mismatch')
         _lib = lib
     return _lib
 

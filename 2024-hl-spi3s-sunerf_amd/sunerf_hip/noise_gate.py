@@ -10,7 +10,8 @@ One call enqueues 64 kernels (16 for ``block_t=1``) on the current stream and re
 tests/noise_gate_reference.py is the NumPy restatement.
 
 Out of scope: measuring the noise spectrum from the data (``spectrum`` is the caller's), blocks other than 16 pixels, gradients,
-and registration or derotation of the frames (structure has to stay inside a block while it is in view: co-align first)."""
+and registration or derotation of the frames (structure has to stay inside a block while it is in view: run
+``sunerf_hip.register.register_frames`` first)."""
 from typing import Optional
 
 import numpy as np

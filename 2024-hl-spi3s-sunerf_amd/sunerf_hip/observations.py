@@ -445,6 +445,32 @@ class ObservationSet:
             pred, target = normalize(pred), normalize(target)
         return image_metrics(pred.contiguous(), target.contiguous(), data_range)
 
+    # ---------------------------------------------------------------- registration
+    def register_views(self, indices: Optional[Sequence[int]] = None, reference: Optional[int] = None, **kw) -> dict:
+        """The views ``indices`` (default: all) put onto the grid, observer and time of view ``reference`` (default: the first of
+        ``indices``): :func:`sunerf_hip.register.register_frames` with each view's own ``c2w``, axes and normalised time.  The
+        ``image`` of the result, ``[T, C, H, W]``, is the stack that ``combine``, ``background`` and ``noise_gate`` take.  ``kw`` as
+        ``register_frames`` takes them (``rotation``, ``order``, ``off_disk``, ``shifts``, ...); ``Rs_per_ds`` and ``seconds_per_dt``
+        default to the set's.  Views with per-pixel angles or a downscale are refused."""
+        from .register import register_frames
+        indices = list(range(len(self.views))) if indices is None else [int(i) for i in indices]
+        if not indices:
+            raise ValueError('register_views: no views')
+        reference = indices[0] if reference is None else int(reference)
+        for i in indices + [reference]:
+            if not 0 <= i < len(self.views):
+                raise IndexError(f'view {i} of {len(self.views)}')
+            v = self.views[i]
+            if v.per_pixel:
+                raise ValueError(f'{v.name}: registration needs a view with 1-d pixel axes (per-pixel angles are not supported)')
+            if v.downscale != 1:
+                raise ValueError(f'{v.name}: registration samples the image planes as they are (downscale {v.downscale} is not supported)')
+        views = [self.views[i] for i in indices]
+        kw.setdefault('Rs_per_ds', self.Rs_per_ds)
+        kw.setdefault('seconds_per_dt', self.seconds_per_dt)
+        return register_frames([v.image for v in views], views, [v.time for v in views], reference=self.views[reference],
+                               reference_time=self.views[reference].time, **kw)
+
     # ---------------------------------------------------------------- co-alignment (DESIGN.md 8x)
     def _pixel_sizes(self, view: View):
         """Refuses a view whose pointing cannot be moved by a shift of its axes, as ``patch_pool`` refuses; for a view without
