@@ -54,7 +54,8 @@ constexpr int NBUF_H = 5;               // ... of a hidden stage: chunk it + 4 i
 #define PIPE_DMA_ON_WEIGHT 2            // who issues the LDS-DMA pieces of a hidden stage: see "WHO ISSUES THE PIECES" below (0: 11.48, 1: 11.38, 2: 11.04 ms, r4_pipe_ab11;
                                         // with the decoder under the matrix chain, where the pieces of modes 0 and 1 compete with it: 0: 11.10, 1: 10.85, 2: 10.75, profiles/r5_ab/).
                                         // Three more variants (3 / 7 / 7 / 7 pieces, protocol split over two waves, the data waves' tile in VGPRs) were measured slower
-                                        // and removed again: commit cafd360 has them, tools/experiments/README.md the numbers
+                                        // and removed again: commit cafd360 has them, tools/experiments/README.md the numbers (3 / 7 / 7 / 7 again in
+                                        // round 6, on the skewed image and the round-5 order: 11.71 against 10.23 ms)
 #endif
 #ifndef PIPE_ZD
 #define PIPE_ZD 2                       // hidden stages below the top: dZ_l is requested this many iterations before it is consumed
@@ -67,7 +68,17 @@ constexpr int NBUF_H = 5;               // ... of a hidden stage: chunk it + 4 i
 #endif
 constexpr int RING = PIPE_RING;                // chunk slots per hand-off ring
 constexpr int SLOT = PKS * 1024;        // one chunk of dZ: 16 fragments
-constexpr int BUF_HID = 24 * 1024;      // hidden stage staging: dZ_l 16 | P[J] 8 KiB (16-bit phases, decoded IN PLACE to fp16 sin = H[J])
+#ifndef PIPE_LDS_IMAGE
+#define PIPE_LDS_IMAGE 1                // LDS image of a hidden stage's fragments: 0 = fragments 1 KiB apart, rows in lane order; 1 = PAIR SKEW, fragments 1088 B apart
+                                        // (the odd fragment of a pair 64 B further, pair stride 2176); 2 = pair skew + ROW SWIZZLE (16-byte row r of a
+                                        // fragment at position r ^ 8 (r >> 5)).  See "LDS IMAGE" in hidden_stage.  Kernel, same-call medians
+                                        // (profiles/r6_ab/): with PIPE_PF = 4 image 1 / 2 -0.16 / -0.19 ms against image 0, with PIPE_PF = 2
+                                        // -0.29 / -0.22 ms (image 0 itself +0.30 ms there).  -DPIPE_LDS_IMAGE=0 -DPIPE_PF=4 is the round-5 kernel,
+                                        // instruction for instruction
+#endif
+static_assert(PIPE_LDS_IMAGE >= 0 && PIPE_LDS_IMAGE <= 2, "PIPE_LDS_IMAGE: 0, 1 or 2");
+constexpr int FRAG_H = PIPE_LDS_IMAGE ? 1088 : 1024;      // distance of two fragments in a hidden stage's staging buffer
+constexpr int BUF_HID = 24 * FRAG_H;    // hidden stage staging: dZ_l 16 | P[J] 8 fragments (16-bit phases, decoded IN PLACE to fp16 sin = H[J]): 24 / 25.5 KiB
 constexpr int BUF_IN = 16 * 1024;       // in-layer stage staging: dZ_0[J] 8 | enc 6 (| 2 unused) KiB
 constexpr int BUF_PRE = 19 * 1024;      // prologue staging: P 16 (decoded in place to H) | dZ_out operand tile 2 KiB | g_raw of the chunk 256 B
 constexpr unsigned SPIN_LIMIT = 50000000u;   // s_memrealtime ticks (100 MHz): 0.5 s
@@ -175,6 +186,19 @@ __device__ __forceinline__ void drain_matrix_pipe() { asm volatile("s_nop 15\n\t
   asm volatile("ds_read_b64_tr_b16 v[" #R0 ":" #R1 "], %1 offset:%2\n\tds_read_b64_tr_b16 v[" #R2 ":" #R3 "], %1 offset:%3" \
                : "={v[" #R0 ":" #R3 "]}"(var) : "v"(base), "i"(OFF), "i"((OFF) + 64) : "memory")
 #endif
+// The lane part of that address in a hidden stage's image (PIPE_LDS_IMAGE; 0: tr_lane_offset of grad_common.h, which the
+// in-layer stage, the prologue and the two-kernel backward keep), and where the 16-byte row of lane `lane` of a fragment sits
+// for everybody who moves whole rows: LDS-DMA (as its SOURCE offset: the DMA writes lane-linearly, and the permutation is an
+// involution), the data-gradient waves' B-fragment reads, the decoder.  Neither the second read's `offset:64` (rows + 4) nor the
+// k-step's + 256 (rows + 16) carries into the bit the swizzle flips (bit 3 of the row: rows q, q + 4 with q < 4).
+__device__ __forceinline__ unsigned tr_lane_offset_image(int lane) {
+  if (PIPE_LDS_IMAGE == 0) return tr_lane_offset(lane);
+  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
+  int row = (p >> 1) * 32 + 8 * (g >> 1) + q;
+  if (PIPE_LDS_IMAGE == 2) row ^= 8 * (row >> 5);
+  return (g & 1) * FRAG_H + row * 16 + (p & 1) * 8;
+}
+__device__ __forceinline__ unsigned frag_row_offset(int lane) { return (PIPE_LDS_IMAGE == 2 ? lane ^ (8 * (lane >> 5)) : lane) * 16; }
 
 // dZ = dH * cos of one 32 x 32 tile, rounded to (saturating) fp16 for the chain -- and, before that rounding, added to this
 // lane's running bias sums `bs` (db = sum over samples of dZ, in fp32: round 4; until then the weight-gradient waves summed
@@ -354,7 +378,15 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
   const unsigned lds_poll = lds_dummy + 1024;
   const unsigned lds_abort = lds_poll + NBUF_H * 256;      // [2]
   unsigned* status = a.ctrl;
-  const unsigned voff = lane * 16;
+  // LDS IMAGE [r6].  One ds_read_b64_tr_b16 is 64 lanes x 8 B = 128 dwords over 64 banks: 2 per bank at best.  With fragments 1 KiB
+  // apart and rows in lane order (image 0) the weight-gradient waves' lanes fall on 32 banks, 4 dwords each: fragment 2T + 1
+  // (lanes 16-31, 48-63) lies 1024 B = 0 mod 256 B behind 2T, and so do rows R + 32 (+ 512 B, the lanes with p >= 2).  Image 1
+  // puts every fragment 64 B further than the last (FRAG_H = 1088): the two fragments of a pair fall on different banks, 64 banks
+  // x 2 dwords.  Image 2 also swaps rows R + 32 + 8 and R + 32 of each 16-row group pair (row r at r ^ 8 (r >> 5)), so that each
+  // half-wave alone covers the 64 banks once.  The global layouts are untouched: the DMA's per-lane SOURCE offset carries the row
+  // permutation, `voff` below, which is also the LDS offset of lane `lane`'s own row for the lane-linear readers and writers.
+  // Operands, registers and summation order are those of image 0: bit-identical gradients.
+  const unsigned voff = frag_row_offset(lane);
 
   char* ring_in = TOP ? nullptr : a.rings + ((size_t)P * n_links + l) * RING * SLOT;
   char* ring_out = a.rings + ((size_t)P * n_links + (l - 1)) * RING * SLOT;
@@ -382,7 +414,7 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
   int run_slot = 0, run_zbuf = 0, run_pbuf = 0;
   auto next_p = [&](int nxt) __attribute__((always_inline)) {
     preal = nxt < n_my;
-    pdst = lds0 + run_pbuf * BUF_HID + 16 * 1024;
+    pdst = lds0 + run_pbuf * BUF_HID + 16 * FRAG_H;
     run_pbuf = run_pbuf + 1 == NBUF_H ? 0 : run_pbuf + 1;
     np = preal ? run_p : safe_p;
     run_p += act_chunk;
@@ -399,13 +431,13 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
       run_z = run_slot == 0 ? ring_in : run_z + SLOT;
     }
   };
-  // LDS image of a chunk: pieces 0..15 dZ fragments, 16..23 P[J] (decoded in place to H[J])
+  // LDS image of a chunk: pieces 0..15 dZ fragments, 16..23 P[J] (decoded in place to H[J]), FRAG_H apart
   auto piece_z = [&](int f) __attribute__((always_inline)) {
-    const unsigned dst = zreal ? zdst + f * 1024 : lds_dummy;
+    const unsigned dst = zreal ? zdst + f * FRAG_H : lds_dummy;
     if (TOP) dma_piece_s<1>(nz + (size_t)f * 1024, voff, dst);
     else dma_piece_s<2>(nz + (size_t)f * 1024, voff, dst);
   };
-  auto piece_p = [&](int f) __attribute__((always_inline)) { dma_piece_s<1>(np + (size_t)f * 1024, voff, preal ? pdst + f * 1024 : lds_dummy); };
+  auto piece_p = [&](int f) __attribute__((always_inline)) { dma_piece_s<1>(np + (size_t)f * 1024, voff, preal ? pdst + f * FRAG_H : lds_dummy); };
   // WHO ISSUES THE PIECES (PIPE_DMA_ON_WEIGHT): 0 = the data-gradient waves, between their matrix instructions (4 dZ fragments +
   // the 2 phase fragments of the wave's own tile each); 1 = the phase fragments by the weight-gradient waves (2 each, between
   // THEIR matrix instructions); 2 = everything by the weight-gradient waves (4 + 2 each).  A piece holds the issuing wave for
@@ -441,9 +473,14 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
 #endif
     // output stores / DMA pieces (dZ fragments w, 4 + w, 8 + w, 12 + w; phase fragments 2 w, 2 w + 1 of this wave's own tile) per iteration
 #ifndef PIPE_PF
-#define PIPE_PF 4
+#define PIPE_PF 2
 #endif
-    constexpr int PF = PIPE_PF;                      // B fragments requested PF k-steps ahead of their matrix instructions
+    // B fragments requested PF k-steps ahead of their matrix instructions.  On image 0 four were best (round 5: PF = 2 +0.22 ms, 6 +0.09 ms;
+    // round 6: image 0 with PF = 2 +0.30 ms): the reads wait behind the weight-gradient waves' operand reads, which start at the same
+    // barrier and are replayed four-fold there.  On the skewed images those take half the LDS cycles or fewer, and two reads ahead are
+    // enough: kernel, same-call medians against the parent (profiles/r6_ab/r6_pipe_ab2.log, ab3.log): image 2 with PF = 1 / 2 / 3 / 4 / 6
+    // -0.05 / -0.22 .. -0.32 / -0.13 / -0.20 / -0.17 ms, image 1 with PF = 2 / 6 -0.29 / -0.25 ms
+    constexpr int PF = PIPE_PF;
     const int U = 4 * j + wave;                      // output tile: features 32 U .. 32 U + 31 of layer l-1
     const int li = (a.n_linear - 2) - l;
     half8 wt_hi[PKS], wt_lo[HI_ONLY ? 1 : PKS];
@@ -478,23 +515,23 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
     typedef __attribute__((address_space(3))) half8 lds_half8;
     v4u dp[2];
     auto read_phases = [&](int b) __attribute__((always_inline)) {
-      const unsigned at = lds0 + b * BUF_HID + (16 + 2 * wave) * 1024 + voff;
+      const unsigned at = lds0 + b * BUF_HID + (16 + 2 * wave) * FRAG_H + voff;
       dp[0] = *(const lds_v4u*)(uintptr_t)at;
-      dp[1] = *(const lds_v4u*)(uintptr_t)(at + 1024);
+      dp[1] = *(const lds_v4u*)(uintptr_t)(at + FRAG_H);
     };
     auto decode = [&](int b) __attribute__((always_inline)) {
-      const unsigned at = lds0 + b * BUF_HID + (16 + 2 * wave) * 1024 + voff;
+      const unsigned at = lds0 + b * BUF_HID + (16 + 2 * wave) * FRAG_H + voff;
       if (PIPE_TRIM) {
         const half8 h0 = decode_phases_pairs(dp[0], cosn2), h1 = decode_phases_pairs(dp[1], cosn2 + 4);
         *(lds_half8*)(uintptr_t)at = h0;
-        *(lds_half8*)(uintptr_t)(at + 1024) = h1;
+        *(lds_half8*)(uintptr_t)(at + FRAG_H) = h1;
         return;
       }
       float sn[16];
       decode_phases(dp[0], sn, cosn);
       decode_phases(dp[1], sn + 8, cosn + 8);
       *(lds_half8*)(uintptr_t)at = to_half8(sn);
-      *(lds_half8*)(uintptr_t)(at + 1024) = to_half8(sn + 8);
+      *(lds_half8*)(uintptr_t)(at + FRAG_H) = to_half8(sn + 8);
     };
     // prologue iterations -(NBUF_H-1) .. -1: DMA only (+ two dummy stores: the same vmcnt accounting as a full iteration); the
     // last of them decodes chunk 0
@@ -560,10 +597,10 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
       float ds0 = 0.f;
 #endif
 #pragma unroll
-      for (int s = 0; s < PF; ++s) bf[s] = *(const half8*)(B + s * 1024 + lane * 16);
+      for (int s = 0; s < PF; ++s) bf[s] = *(const half8*)(B + s * FRAG_H + voff);
 #pragma unroll
       for (int ks = 0; ks < PKS; ++ks) {
-        if (ks + PF < PKS) bf[(ks + PF) % (PF + 1)] = *(const half8*)(B + (ks + PF) * 1024 + lane * 16);
+        if (ks + PF < PKS) bf[(ks + PF) % (PF + 1)] = *(const half8*)(B + (ks + PF) * FRAG_H + voff);
         if constexpr (!HI_ONLY) dacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wt_lo[ks], bf[ks % (PF + 1)], dacc, 0, 0, 0);
         dacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wt_hi[ks], bf[ks % (PF + 1)], dacc, 0, 0, 0);
         if (NP_D >= 4) {
@@ -588,9 +625,9 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
       }
 #if PIPE_DECODE_UNDER_CHAIN
       if (decode_next) {
-        const unsigned at = lds0 + nbuf * BUF_HID + (16 + 2 * wave) * 1024 + voff;
+        const unsigned at = lds0 + nbuf * BUF_HID + (16 + 2 * wave) * FRAG_H + voff;
         *(lds_half8*)(uintptr_t)at = hn[0];
-        *(lds_half8*)(uintptr_t)(at + 1024) = hn[1];
+        *(lds_half8*)(uintptr_t)(at + FRAG_H) = hn[1];
       }
 #endif
       if (stamp) { asm volatile("" :: "v"(dacc)); s3 = __builtin_amdgcn_s_memtime(); }
@@ -671,7 +708,7 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
   unsigned have_in = 0, have_out = 0;      // wave 4: newest known min(prod) of the input link / min(cons) of the output link
   unsigned st_in[2] = {0, 0}, st_out[2] = {0, 0};       // (lane 0 of wave 4) fallback spins and the 100 MHz ticks they took
   const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
-  const unsigned laneoff = tr_lane_offset(lane);
+  const unsigned laneoff = tr_lane_offset_image(lane);
 
   // gate of iteration `itn` (wave 4): its DMA (chunk itn + NBUF_H - 1) needs that chunk published by both producers, its output
   // (slot itn % RING) needs chunk itn - RING landed in both consumers.  Normally the polled counters already say so.
@@ -754,12 +791,13 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
     if (stamp) s1 = __builtin_amdgcn_s_memtime();
     // operand bases of this wave's block: row tiles r0.. of the dZ fragments, column tiles c0.. of the H fragments (fp16 sin,
     // decoded in place by the data-gradient waves one iteration ago); the tile and k-step parts of the addresses are immediates
-    const unsigned bufA = lds0 + buf * BUF_HID + laneoff + r0 * 2048, bufB = lds0 + buf * BUF_HID + laneoff + 16 * 1024 + c0 * 2048;
+    constexpr int PAIR = 2 * FRAG_H;      // a tile's fragment pair
+    const unsigned bufA = lds0 + buf * BUF_HID + laneoff + r0 * PAIR, bufB = lds0 + buf * BUF_HID + laneoff + 16 * FRAG_H + c0 * PAIR;
     // operands of the two k-steps: A = dZ^T row tiles r0 .. r0 + 3, B = H column tiles c0, c0 + 1; registers v80 .. v127
     half8 A0[4], B0[2], A1[4], B1[2];
-    TR_FIXED(80, 81, 82, 83, 0 * 2048, A0[0], bufA); TR_FIXED(84, 85, 86, 87, 1 * 2048, A0[1], bufA);
-    TR_FIXED(88, 89, 90, 91, 2 * 2048, A0[2], bufA); TR_FIXED(92, 93, 94, 95, 3 * 2048, A0[3], bufA);
-    TR_FIXED(96, 97, 98, 99, 0 * 2048, B0[0], bufB); TR_FIXED(100, 101, 102, 103, 1 * 2048, B0[1], bufB);
+    TR_FIXED(80, 81, 82, 83, 0 * PAIR, A0[0], bufA); TR_FIXED(84, 85, 86, 87, 1 * PAIR, A0[1], bufA);
+    TR_FIXED(88, 89, 90, 91, 2 * PAIR, A0[2], bufA); TR_FIXED(92, 93, 94, 95, 3 * PAIR, A0[3], bufA);
+    TR_FIXED(96, 97, 98, 99, 0 * PAIR, B0[0], bufB); TR_FIXED(100, 101, 102, 103, 1 * PAIR, B0[1], bufB);
     typedef __attribute__((address_space(3))) v4u lds_v4u;
     v4u pw = {0, 0, 0, 0};
     if (gatew) pw = *(const lds_v4u*)(uintptr_t)(lds_poll + buf * 256);     // the poll issued NBUF_H-1 iterations ago
@@ -775,9 +813,9 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
     }
     if (stamp) s2 = __builtin_amdgcn_s_memtime();
     asm volatile("" : "+v"(A0[0]), "+v"(A0[1]), "+v"(A0[2]), "+v"(A0[3]), "+v"(B0[0]), "+v"(B0[1]));
-    TR_FIXED(104, 105, 106, 107, 0 * 2048 + 256, A1[0], bufA); TR_FIXED(108, 109, 110, 111, 1 * 2048 + 256, A1[1], bufA);
-    TR_FIXED(112, 113, 114, 115, 2 * 2048 + 256, A1[2], bufA); TR_FIXED(116, 117, 118, 119, 3 * 2048 + 256, A1[3], bufA);
-    TR_FIXED(120, 121, 122, 123, 0 * 2048 + 256, B1[0], bufB); TR_FIXED(124, 125, 126, 127, 1 * 2048 + 256, B1[1], bufB);
+    TR_FIXED(104, 105, 106, 107, 0 * PAIR + 256, A1[0], bufA); TR_FIXED(108, 109, 110, 111, 1 * PAIR + 256, A1[1], bufA);
+    TR_FIXED(112, 113, 114, 115, 2 * PAIR + 256, A1[2], bufA); TR_FIXED(116, 117, 118, 119, 3 * PAIR + 256, A1[3], bufA);
+    TR_FIXED(120, 121, 122, 123, 0 * PAIR + 256, B1[0], bufB); TR_FIXED(124, 125, 126, 127, 1 * PAIR + 256, B1[1], bufB);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       if (ks == 1) {
@@ -1234,7 +1272,8 @@ extern "C" int sunerf_mlp_backward_pipe(int d_filter, int n_linear, int d_out, c
   // sticky block in front of it is only ever OR-ed into (reduce_grads_kernel) and belongs to the caller
   if ((e = hipMemsetAsync(ws + L.ctrl, 0, L.rings - L.ctrl, st)) != hipSuccess) return (int)e;
   const size_t lds_pre = (size_t)NBUF * BUF_PRE + 1024;
-  const size_t lds_pipe = (size_t)NBUF_H * BUF_HID + 1024 + NBUF_H * 256 + 64;
+  constexpr size_t lds_pipe = (size_t)NBUF_H * BUF_HID + 1024 + NBUF_H * 256 + 64;      // five staging buffers, dummy piece, poll slots, abort / start words
+  static_assert(lds_pipe <= 160 * 1024 && (size_t)NBUF * BUF_IN + 1024 + NBUF * 256 + 64 <= lds_pipe, "LDS of a CU: 160 KiB");
   if ((e = hipFuncSetAttribute((const void*)bwd_prologue_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pre)) != hipSuccess) return (int)e;
   if ((e = hipFuncSetAttribute((const void*)bwd_pipe_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pipe)) != hipSuccess) return (int)e;
   if ((e = hipFuncSetAttribute((const void*)bwd_pipe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pipe)) != hipSuccess) return (int)e;
