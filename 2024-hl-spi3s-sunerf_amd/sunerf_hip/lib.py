@@ -362,6 +362,22 @@ _REGISTER_SIGNATURES = {
 REGISTER_SYMBOLS = tuple(_REGISTER_SIGNATURES)
 REGISTER_ABI_VERSION = 1
 
+# The enhancement table (include/sunerf_hip_enhance.h): multi-scale Gaussian normalisation, ring statistics and the normalising
+# radial graded filter.  A sixteenth table beside the fifteen above, which stay as they are and keep their versions.
+_ENHANCE_SIGNATURES = {
+    'sunerf_enhance_abi_version': (ctypes.c_int, []),
+    'sunerf_enhance_mgn_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3),
+    'sunerf_enhance_mgn': (ctypes.c_int, [c_f32p, c_void] + [ctypes.c_int] * 3 + [c_void, c_void, ctypes.c_int, ctypes.c_double]
+                           + [ctypes.c_float] * 3 + [c_f32p] * 6 + [c_void, c_void, ctypes.c_size_t, c_void]),
+    'sunerf_enhance_radial_statistics': (ctypes.c_int, [c_f32p, c_void] + [ctypes.c_int] * 3 + [ctypes.c_double] * 2
+                                         + [c_void, ctypes.c_int, ctypes.c_int] + [c_void] * 6),
+    'sunerf_enhance_nrgf': (ctypes.c_int, [c_f32p, c_void] + [ctypes.c_int] * 3 + [ctypes.c_double] * 2
+                            + [c_void, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int] + [c_void] * 5 + [c_f32p, c_void, c_void]),
+}
+
+ENHANCE_SYMBOLS = tuple(_ENHANCE_SIGNATURES)
+ENHANCE_ABI_VERSION = 1
+
 
 class SunerfHipError(RuntimeError):
     pass
@@ -466,6 +482,12 @@ def load():
             fn.argtypes = args
         if lib.sunerf_register_abi_version() != REGISTER_ABI_VERSION:
             raise SunerfHipError('libsunerf_hip.so registration ABI version mismatch')
+        for name, (res, args) in _ENHANCE_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        if lib.sunerf_enhance_abi_version() != ENHANCE_ABI_VERSION:
+            raise SunerfHipError('libsunerf_hip.so enhancement ABI version mismatch')
         _lib = lib
     return _lib
 
