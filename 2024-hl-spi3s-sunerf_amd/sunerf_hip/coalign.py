@@ -14,6 +14,7 @@ from typing import Tuple, Union
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream, _workspace
 
 MAX_SHIFT = 32                  # include/sunerf_hip_coalign.h: SUNERF_COALIGN_MAX_SHIFT
 N_SUMS = 6                      # n, Sa, Sb, Saa, Sbb, Sab
@@ -33,7 +34,6 @@ def _window(max_shift) -> Tuple[int, int]:
 def launch(image, template, bad_image, bad_template, my: int, mx: int) -> torch.Tensor:
     """``sunerf_coalign_shift_sums`` on device tensors: ``image`` and ``template`` [C, H, W] float32, the masks uint8 of that
     shape or None.  Returns ``sums`` [C, 2 my + 1, 2 mx + 1, 6] float64."""
-    from .ops import _ptr, _stream, _workspace
     c, h, w = image.shape
     dev = image.device
     sums = torch.empty((c, 2 * my + 1, 2 * mx + 1, N_SUMS), dtype=torch.float64, device=dev)

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream, _workspace
 from .instrument import BOUNDARY, Instrument, correlate_bin_adjoint
 
 MAX_ITERATIONS = 10000                           # include/sunerf_hip_deconvolve.h
@@ -39,7 +40,6 @@ def launch(u, d, bad, norm, params, taps, n_kernels, kh, kw, bin_factor, ay, ax,
     ``state`` [C, 4] float64 (deviance, n_valid, iterations_applied, stopped) and ``ratio`` [C, h, w] float32, the call's scratch
     (the ratio of the last pass that ran on each plane).  ``params`` [C, 2] and ``taps`` are float64 on the device, ``bad`` uint8
     or None."""
-    from .ops import _ptr, _stream, _workspace
     c, h, w = u.shape
     dev = u.device
     state = torch.empty((c, N_STATE), dtype=torch.float64, device=dev)

@@ -13,7 +13,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import lib as _l
-from .ops import _dev, _ptr, _stream
+from ._ffi import _dev, _ptr, _stream
 
 MAX_NODES = 128
 OUTPUTS = ('dem', 'em', 'logt_mean', 'column')

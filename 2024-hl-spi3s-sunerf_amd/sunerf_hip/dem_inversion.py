@@ -14,8 +14,8 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import lib as _l
+from ._ffi import _dev, _ptr, _stream
 from .dem import MAX_NODES
-from .ops import _dev, _ptr, _stream
 
 MAX_CHANNELS = 8
 OUTPUTS = ('dem', 'em', 'logt_mean', 'chi2', 'lam', 'status')

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream, _workspace
 
 SPIKE, INVALID, UNFILLED = 1, 2, 4              # include/sunerf_hip_despike.h
 MODES = {'model': 0, 'mad': 1}
@@ -41,7 +42,6 @@ def despike_params(instrument, n_channels: int) -> np.ndarray:
 def launch(image, bad, params, radius, mode, flags, n_sigma, grow_sigma, min_valid, max_iterations):
     """``sunerf_despike`` on device tensors: ``image`` [C, H, W] float32, ``bad`` uint8 of that shape or None, ``params`` [C, 4]
     float64.  Returns ``(clean, mask, state)``: float32 and uint8 of the image's shape and [C, 6] float64."""
-    from .ops import _ptr, _stream, _workspace
     c, h, w = image.shape
     dev = image.device
     clean = torch.empty_like(image)

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import grid_field as _gf
-from .ops import _dev, _ptr
+from ._ffi import _dev, _ptr
 
 TIME_CLAMP, TIME_FILL = 0, 1
 TIME_MODES = {'clamp': TIME_CLAMP, 'fill': TIME_FILL}

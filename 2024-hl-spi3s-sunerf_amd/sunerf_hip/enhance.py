@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream, _workspace
 
 MAX_SCALES, MAX_RADIUS = 8, 128
 MAX_RINGS, MAX_SEGMENTS, MAX_BINS = 4096, 360, 65536
@@ -100,7 +101,6 @@ def mgn_launch(planes, bad, sigma, weights, truncate, k, gamma, h, lo, hi, floor
     """``sunerf_enhance_mgn`` on checked arguments: ``planes`` float32 [C, H, W] and ``bad`` uint8 or None on the device, ``sigma``
     float64 and ``weights`` float32 host arrays, ``lo`` / ``hi`` / ``floor`` float32 device tensors [C] or None.  Returns ``(out,
     lo, hi, state [C, 3])``."""
-    from .ops import _ptr, _stream, _workspace
     dev = planes.device
     c, hgt, wid = (int(v) for v in planes.shape)
     lib = _l.load()
@@ -188,7 +188,6 @@ def _geometry(name, center, edges, n_segments=1):
 
 def statistics_launch(planes, bad, cy, cx, edges, n_segments):
     """``sunerf_enhance_radial_statistics``: ``edges`` a float64 device tensor.  Returns count, mean, std, min, max ``[C, R, S]``."""
-    from .ops import _ptr, _stream
     dev = planes.device
     c, hgt, wid = (int(v) for v in planes.shape)
     shape = (c, int(edges.shape[0]) - 1, int(n_segments))
@@ -219,7 +218,6 @@ def radial_statistics(image, center, edges, n_segments: int = 1, bad=None) -> di
 def nrgf_launch(planes, bad, cy, cx, edges, outside, missing, statistics):
     """``sunerf_enhance_nrgf``: ``statistics`` None (computed in the call) or ``(count, mean, std)`` device tensors ``[C, R]``.
     Returns ``(out, state [C, 3], (count, mean, std, min, max))`` -- min and max None with the caller's statistics."""
-    from .ops import _ptr, _stream
     dev = planes.device
     c, hgt, wid = (int(v) for v in planes.shape)
     rings = int(edges.shape[0]) - 1

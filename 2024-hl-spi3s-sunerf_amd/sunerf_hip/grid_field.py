@@ -17,7 +17,7 @@ from typing import Callable, NamedTuple, Optional, Sequence
 import torch
 
 from . import lib as _l
-from .ops import _dev, _ptr, _stream, _workspace
+from ._ffi import _dev, _ptr, _stream, _workspace
 from .volume import CartesianGrid, Plane, _Grid
 
 MAX_CHANNELS = 4

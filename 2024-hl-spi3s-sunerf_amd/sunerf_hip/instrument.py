@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream
 
 MAX_KERNEL, MAX_BIN = 96, 8                      # include/sunerf_hip_instrument.h
 BOUNDARY = {'zero': 0, 'nearest': 1}
@@ -285,7 +286,6 @@ class Instrument:
               want_sigma: bool = True, want_saturated: bool = True):
         """The noise stage alone on ``expected`` [C, H, W] (image units): ``(image, sigma, saturated)``; element (c, r, k) draws
         with the counter ``index_offset + (c H + r) W + k``."""
-        from .ops import _ptr, _stream
         expected = self._planes(expected, 'Instrument.noise')
         c, h, w = expected.shape
         dev = expected.device
@@ -354,7 +354,6 @@ class Instrument:
 
 
 def _correlate_bin(planes, taps, n_kernels, kh, kw, bin_factor, ay, ax, scale, boundary):
-    from .ops import _ptr, _stream
     c, h, w = planes.shape
     dev = planes.device
     out = torch.empty((c, h // bin_factor, w // bin_factor), dtype=torch.float32, device=dev)
@@ -366,7 +365,6 @@ def _correlate_bin(planes, taps, n_kernels, kh, kw, bin_factor, ay, ax, scale, b
 def correlate_bin_adjoint(g_out, height, width, taps, n_kernels, kh, kw, bin_factor, ay, ax, scale, boundary):
     """``g_in`` [C, height, width] float32: the transpose of the strided correlation applied to ``g_out``
     [C, height // bin, width // bin] (``sunerf_patch_correlate_bin_adjoint``)."""
-    from .ops import _ptr, _stream
     c = g_out.shape[0]
     dev = g_out.device
     if tuple(g_out.shape) != (c, height // bin_factor, width // bin_factor) or g_out.dtype != torch.float32:
@@ -396,7 +394,6 @@ class _CorrelateBin(torch.autograd.Function):
 
 def philox(counters: torch.Tensor, key0: int, key1: int) -> torch.Tensor:
     """Philox4x32-10 of ``counters`` [n, 4] (int32 / uint32 bit patterns, on the device) under the key: [n, 4], same dtype."""
-    from .ops import _ptr, _stream
     if not counters.is_cuda:
         raise _l.SunerfHipError('philox runs on a ROCm device (there is no CPU path)')
     if counters.dim() != 2 or counters.shape[1] != 4 or counters.element_size() != 4:

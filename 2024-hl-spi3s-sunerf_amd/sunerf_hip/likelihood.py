@@ -19,8 +19,8 @@ import torch
 from torch import nn
 
 from . import lib as _l
+from ._ffi import _dev, _ptr, _stream
 from .instrument import Instrument
-from .ops import _dev, _ptr, _stream
 from .response import MAX_CHANNELS, ResponseSet, as_response_set
 
 MODES = {'observed': 0, 'model': 1}

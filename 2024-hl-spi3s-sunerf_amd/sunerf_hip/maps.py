@@ -15,7 +15,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import lib as _l
-from .ops import _dev, _ptr, _stream
+from ._ffi import _dev, _ptr, _stream
 
 TILE_SCRATCH_BYTES = 1 << 30        # default tile: a tile's per-sample scratch stays under about this
 

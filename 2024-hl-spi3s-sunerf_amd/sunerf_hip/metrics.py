@@ -11,7 +11,7 @@ from typing import Dict
 import torch
 
 from . import lib as _l
-from .ops import _ptr, _stream
+from ._ffi import _ptr, _stream
 
 
 def image_metrics(pred: torch.Tensor, target: torch.Tensor, data_range: float) -> Dict[str, torch.Tensor]:

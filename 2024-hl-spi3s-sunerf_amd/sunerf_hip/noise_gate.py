@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream
 from .despike import _per_plane
 
 MODES = {'gate': 0, 'wiener': 1}                # include/sunerf_hip_noise_gate.h
@@ -32,7 +33,6 @@ def launch(frames, bad, params, spectrum, block_t, mode, flags, n_sigma):
     """``sunerf_noise_gate`` on device tensors: ``frames`` [T, C, H, W] float32, ``bad`` uint8 of that shape or None, ``params``
     [C, 4] float64, ``spectrum`` [C, block_t, 16, 16] float32 or None.  Returns ``(out, state)``: float32 of the frames' shape and
     [C, 4] int64."""
-    from .ops import _ptr, _stream
     t, c, h, w = frames.shape
     dev = frames.device
     out = torch.empty((t, c, h, w), dtype=torch.float32, device=dev)

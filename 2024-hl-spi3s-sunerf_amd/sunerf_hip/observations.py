@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream
 from .dist import shard_range
 from .feed import RayPool
 
@@ -160,7 +161,6 @@ class _Table:
 
     def build(self, out: Dict[str, torch.Tensor], slot_begin: int, n_slots: int, permute: bool, seed: int = 0, epoch: int = 0):
         """Records ``[slot_begin, slot_begin + n_slots)`` into the first ``n_slots`` rows of ``out``'s tensors."""
-        from .ops import _ptr, _stream
         if n_slots > out['rays'].shape[0]:
             raise ValueError('output tensors are smaller than the slot range')
         _l.call(self.device, 'sunerf_build_ray_pool', _ptr(self.desc), len(self.views), self.n_pixels, _ptr(self.valid_index),

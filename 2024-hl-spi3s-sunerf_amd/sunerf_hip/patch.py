@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream
 from .instrument import Instrument
 from .observations import MAX_CHANNELS, View
 
@@ -87,7 +88,6 @@ def patch_view_descriptors(views: Sequence[View], axes: Sequence[Tuple[torch.Ten
 def records(desc: torch.Tensor, n_views: int, triples: torch.Tensor, n_channels: int, patch: int, bin_factor: int, kh: int, kw: int,
             with_wavelength: bool) -> Dict[str, torch.Tensor]:
     """``sunerf_patch_records`` on a device table ``desc`` and device int32 triples [n, 3] = (view, R0, C0)."""
-    from .ops import _ptr, _stream
     dev = desc.device
     if dev.type != 'cuda':
         raise _l.SunerfHipError('patch records are written by sunerf_patch_records on a ROCm device (there is no CPU path)')

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream
 
 SEGMENT = 128                                   # SUNERF_PREP_SEGMENT: samples of a line that one thread filters
 HORIZON = {0: 0, 1: 0, 2: 23, 3: 30, 4: 39, 5: 47}      # samples a segment's recursions start early / late (largest pole)
@@ -148,7 +149,6 @@ def _check_order(order) -> int:
 def spline_prefilter(image: torch.Tensor, order: int = 3, want_mask: bool = False):
     """``(coefficients (C, H, W) fp64, mask (C, H, W) uint8 or None)`` of device planes ``(C, H, W)`` fp32:
     ``scipy.ndimage.spline_filter(order, mode='mirror')`` with non-finite pixels taken as 0 and flagged in the mask."""
-    from .ops import _ptr, _stream
     order = _check_order(order)
     image = _device_planes(image)
     dev = image.device
@@ -168,7 +168,6 @@ def affine_resample(coefficients: torch.Tensor, matrix, offset, out_shape, order
     """``(C, H', W')`` fp32 from prefiltered planes: ``scipy.ndimage.affine_transform(matrix, offset, mode='constant',
     cval=missing)`` followed per plane by the epilogue that ``flags`` and ``params (C, 6)`` fp64 = lo, hi, factor, vmin, vmax, 0
     describe (``include/sunerf_hip_prep.h``).  ``params=None``: factor 1."""
-    from .ops import _ptr, _stream
     order = _check_order(order)
     if coefficients.dim() != 3 or coefficients.dtype != torch.float64 or not coefficients.is_cuda:
         raise ValueError('coefficients must be (C, H, W) fp64 on a ROCm device')
@@ -197,7 +196,6 @@ def affine_resample(coefficients: torch.Tensor, matrix, offset, out_shape, order
 def order_statistics(x: torch.Tensor, ranks: torch.Tensor):
     """``(values (C, R) fp32, nan_count (C,) int64)``: the elements of 0-based rank ``ranks (C, R)`` (int64, on the device) of
     every plane of ``x (C, ...)`` in ascending order with NaNs left out; NaN for a rank outside the valid ones."""
-    from .ops import _ptr, _stream
     if not x.is_cuda:
         raise _l.SunerfHipError('order statistics run on a ROCm device (there is no CPU path)')
     x = x.detach().to(torch.float32).contiguous()

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream, _workspace
 from .instrument import BOUNDARY, FWHM_PER_SIGMA, MAX_KERNEL, Instrument, _correlate_bin, correlate_bin_adjoint
 
 _WORKSPACES = {}
@@ -23,7 +24,6 @@ def tap_gradient(planes: torch.Tensor, g_out: torch.Tensor, n_kernels: int, kh: 
     """``sunerf_psf_grad_taps``: fp64 ``[n_kernels, kh, kw]``, the gradient with respect to the taps of the strided correlation
     that read ``planes`` [n, H, W] (float32, on the device) and whose output has the cotangent ``g_out`` [n, H // bin, W // bin]
     (float32).  Plane ``p`` belongs to kernel ``p % n_kernels``; ``n_kernels`` divides ``n``.  The empty call gives zeros."""
-    from .ops import _ptr, _stream, _workspace
     if not isinstance(planes, torch.Tensor) or not isinstance(g_out, torch.Tensor):
         raise TypeError('tap_gradient: planes and g_out must be torch.Tensors')
     if not planes.is_cuda or g_out.device != planes.device:

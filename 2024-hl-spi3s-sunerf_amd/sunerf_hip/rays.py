@@ -14,7 +14,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import lib as _l
-from .ops import _ptr, _stream
+from ._ffi import _ptr, _stream
 
 
 def pose_spherical(theta: float, phi: float, radius: float, shift: Optional[Sequence[float]] = None) -> torch.Tensor:

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream
 
 # struct SunerfRegisterFrameDesc (include/sunerf_hip_register.h)
 FRAME_DESC = np.dtype({'names': ['coefficients', 'mask', 'tx', 'ty', 'height', 'width', 'c2w', 'dt', 'shift_y', 'shift_x'],
@@ -65,7 +66,6 @@ def launch(table, n_frames, n_planes, order, c2w_ref, tx_ref, ty_ref, radius, A,
     """``sunerf_register_frames`` on device tensors: ``table`` uint8 [n_frames * 112] (``FRAME_DESC`` rows), ``c2w_ref`` float32 [12],
     ``tx_ref`` [W] and ``ty_ref`` [H] float64.  Returns ``(out [T, C, H, W] float32, status [T, H, W] uint8, coords [T, 2, H, W]
     float64 or None, state [T, 4] int64)``."""
-    from .ops import _ptr, _stream
     dev = table.device
     h, w = int(ty_ref.shape[0]), int(tx_ref.shape[0])
     out = torch.empty((n_frames, n_planes, h, w), dtype=torch.float32, device=dev)

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream
 from .observations import AU_IN_SOLAR_RADII, VIEW_DESC, View, view_descriptors
 
 # struct SunerfObserverDesc (include/sunerf_hip.h)
@@ -95,7 +96,6 @@ def map_rows(views: Sequence[View], lat: torch.Tensor, lon: torch.Tensor, Rs_per
     """Rows ``[row_begin, row_begin + n_rows)`` of the coadd, before the fill (``sunerf_synchronic_map``): ``image``
     (C, n_rows, n_lon) fp32 with NaN where no view covers, ``footprint`` int32 and, with ``want_coords`` (one view only),
     ``coords`` (3, n_rows, n_lon) fp64 = the view's pixel coordinates x, y and the visibility margin ``p . o - R^2``."""
-    from .ops import _ptr, _stream
     n_channels = check_views(views)
     radius = _radius(Rs_per_ds)
     if want_coords and len(views) != 1:
@@ -135,7 +135,6 @@ def fill_map(image: torch.Tensor, fill='mean') -> torch.Tensor:
     """``nan_to_num(image, nan=nanmean(image))`` per channel, in place (``sunerf_map_fill``, reprojection.py:90-92).
     ``fill``: ``'mean'``, None (NaNs stay) or a number.  Returns ``stats`` (C, 2) fp64 on the device: the mean of the non-NaN
     pixels of every channel and their number."""
-    from .ops import _ptr, _stream
     if not image.is_cuda or image.dtype != torch.float32 or not image.is_contiguous() or image.dim() != 3:
         raise _l.SunerfHipError('fill_map: the map must be a contiguous (C, n_lat, n_lon) float32 tensor on a ROCm device')
     if fill is None:
@@ -217,7 +216,6 @@ class SynchronicMap:
         return int(self.image.shape[1]), int(self.image.shape[2])
 
     def _reproject(self, observers: Sequence, off_disk=None, want_coords: bool = False):
-        from .ops import _ptr, _stream
         observers = [_as_observer(o) for o in observers]
         if not observers:
             raise ValueError('no observers')

@@ -15,7 +15,7 @@ import math
 import torch
 
 from . import lib as _l
-from .ops import _dev, _ptr, _stream
+from ._ffi import _dev, _ptr, _stream
 
 STAT_KEYS = ('dssim_coarse', 'dssim_fine', 'n_valid', 'n_invalid')
 MIN_WINDOW, MAX_WINDOW, MAX_PATCH, MAX_CHANNELS = 3, 11, 64, 64

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _ptr, _stream
 from .despike import MODES, _per_plane
 
 REJECTED, INVALID = 1, 2                        # include/sunerf_hip_stack.h
@@ -33,7 +34,6 @@ def launch(frames, bad, params, method, q, rank, mode, flags, n_sigma, iteration
     """``sunerf_stack_combine`` on device tensors: ``frames`` [T, C, H, W] float32, ``bad`` uint8 of that shape or None,
     ``params`` [C, 4] float64.  Returns ``(image, count, mask, state)``: [C, H, W] float32 and uint8, [T, C, H, W] uint8 (None
     without ``with_mask``) and [C, 4] int64."""
-    from .ops import _ptr, _stream
     t, c, h, w = frames.shape
     dev = frames.device
     image = torch.empty((c, h, w), dtype=torch.float32, device=dev)

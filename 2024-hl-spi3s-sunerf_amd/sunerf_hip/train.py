@@ -15,7 +15,7 @@ import torch.distributed as dist
 from torch.utils.weak import WeakIdKeyDictionary
 
 from . import lib as _l
-from .ops import _dev, _ptr, _stream
+from ._ffi import _dev, _ptr, _stream
 
 STAT_KEYS = ('loss', 'coarse', 'fine', 'regularization', 'psnr', 'non_finite')
 _ws = {}      # (device, stream) -> zero-initialised reduction workspace

@@ -18,8 +18,9 @@ import numpy as np
 import torch
 
 from . import lib as _l
+from ._ffi import _dev, _ptr, _stream
 from .maps import _gather_rows, _process_group, column_directions
-from .ops import AIA_WAVELENGTHS, _dev, _ptr, _stream
+from .ops import AIA_WAVELENGTHS
 
 TILE_POINTS = 1 << 22               # default tile: 64 MiB of query points, 32 MiB of answers
 LN10 = 2.302585092994046

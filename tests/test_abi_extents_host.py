@@ -19,7 +19,7 @@ FLOATS = (ctypes.c_float, ctypes.c_double)
 def test_every_exported_symbol_has_a_case_or_a_reason():
     cases, none = set(ac.CASES), set(ac.NO_DEVICE_ACCESS)
     assert not cases & none, sorted(cases & none)
-    exported = set(lib.EXPORTED_SYMBOLS)
+    exported = set(lib.symbols('core'))
     assert cases | none == exported, (sorted(exported - cases - none), sorted((cases | none) - exported))
     assert all(isinstance(r, str) and r for r in ac.NO_DEVICE_ACCESS.values())
     assert all(ac.TILES[name] for name in cases)
@@ -29,7 +29,7 @@ def test_every_exported_symbol_has_a_case_or_a_reason():
 @pytest.mark.parametrize('name', sorted(ac.CASES))
 def test_cases_build_on_the_cpu_with_tagged_sized_arguments(name):
     builder, shapes = ac.CASES[name]
-    argtypes = lib._SIGNATURES[name][1]
+    argtypes = lib.signature(name)[1]
     for shape in shapes:
         case = builder(shape, 'cpu')
         assert case.name == name and len(case.args) == len(argtypes), (shape, len(case.args), len(argtypes))

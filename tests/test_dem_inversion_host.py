@@ -156,7 +156,7 @@ def test_entry_point_is_declared_bound_and_exported(lib):
     header = open(os.path.join(ROOT, 'include', 'sunerf_hip.h')).read()
     declared = set(re.findall(r'\b(sunerf_\w+)\s*\(', header))
     assert 'sunerf_dem_invert' in declared
-    assert 'sunerf_dem_invert' in sunerf_hip.EXPORTED_SYMBOLS
+    assert 'sunerf_dem_invert' in sunerf_hip.symbols('core')
     assert getattr(lib, 'sunerf_dem_invert') is not None
     assert 'DESIGN.md 8k' in header and 'density_temperature.py:237-265' in header
     assert lib.sunerf_abi_version() == 9

@@ -85,12 +85,18 @@ def _untouched(case, before, what, but=()):
 
 @pytest.mark.parametrize('name,shape', PAIRS, ids=[f'{n[7:]}-{ac.shape_id(s)}' for n, s in PAIRS])
 def test_entry_point_stays_inside_its_buffers(name, shape):
+    check_entry_point(ac.CASES[name][0], name, shape)
+
+
+def check_entry_point(builder, name, shape):
+    """The checks of this file's docstring on the case ``builder(shape, device)`` builds for the entry point ``name``; the tables
+    beside the core one (tests/test_gpu_*_abi.py) call it with the builders of their own case tables."""
     if _FAULT:
         pytest.exit(f'a GPU fault ended the session: {_FAULT[0]}', returncode=3)
     assert torch.cuda.is_available(), 'GPU tests need a ROCm device'
     dev = torch.device('cuda', torch.cuda.current_device())
-    builder, _ = ac.CASES[name]
     case = builder(shape, dev)
+    assert case.name == name
     arena = case.arena
     initial = arena.payload_bits(IN, INOUT)
 

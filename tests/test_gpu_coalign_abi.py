@@ -4,9 +4,7 @@ equal to the wrapper by bits and independent of what they and the workspace held
 cases built with ``abi_cases.Ctx`` / ``Case`` and the guarded arena of tests/abi_arena.py, with the extents the header states:
 ``sums`` at ``n_planes (2 max_dy + 1) (2 max_dx + 1) 6`` doubles and the workspace at exactly ``sunerf_coalign_workspace_bytes``.
 
-The cases live in this file's own table ``COALIGN_CASES``: ``abi_cases.CASES`` mirrors ``lib.EXPORTED_SYMBOLS`` and this entry
-point is in ``lib.COALIGN_SYMBOLS``.  A case is put into ``abi_cases.CASES`` only for the time of its own test (``monkeypatch``),
-as tests/test_gpu_despike_abi.py does, so that the checking code is tests/test_gpu_abi_extents.py's."""
+The cases live in this file's own table ``COALIGN_CASES`` (tests/test_abi_tables_host.py holds it to the table's symbols)."""
 import pytest
 import torch
 
@@ -67,8 +65,6 @@ def test_argument_checks_come_in_the_documented_order():
 
 
 @pytest.mark.parametrize('name,shape', PAIRS, ids=[f'{n[7:]}-{ac.shape_id(s)}' for n, s in PAIRS])
-def test_coalign_entry_point_stays_inside_its_buffers(name, shape, monkeypatch):
+def test_coalign_entry_point_stays_inside_its_buffers(name, shape):
     import test_gpu_abi_extents as extents
-    assert name not in ac.CASES
-    monkeypatch.setitem(ac.CASES, name, COALIGN_CASES[name])
-    extents.test_entry_point_stays_inside_its_buffers(name, shape)
+    extents.check_entry_point(COALIGN_CASES[name][0], name, shape)

@@ -5,9 +5,7 @@ cases built with ``abi_cases.Ctx`` / ``Case`` and the guarded arena of tests/abi
 ``clean`` and ``mask`` at the image's shape, ``state`` at 6 doubles per plane, and the workspace at exactly
 ``sunerf_despike_workspace_bytes``.
 
-The cases live in this file's own table ``DESPIKE_CASES``: ``abi_cases.CASES`` mirrors ``lib.EXPORTED_SYMBOLS`` and this entry
-point is in ``lib.DESPIKE_SYMBOLS``.  A case is put into ``abi_cases.CASES`` only for the time of its own test (``monkeypatch``),
-as tests/test_gpu_psf_grad_abi.py does, so that the checking code is tests/test_gpu_abi_extents.py's."""
+The cases live in this file's own table ``DESPIKE_CASES`` (tests/test_abi_tables_host.py holds it to the table's symbols)."""
 import numpy as np
 import pytest
 import torch
@@ -77,8 +75,6 @@ def test_the_planes_of_the_stopping_cases_stop_at_different_passes():
 
 
 @pytest.mark.parametrize('name,shape', PAIRS, ids=[f'{n[7:]}-{ac.shape_id(s)}' for n, s in PAIRS])
-def test_despike_entry_point_stays_inside_its_buffers(name, shape, monkeypatch):
+def test_despike_entry_point_stays_inside_its_buffers(name, shape):
     import test_gpu_abi_extents as extents
-    assert name not in ac.CASES
-    monkeypatch.setitem(ac.CASES, name, DESPIKE_CASES[name])
-    extents.test_entry_point_stays_inside_its_buffers(name, shape)
+    extents.check_entry_point(DESPIKE_CASES[name][0], name, shape)

@@ -3,9 +3,7 @@ tests/test_gpu_abi_extents.py (runs A and B, guards, inputs untouched, outputs e
 what they held, the workspace bound, the empty call) on cases built with ``abi_cases.Ctx`` / ``Case`` / ``HostValue`` and the
 guarded arena of tests/abi_arena.py, with the extents the extension header states.
 
-The cases live in this file's own table ``EXT_CASES``: ``abi_cases.CASES`` mirrors ``lib.EXPORTED_SYMBOLS`` (a host test holds the
-two equal) and these entry points are in ``lib.EXTENSION_SYMBOLS``.  A case is put into ``abi_cases.CASES`` only for the time of
-its own test (``monkeypatch``), so that the checking code is the one of tests/test_gpu_abi_extents.py itself."""
+The cases live in this file's own table ``EXT_CASES`` (tests/test_abi_tables_host.py holds it to the table's symbols)."""
 import pytest
 import torch
 
@@ -135,8 +133,6 @@ PAIRS = [(name, shape) for name, (_, shapes) in EXT_CASES.items() for shape in s
 
 
 @pytest.mark.parametrize('name,shape', PAIRS, ids=[f'{n[7:]}-{ac.shape_id(s)}' for n, s in PAIRS])
-def test_extension_entry_point_stays_inside_its_buffers(name, shape, monkeypatch):
+def test_extension_entry_point_stays_inside_its_buffers(name, shape):
     import test_gpu_abi_extents as extents
-    assert name not in ac.CASES
-    monkeypatch.setitem(ac.CASES, name, EXT_CASES[name])
-    extents.test_entry_point_stays_inside_its_buffers(name, shape)
+    extents.check_entry_point(EXT_CASES[name][0], name, shape)

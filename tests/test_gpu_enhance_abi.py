@@ -6,9 +6,7 @@ extents the header states: MGN's ``out`` at the size of the image, ``lo_out`` / 
 plane, the workspace at ``sunerf_enhance_mgn_workspace_bytes``; the ring tables at ``n_planes n_rings n_segments``; NRGF's ``out`` at
 the size of the image and ``state`` at 3 int64 per plane.
 
-The cases live in this file's own table ``ENHANCE_CASES``: ``abi_cases.CASES`` mirrors ``lib.EXPORTED_SYMBOLS`` and these entry points
-are in ``lib.ENHANCE_SYMBOLS``.  A case is put into ``abi_cases.CASES`` only for the time of its own test (``monkeypatch``), as
-tests/test_gpu_register_abi.py does, so that the checking code is tests/test_gpu_abi_extents.py's."""
+The cases live in this file's own table ``ENHANCE_CASES`` (tests/test_abi_tables_host.py holds it to the table's symbols)."""
 import ctypes
 
 import numpy as np
@@ -147,11 +145,9 @@ def test_argument_checks_come_in_the_documented_order():
 
 
 @pytest.mark.parametrize('name,shape', PAIRS, ids=[f'{n[7:]}-{ac.shape_id(s)}' for n, s in PAIRS])
-def test_enhance_entry_point_stays_inside_its_buffers(name, shape, monkeypatch):
+def test_enhance_entry_point_stays_inside_its_buffers(name, shape):
     import test_gpu_abi_extents as extents
-    assert name not in ac.CASES
-    monkeypatch.setitem(ac.CASES, name, ENHANCE_CASES[name])
-    extents.test_entry_point_stays_inside_its_buffers(name, shape)
+    extents.check_entry_point(ENHANCE_CASES[name][0], name, shape)
     builder, _ = ENHANCE_CASES[name]
     for empty in ({2: 0}, {3: 0}, {4: 0}):          # no plane, no row, no column: nothing to do, nothing written
         case = builder(shape, torch.device('cuda', torch.cuda.current_device()))

@@ -3,9 +3,7 @@ buffers: the checks of tests/test_gpu_abi_extents.py (runs A and B with sentinel
 equal to the wrapper by bits and independent of what they held, the workspace bound, the empty call, the header's rejections) on
 cases built with ``abi_cases.Ctx`` / ``Case`` and the guarded arena of tests/abi_arena.py, with the extents the header states.
 
-The cases live in this file's own table ``LIKELIHOOD_CASES``: ``abi_cases.CASES`` mirrors ``lib.EXPORTED_SYMBOLS`` and this entry
-point is in ``lib.LIKELIHOOD_SYMBOLS``.  A case is put into ``abi_cases.CASES`` only for the time of its own test (``monkeypatch``),
-as tests/test_gpu_patch_abi.py does, so that the checking code is tests/test_gpu_abi_extents.py's."""
+The cases live in this file's own table ``LIKELIHOOD_CASES`` (tests/test_abi_tables_host.py holds it to the table's symbols)."""
 import ctypes
 
 import pytest
@@ -63,8 +61,6 @@ def test_argument_checks_come_in_the_documented_order():
 
 
 @pytest.mark.parametrize('name,shape', PAIRS, ids=[f'{n[7:]}-{ac.shape_id(s)}' for n, s in PAIRS])
-def test_likelihood_entry_point_stays_inside_its_buffers(name, shape, monkeypatch):
+def test_likelihood_entry_point_stays_inside_its_buffers(name, shape):
     import test_gpu_abi_extents as extents
-    assert name not in ac.CASES
-    monkeypatch.setitem(ac.CASES, name, LIKELIHOOD_CASES[name])
-    extents.test_entry_point_stays_inside_its_buffers(name, shape)
+    extents.check_entry_point(LIKELIHOOD_CASES[name][0], name, shape)

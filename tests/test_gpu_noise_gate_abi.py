@@ -4,9 +4,7 @@ equal to the wrapper by bits and independent of what they held, the empty call, 
 ``abi_cases.Ctx`` / ``Case`` and the guarded arena of tests/abi_arena.py, with the extents the header states: ``out`` at the size
 of ``frames``, ``state`` at 4 int64 per plane, ``spectrum`` at ``n_planes bt 256`` floats or NULL; there is no workspace.
 
-The cases live in this file's own table ``NOISE_GATE_CASES``: ``abi_cases.CASES`` mirrors ``lib.EXPORTED_SYMBOLS`` and this entry
-point is in ``lib.NOISE_GATE_SYMBOLS``.  A case is put into ``abi_cases.CASES`` only for the time of its own test (``monkeypatch``),
-as tests/test_gpu_stack_abi.py does, so that the checking code is tests/test_gpu_abi_extents.py's."""
+The cases live in this file's own table ``NOISE_GATE_CASES`` (tests/test_abi_tables_host.py holds it to the table's symbols)."""
 import numpy as np
 import pytest
 import torch
@@ -66,8 +64,6 @@ def test_argument_checks_come_in_the_documented_order():
 
 
 @pytest.mark.parametrize('name,shape', PAIRS, ids=[f'{n[7:]}-{ac.shape_id(s)}' for n, s in PAIRS])
-def test_noise_gate_entry_point_stays_inside_its_buffers(name, shape, monkeypatch):
+def test_noise_gate_entry_point_stays_inside_its_buffers(name, shape):
     import test_gpu_abi_extents as extents
-    assert name not in ac.CASES
-    monkeypatch.setitem(ac.CASES, name, NOISE_GATE_CASES[name])
-    extents.test_entry_point_stays_inside_its_buffers(name, shape)
+    extents.check_entry_point(NOISE_GATE_CASES[name][0], name, shape)

@@ -6,9 +6,7 @@ the header states: ``out`` at ``n_frames n_planes out_height out_width`` floats,
 two doubles or NULL, ``state`` at 4 int64 per frame; per frame ``coefficients`` and ``mask`` at ``n_planes height width``, ``tx`` at
 ``width`` and ``ty`` at ``height``; there is no workspace.
 
-The cases live in this file's own table ``REGISTER_CASES``: ``abi_cases.CASES`` mirrors ``lib.EXPORTED_SYMBOLS`` and this entry point is
-in ``lib.REGISTER_SYMBOLS``.  A case is put into ``abi_cases.CASES`` only for the time of its own test (``monkeypatch``), as
-tests/test_gpu_noise_gate_abi.py does, so that the checking code is tests/test_gpu_abi_extents.py's."""
+The cases live in this file's own table ``REGISTER_CASES`` (tests/test_abi_tables_host.py holds it to the table's symbols)."""
 import numpy as np
 import pytest
 import torch
@@ -82,11 +80,9 @@ def test_argument_checks_come_in_the_documented_order():
 
 
 @pytest.mark.parametrize('name,shape', PAIRS, ids=[f'{n[7:]}-{ac.shape_id(s)}' for n, s in PAIRS])
-def test_register_entry_point_stays_inside_its_buffers(name, shape, monkeypatch):
+def test_register_entry_point_stays_inside_its_buffers(name, shape):
     import test_gpu_abi_extents as extents
-    assert name not in ac.CASES
-    monkeypatch.setitem(ac.CASES, name, REGISTER_CASES[name])
-    extents.test_entry_point_stays_inside_its_buffers(name, shape)
+    extents.check_entry_point(REGISTER_CASES[name][0], name, shape)
     for empty in ({7: 0}, {8: 0}):          # out_height or out_width 0: nothing to do, nothing written
         case = frames(shape, torch.device('cuda', torch.cuda.current_device()))
         case.arena.fill_guards('A')

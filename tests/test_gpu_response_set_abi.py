@@ -3,9 +3,7 @@ tests/test_gpu_abi_extents.py (runs A and B with sentinel and NaN fills, guards,
 by bits and independent of what they held, the empty call) on cases built with ``abi_cases.Ctx`` / ``Case`` and the guarded arena
 of tests/abi_arena.py, with the extents the response-set header states.
 
-The cases live in this file's own table ``RESPONSE_CASES``: ``abi_cases.CASES`` mirrors ``lib.EXPORTED_SYMBOLS`` and these entry
-points are in ``lib.RESPONSE_SYMBOLS``.  A case is put into ``abi_cases.CASES`` only for the time of its own test
-(``monkeypatch``), as tests/test_gpu_dynamic_grid_abi.py does, so that the checking code is tests/test_gpu_abi_extents.py's."""
+The cases live in this file's own table ``RESPONSE_CASES`` (tests/test_abi_tables_host.py holds it to the table's symbols)."""
 import functools
 
 import pytest
@@ -121,8 +119,6 @@ PAIRS = [(name, shape) for name, (_, shapes) in RESPONSE_CASES.items() for shape
 
 
 @pytest.mark.parametrize('name,shape', PAIRS, ids=[f'{n[7:]}-{ac.shape_id(s)}' for n, s in PAIRS])
-def test_response_entry_point_stays_inside_its_buffers(name, shape, monkeypatch):
+def test_response_entry_point_stays_inside_its_buffers(name, shape):
     import test_gpu_abi_extents as extents
-    assert name not in ac.CASES
-    monkeypatch.setitem(ac.CASES, name, RESPONSE_CASES[name])
-    extents.test_entry_point_stays_inside_its_buffers(name, shape)
+    extents.check_entry_point(RESPONSE_CASES[name][0], name, shape)

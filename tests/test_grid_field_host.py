@@ -14,7 +14,7 @@ import torch
 import grid_field_reference as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ('sunerf_grid_field_desc_bytes', 'sunerf_grid_field_fwd', 'sunerf_grid_field_bwd_workspace_bytes',
+ENTRY_POINTS = ('sunerf_grid_field_desc_bytes', 'sunerf_grid_field_fwd', 'sunerf_grid_field_bwd_workspace_bytes',
                'sunerf_grid_field_bwd')
 
 
@@ -282,8 +282,8 @@ def test_entry_points_are_declared_bound_and_exported(lib):
     from sunerf_hip.grid_field import GridFieldDesc
     header = open(os.path.join(ROOT, 'include', 'sunerf_hip.h')).read()
     declared = set(re.findall(r'\b(sunerf_\w+)\s*\(', header))
-    for name in NEW_SYMBOLS:
-        assert name in declared and name in sunerf_hip.EXPORTED_SYMBOLS and getattr(lib, name) is not None, name
+    for name in ENTRY_POINTS:
+        assert name in declared and name in sunerf_hip.symbols('core') and getattr(lib, name) is not None, name
     assert 'mhd_model.py:45-75' in header and 'evaluation/stash/voxel_volume.py' in header
     assert lib.sunerf_abi_version() == 9
     assert lib.sunerf_grid_field_desc_bytes() == ctypes.sizeof(GridFieldDesc)

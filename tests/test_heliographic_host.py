@@ -107,7 +107,7 @@ def test_thomson_is_refused():
 
 def test_exported_symbols():
     import sunerf_hip
-    assert {'sunerf_column_rays', 'sunerf_column_stats'} <= set(sunerf_hip.EXPORTED_SYMBOLS)
+    assert {'sunerf_column_rays', 'sunerf_column_stats'} <= set(sunerf_hip.symbols('core'))
 
 
 def test_loader_axes_and_time(monkeypatch):

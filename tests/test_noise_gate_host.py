@@ -6,7 +6,6 @@ of DESIGN.md 8z, and that no case of tests/test_gpu_noise_gate.py excludes more 
 import ctypes
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
@@ -15,8 +14,6 @@ import torch
 import noise_gate_reference as nr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ('sunerf_noise_gate_abi_version', 'sunerf_noise_gate')
-
 
 @pytest.fixture(scope='session')
 def lib():
@@ -29,33 +26,12 @@ def lib():
 
 # ---- the fourteenth table ---------------------------------------------------------------------------------------------------------
 def test_entry_points_are_declared_and_bound(lib):
-    import hashlib
-
-    import sunerf_hip
-    from sunerf_hip import lib as binding
-    from test_ssim_loss_host import EXPORTED_SHA256, N_EXPORTED
-    read = lambda *p: open(os.path.join(ROOT, *p)).read()          # noqa: E731
-    header = read('include', 'sunerf_hip_noise_gate.h')
-    declared = set(re.findall(r'\b(sunerf_\w+)\s*\(', header))
-    assert declared == set(NEW_SYMBOLS) == set(sunerf_hip.NOISE_GATE_SYMBOLS) == set(binding._NOISE_GATE_SIGNATURES)
-    assert binding.NOISE_GATE_SYMBOLS == tuple(binding._NOISE_GATE_SIGNATURES)
-    taken = (sunerf_hip.EXPORTED_SYMBOLS + sunerf_hip.EXTENSION_SYMBOLS + sunerf_hip.RESPONSE_SYMBOLS + sunerf_hip.PREP_SYMBOLS
-             + sunerf_hip.INSTRUMENT_SYMBOLS + sunerf_hip.PATCH_SYMBOLS + sunerf_hip.LIKELIHOOD_SYMBOLS + sunerf_hip.SSIM_LOSS_SYMBOLS
-             + sunerf_hip.DECONVOLVE_SYMBOLS + sunerf_hip.PSF_GRAD_SYMBOLS + sunerf_hip.DESPIKE_SYMBOLS + sunerf_hip.COALIGN_SYMBOLS
-             + sunerf_hip.STACK_SYMBOLS)
-    for name in NEW_SYMBOLS:
-        fn = getattr(lib, name)
-        assert name not in taken
-        assert fn.restype is binding._NOISE_GATE_SIGNATURES[name][0] and list(fn.argtypes) == binding._NOISE_GATE_SIGNATURES[name][1]
-    assert lib.sunerf_noise_gate_abi_version() == binding.NOISE_GATE_ABI_VERSION == 1
-    assert '#define SUNERF_NOISE_GATE_ABI_VERSION 1' in header
+    """(The table itself -- declared, bound, frozen, versioned, built: tests/test_abi_tables_host.py.)"""
+    header = open(os.path.join(ROOT, 'include', 'sunerf_hip_noise_gate.h')).read()
+    assert lib.sunerf_noise_gate_abi_version() == 1
     for define in ('SUNERF_NOISE_GATE_BLOCK 16', 'SUNERF_NOISE_GATE_STATE 4', 'SUNERF_NOISE_GATE_MODE_GATE 0',
                    'SUNERF_NOISE_GATE_MODE_WIENER 1', 'SUNERF_NOISE_GATE_FILL_INVALID 1'):
         assert f'#define {define}' in header, define
-    assert len(re.findall(r'\bnoise_gate\b', read('2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh'))) == 2
-    assert 'NOISE_GATE_SYMBOLS' in read('__graft_entry__.py')
-    assert len(binding.EXPORTED_SYMBOLS) == N_EXPORTED
-    assert hashlib.sha256('\n'.join(binding.EXPORTED_SYMBOLS).encode()).hexdigest() == EXPORTED_SHA256
     from sunerf_hip import noise_gate as wrapper
     assert wrapper.MODES == {'gate': nr.GATE, 'wiener': nr.WIENER} and wrapper.FILL_INVALID == nr.FILL_INVALID == 1
     assert wrapper.BLOCK_T == nr.BLOCK_T == (1, 4, 8, 16) and wrapper.BLOCK == nr.BLOCK == 16 and wrapper.N_STATE == 4

@@ -203,7 +203,7 @@ def test_entry_point_is_declared_bound_and_exported(lib):
     import sunerf_hip
     header = open(os.path.join(ROOT, 'include', 'sunerf_hip.h')).read()
     for name in ('sunerf_build_ray_pool', 'sunerf_view_desc_bytes'):
-        assert re.search(r'\b' + name + r'\s*\(', header) and name in sunerf_hip.EXPORTED_SYMBOLS
+        assert re.search(r'\b' + name + r'\s*\(', header) and name in sunerf_hip.symbols('core')
         assert getattr(lib, name) is not None
     assert re.search(r'#define\s+SUNERF_ABI_VERSION\s+9\b', header) and lib.sunerf_abi_version() == 9
     from sunerf_hip.observations import VIEW_DESC

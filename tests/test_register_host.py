@@ -6,7 +6,6 @@ and that no case of tests/test_gpu_register.py leaves more than 2 % of its pixel
 import ctypes
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -16,8 +15,6 @@ import prep_reference as pr
 import register_reference as rr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ('sunerf_register_abi_version', 'sunerf_register_frame_desc_bytes', 'sunerf_register_frames')
-
 
 @pytest.fixture(scope='session')
 def lib():
@@ -30,34 +27,13 @@ def lib():
 
 # ---- the fifteenth table ----------------------------------------------------------------------------------------------------------
 def test_entry_points_are_declared_and_bound(lib):
-    import hashlib
-
-    import sunerf_hip
-    from sunerf_hip import lib as binding
-    from test_ssim_loss_host import EXPORTED_SHA256, N_EXPORTED
-    read = lambda *p: open(os.path.join(ROOT, *p)).read()          # noqa: E731
-    header = read('include', 'sunerf_hip_register.h')
-    declared = set(re.findall(r'\b(sunerf_\w+)\s*\(', header))
-    assert declared == set(NEW_SYMBOLS) == set(sunerf_hip.REGISTER_SYMBOLS) == set(binding._REGISTER_SIGNATURES)
-    assert binding.REGISTER_SYMBOLS == tuple(binding._REGISTER_SIGNATURES)
-    taken = (sunerf_hip.EXPORTED_SYMBOLS + sunerf_hip.EXTENSION_SYMBOLS + sunerf_hip.RESPONSE_SYMBOLS + sunerf_hip.PREP_SYMBOLS
-             + sunerf_hip.INSTRUMENT_SYMBOLS + sunerf_hip.PATCH_SYMBOLS + sunerf_hip.LIKELIHOOD_SYMBOLS + sunerf_hip.SSIM_LOSS_SYMBOLS
-             + sunerf_hip.DECONVOLVE_SYMBOLS + sunerf_hip.PSF_GRAD_SYMBOLS + sunerf_hip.DESPIKE_SYMBOLS + sunerf_hip.COALIGN_SYMBOLS
-             + sunerf_hip.STACK_SYMBOLS + sunerf_hip.NOISE_GATE_SYMBOLS)
-    for name in NEW_SYMBOLS:
-        fn = getattr(lib, name)
-        assert name not in taken
-        assert fn.restype is binding._REGISTER_SIGNATURES[name][0] and list(fn.argtypes) == binding._REGISTER_SIGNATURES[name][1]
-    assert lib.sunerf_register_abi_version() == binding.REGISTER_ABI_VERSION == 1
-    assert '#define SUNERF_REGISTER_ABI_VERSION 1' in header
+    """(The table itself -- declared, bound, frozen, versioned, built: tests/test_abi_tables_host.py.)"""
+    header = open(os.path.join(ROOT, 'include', 'sunerf_hip_register.h')).read()
+    assert lib.sunerf_register_abi_version() == 1
     for define in ('SUNERF_REGISTER_TILE 16', 'SUNERF_REGISTER_STATE 4', 'SUNERF_REGISTER_ON_DISK 1', 'SUNERF_REGISTER_OFF_DISK 2',
                    'SUNERF_REGISTER_BEHIND 4', 'SUNERF_REGISTER_OUTSIDE 8', 'SUNERF_REGISTER_OFF_DISK_MISSING 0',
                    'SUNERF_REGISTER_OFF_DISK_CLOSEST 1', 'SUNERF_REGISTER_PROPAGATE 1', 'SUNERF_REGISTER_EDGE_EPS 9.5367431640625e-07'):
         assert f'#define {define}' in header, define
-    assert len(re.findall(r'\bregister(?:;|\.o\b)', read('2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh'))) == 2          # compiled and linked
-    assert 'REGISTER_SYMBOLS' in read('__graft_entry__.py')
-    assert len(binding.EXPORTED_SYMBOLS) == N_EXPORTED
-    assert hashlib.sha256('\n'.join(binding.EXPORTED_SYMBOLS).encode()).hexdigest() == EXPORTED_SHA256
     from sunerf_hip import register as wrapper
     assert lib.sunerf_register_frame_desc_bytes() == wrapper.FRAME_DESC.itemsize == 112
     assert (wrapper.ON_DISK, wrapper.OFF_DISK, wrapper.BEHIND, wrapper.OUTSIDE) == (rr.ON_DISK, rr.OFF_DISK, rr.BEHIND, rr.OUTSIDE) == (1, 2, 4, 8)

@@ -222,22 +222,22 @@ def test_random_cases_leave_out_few_samples():
 
 
 # ----------------------------------------------------------------------------------------------- 6. the entry points
-NEW_SYMBOLS = ('sunerf_synchronic_map', 'sunerf_reproject_views', 'sunerf_map_fill', 'sunerf_map_fill_workspace_bytes',
-               'sunerf_observer_desc_bytes')
+ENTRY_POINTS = ('sunerf_synchronic_map', 'sunerf_reproject_views', 'sunerf_map_fill', 'sunerf_map_fill_workspace_bytes',
+                'sunerf_observer_desc_bytes')
 
 
 def test_entry_points_are_declared_bound_and_exported(lib):
     import sunerf_hip
-    from sunerf_hip.lib import _SIGNATURES
+    from sunerf_hip.lib import signature
     from sunerf_hip.observations import VIEW_DESC
     from sunerf_hip.reprojection import OBSERVER_DESC
     header = open(os.path.join(ROOT, 'include', 'sunerf_hip.h')).read()
-    for name in NEW_SYMBOLS:
+    for name in ENTRY_POINTS:
         declaration = re.search(r'^(?:int|size_t)\s+' + name + r'\s*\(([^;]*)\)\s*;', header, re.M)
-        assert declaration and name in sunerf_hip.EXPORTED_SYMBOLS and getattr(lib, name) is not None, name
+        assert declaration and name in sunerf_hip.symbols('core') and getattr(lib, name) is not None, name
         params = declaration.group(1).strip()
         n_params = 0 if params == 'void' else params.count(',') + 1
-        assert n_params == len(_SIGNATURES[name][1]), (name, n_params, len(_SIGNATURES[name][1]))
+        assert n_params == len(signature(name)[1]), (name, n_params, len(signature(name)[1]))
     assert re.search(r'#define\s+SUNERF_ABI_VERSION\s+9\b', header) and lib.sunerf_abi_version() == 9
     assert lib.sunerf_observer_desc_bytes() == OBSERVER_DESC.itemsize == 80
     assert lib.sunerf_view_desc_bytes() == VIEW_DESC.itemsize == 232          # layout unchanged

@@ -4,7 +4,6 @@ own order statistics and against stacks small enough to check by hand, the inter
 of hits on Poisson and read noise, and the background of a sequence whose moving term leaves every pixel.  Every figure is printed."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,8 +12,6 @@ import torch
 import stack_reference as sr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ('sunerf_stack_abi_version', 'sunerf_stack_combine')
-
 
 @pytest.fixture(scope='session')
 def lib():
@@ -27,33 +24,13 @@ def lib():
 
 # ---- the thirteenth table ---------------------------------------------------------------------------------------------------------
 def test_entry_points_are_declared_and_bound(lib):
-    import hashlib
-
-    import sunerf_hip
-    from sunerf_hip import lib as binding
-    from test_ssim_loss_host import EXPORTED_SHA256, N_EXPORTED
-    read = lambda *p: open(os.path.join(ROOT, *p)).read()          # noqa: E731
-    header = read('include', 'sunerf_hip_stack.h')
-    declared = set(re.findall(r'\b(sunerf_\w+)\s*\(', header))
-    assert declared == set(NEW_SYMBOLS) == set(sunerf_hip.STACK_SYMBOLS) == set(binding._STACK_SIGNATURES)
-    assert binding.STACK_SYMBOLS == tuple(binding._STACK_SIGNATURES)
-    taken = (sunerf_hip.EXPORTED_SYMBOLS + sunerf_hip.EXTENSION_SYMBOLS + sunerf_hip.RESPONSE_SYMBOLS + sunerf_hip.PREP_SYMBOLS
-             + sunerf_hip.INSTRUMENT_SYMBOLS + sunerf_hip.PATCH_SYMBOLS + sunerf_hip.LIKELIHOOD_SYMBOLS + sunerf_hip.SSIM_LOSS_SYMBOLS
-             + sunerf_hip.DECONVOLVE_SYMBOLS + sunerf_hip.PSF_GRAD_SYMBOLS + sunerf_hip.DESPIKE_SYMBOLS + sunerf_hip.COALIGN_SYMBOLS)
-    for name in NEW_SYMBOLS:
-        fn = getattr(lib, name)
-        assert name not in taken
-        assert fn.restype is binding._STACK_SIGNATURES[name][0] and list(fn.argtypes) == binding._STACK_SIGNATURES[name][1]
-    assert lib.sunerf_stack_abi_version() == binding.STACK_ABI_VERSION == 1
-    assert '#define SUNERF_STACK_ABI_VERSION 1' in header
+    """(The table itself -- declared, bound, frozen, versioned, built: tests/test_abi_tables_host.py.)"""
+    header = open(os.path.join(ROOT, 'include', 'sunerf_hip_stack.h')).read()
+    assert lib.sunerf_stack_abi_version() == 1
     for define in ('SUNERF_STACK_MAX_FRAMES 64', 'SUNERF_STACK_MAX_ITERATIONS 16', 'SUNERF_STACK_STATE 4', 'SUNERF_STACK_REJECTED 1',
                    'SUNERF_STACK_INVALID 2', 'SUNERF_STACK_MEAN 0', 'SUNERF_STACK_MEDIAN 1', 'SUNERF_STACK_PERCENTILE 2',
                    'SUNERF_STACK_RANK 3', 'SUNERF_STACK_MODE_MODEL 0', 'SUNERF_STACK_MODE_MAD 1', 'SUNERF_STACK_TWO_SIDED 1'):
         assert f'#define {define}' in header, define
-    assert len(re.findall(r'\bstack\b', read('2024-hl-spi3s-sunerf_amd', 'csrc', 'build.sh'))) == 2
-    assert 'STACK_SYMBOLS' in read('__graft_entry__.py')
-    assert len(binding.EXPORTED_SYMBOLS) == N_EXPORTED
-    assert hashlib.sha256('\n'.join(binding.EXPORTED_SYMBOLS).encode()).hexdigest() == EXPORTED_SHA256
     from sunerf_hip import despike, stack as wrapper
     assert (wrapper.REJECTED, wrapper.INVALID) == (sr.REJECTED, sr.INVALID) == (despike.SPIKE, despike.INVALID) == (1, 2)
     assert wrapper.METHODS == {'mean': sr.MEAN, 'median': sr.MEDIAN, 'percentile': sr.PERCENTILE, 'rank': sr.RANK, 'min': sr.RANK,

@@ -230,7 +230,7 @@ def test_thomson_and_hooked_renderings_name_their_kind():
 
 def test_exported_symbols():
     import sunerf_hip
-    assert {'sunerf_grid_points', 'sunerf_field_quantities', 'sunerf_volume_metrics'} <= set(sunerf_hip.EXPORTED_SYMBOLS)
+    assert {'sunerf_grid_points', 'sunerf_field_quantities', 'sunerf_volume_metrics'} <= set(sunerf_hip.symbols('core'))
 
 
 # ---- loader -----------------------------------------------------------------------------------------------------------------
