@@ -11,6 +11,7 @@
 // column_rays_kernel  : one thread per column; u in fp64, rounded to fp32; 28 bytes written per column.
 // column_stats_kernel : one wave64 per column; reads raw (S, 2) and the shared z row, reduces in fp32.
 #include "sunerf_common.h"
+#include "ray_scan.h"
 #include "../../include/sunerf_hip.h"
 
 namespace {
@@ -49,12 +50,6 @@ struct ColumnStatArgs {
   float* emission; float* absorption;
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(CS_THREADS) void column_stats_kernel(ColumnStatArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t col = (int64_t)blockIdx.x * CS_COLS + (threadIdx.x >> 6);
@@ -78,7 +73,7 @@ __global__ __launch_bounds__(CS_THREADS) void column_stats_kernel(ColumnStatArgs
       a.absorption[o] = 1.f - expf(-fmaxf(raw[2 * j + 1], 0.f) * dr);   // eruption_profile.py:93
     }
   }
-  s_e = wave_sum(s_e); s_re = wave_sum(s_re); s_col = wave_sum(s_col);
+  s_e = sum64(s_e); s_re = sum64(s_re); s_col = sum64(s_col);
   if (lane == 0) {
     a.emission_height[col] = a.height_scale * (s_re / s_e);            // topographical_profile.py:57
     a.emission_column[col] = s_col;

@@ -74,11 +74,7 @@ __global__ __launch_bounds__(DEM_THREADS) void dem_integral_kernel(DemArgs a) {
     const f32x2 rr = *(const f32x2*)(r + 2 * jj);
     const float rho = expf(fmaxf(rr[0] + a.base_rho, 0.f));
     const float logt = fmaxf(rr[1] + a.base_t, 0.f);
-    // trapezoid weight of point j on the grid z[0..S-2]: the missing neighbours of the two ends dropped
-    float q = 0.f;
-    if (jj >= 1) q += zj - zm;
-    if (jj <= S - 3) q += zp - zj;
-    q *= 0.5f;
+    const float q = trapezoid_weight(jj, zm, zj, zp, S);              // of point j on the grid z[0..S-2]
     // t_j = exp(-A_{j+1}), A_{j+1} = A_j + ((ab_{j+1} + ab_j) * (z_{j+1} - z_j)) / 2
     float t = 1.f;
     if (kappa > 0.f) {                                               // (uniform: one scalar for the whole launch)
@@ -90,8 +86,7 @@ __global__ __launch_bounds__(DEM_THREADS) void dem_integral_kernel(DemArgs a) {
     }
     bool inside = valid;
     if (a.masked) {
-      const float px = ox + dx * zj, py = oy + dy * zj, pz = oz + dz * zj;
-      const float rad = sqrtf((px * px + py * py) + pz * pz);
+      const float rad = sample_radius(ox, oy, oz, dx, dy, dz, zj);
       inside = valid && rad >= a.r_in && rad <= a.r_out;              // a NaN radius fails both
     }
     const float v = inside ? q * t * (rho * rho) : 0.f;

@@ -160,12 +160,6 @@ __global__ __launch_bounds__(256) void simple_star_kernel(StarArgs a) {
 constexpr int STAR_BWD_THREADS = 256;
 constexpr int STAR_BWD_MAX_GRID = 1024;
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(STAR_BWD_THREADS) void simple_star_bwd_partial_kernel(StarArgs a, const float* g_raw,
                                                                                     double* partials) {
   const float Rs = a.params[0], h0 = a.params[1], T0 = a.params[2], rho_0 = a.params[3];
@@ -188,7 +182,7 @@ __global__ __launch_bounds__(STAR_BWD_THREADS) void simple_star_bwd_partial_kern
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const double v = wave_sum(acc[k]);
+    const double v = sum64(acc[k]);
     if (lane == 0) red[wave][k] = v;
   }
   __syncthreads();
@@ -212,7 +206,7 @@ __global__ __launch_bounds__(STAR_BWD_THREADS) void simple_star_bwd_finish_kerne
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const double v = wave_sum(acc[k]);
+    const double v = sum64(acc[k]);
     if (lane == 0) red[wave][k] = v;
   }
   __syncthreads();

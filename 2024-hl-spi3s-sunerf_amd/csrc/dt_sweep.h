@@ -10,7 +10,7 @@
 // channels looped inside.  Everything sequential along the ray in the reference -- the running optical depth
 // (cumulative_trapezoid), the trapezoid sum of the attenuated emission and, in the backward pass, the suffix sums of the
 // optical-depth gradients -- is a chunk-wise scan over the 32 lanes with a scalar carry from chunk to chunk, like the
-// emission integral (render_fwd.hip, render_bwd.hip).  (The first version walked the samples with ONE thread per ray and
+// emission integral (emission_sweep.h). (The first version walked the samples with ONE thread per ray and
 // channel: 1.2 ms for the backward of 8192 rays x 256 samples x 7 channels, 10 % of a config-5 training step.)
 //
 // What the two files differ in is a SET POLICY, a struct of static members that each of them defines:
@@ -156,9 +156,7 @@ __device__ __forceinline__ void dt_forward(const typename Set::Args& a, float* l
     a.weights[ray * S + i] = w;
     a.reg_q[ray * S + i] = q;
     if (a.regularization || a.height_map) {
-      const float zi = z[i];
-      const float px = ox + dx * zi, py = oy + dy * zi, pz = oz + dz * zi;
-      const float pd = sqrtf((px * px + py * py) + pz * pz);
+      const float pd = sample_radius(ox, oy, oz, dx, dy, dz, z[i]);
       hm += w * pd;
       if (a.regularization) a.regularization[ray * S + i] = fmaxf(pd - a.reg_radius, 0.f) * fmaxf(q, 0.f);
     }
@@ -222,13 +220,6 @@ __global__ __launch_bounds__(DT_THREADS) void dt_bwd_kernel(typename Set::Args a
   }
   const float ox = a.rays_o[ray * 3 + 0], oy = a.rays_o[ray * 3 + 1], oz = a.rays_o[ray * 3 + 2];
   const float dx = a.rays_d[ray * 3 + 0], dy = a.rays_d[ray * 3 + 1], dz = a.rays_d[ray * 3 + 2];
-  // trapezoid weight of term_j on the grid z[0..S-2]:  wt_j = (dz_{j-1} + dz_j) / 2 with missing neighbours dropped
-  auto wt = [&](int j, float zm, float z0, float zp1) {
-    float w = 0.f;
-    if (j >= 1) w += z0 - zm;
-    if (j <= S - 3) w += zp1 - z0;
-    return 0.5f * w;
-  };
   float inv_denom = 0.f, gw_dot_w = 0.f;
   if (EXTRA && a.g_weights) {
     float sum = 0.f;
@@ -253,7 +244,7 @@ __global__ __launch_bounds__(DT_THREADS) void dt_bwd_kernel(typename Set::Args a
     const f32x2 rr = *(const f32x2*)(r + 2 * kk);
     const float inf0 = rr[0] + a.base_rho, inf1 = rr[1] + a.base_t;
     const float rho = expf(fmaxf(inf0, 0.f)), logt = fmaxf(inf1, 0.f);
-    const float wk = wt(kk, zm, zk, zp1);
+    const float wk = trapezoid_weight(kk, zm, zk, zp1, S);      // of term_k on the grid z[0..S-2]
     // lane 0 also needs dL/dA of the sample below its chunk (k - 1): its term is recomputed here
     const bool below = n == 0 && k >= 1;
     float rho_b = 0.f, logt_b = 0.f, w_b = 0.f;
@@ -261,7 +252,7 @@ __global__ __launch_bounds__(DT_THREADS) void dt_bwd_kernel(typename Set::Args a
       const f32x2 rb = *(const f32x2*)(r + 2 * (k - 1));
       rho_b = expf(fmaxf(rb[0] + a.base_rho, 0.f));
       logt_b = fmaxf(rb[1] + a.base_t, 0.f);
-      w_b = wt(k - 1, z[k >= 2 ? k - 2 : 0], zm, zk);
+      w_b = trapezoid_weight(k - 1, z[k >= 2 ? k - 2 : 0], zm, zk, S);
     }
     float g0 = 0.f, g1 = 0.f;
 #pragma unroll
@@ -298,8 +289,7 @@ __global__ __launch_bounds__(DT_THREADS) void dt_bwd_kernel(typename Set::Args a
       // regularization_k = relu(|p_k| - R) * relu(relu(inf0))
       const float gr = a.g_reg ? a.g_reg[ray * S + k] : 0.f;
       if (gr != 0.f && inf0 > 0.f) {
-        const float px = ox + dx * zk, py = oy + dy * zk, pz = oz + dz * zk;
-        g0 += gr * fmaxf(sqrtf((px * px + py * py) + pz * pz) - a.reg_radius, 0.f);
+        g0 += gr * fmaxf(sample_radius(ox, oy, oz, dx, dy, dz, zk) - a.reg_radius, 0.f);
       }
       if (EXTRA && inf0 > 0.f) {
         if (a.g_reg_q) g0 += a.g_reg_q[ray * S + k];
@@ -322,18 +312,11 @@ __global__ __launch_bounds__(DT_THREADS) void dt_bwd_kernel(typename Set::Args a
   }
   if (n == 0 && g_vol != 0.f) atomicAdd(acc + Set::VOL, g_vol);
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) local_max = fmaxf(local_max, __shfl_xor(local_max, d));
-  if ((tid & 63) == 0) wave_max[tid >> 6] = local_max;
+  batch_max_stage(local_max, wave_max, tid);
   __syncthreads();
   if (tid < Set::n_abs(a) && acc[tid] != 0.f) atomicAdd(a.g_log_abs + tid, acc[tid]);
   if (tid == Set::VOL && acc[Set::VOL] != 0.f) atomicAdd(a.g_vol_c, acc[Set::VOL]);
-  if (tid == 0) {
-    float m = wave_max[0];
-#pragma unroll
-    for (int w = 1; w < DT_THREADS / 64; ++w) m = fmaxf(m, wave_max[w]);
-    if (m > 0.f && m < INFINITY) atomicMax(a.g_absmax_bits, __float_as_uint(m));
-  }
+  batch_max_publish<DT_THREADS / 64>(wave_max, tid, a.g_absmax_bits);
 }
 
 // launches the backward kernel; the entry point has checked the arguments

@@ -1,5 +1,6 @@
 // Weight packing: nn.Linear fp32 parameters -> fp16 hi/lo MFMA A-fragment image (layout: sunerf_common.h).
 #include "sunerf_common.h"
+#include "ray_scan.h"
 #include "../../include/sunerf_hip.h"
 
 namespace {
@@ -33,16 +34,11 @@ __global__ void pack_absmax_kernel(PackArgs a) {
       m = fmaxf(m, fabsf(a.W[l][i]));
   }
   if (l < a.n_linear - 1) m *= 0.15915494309189535f;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));
   // one atomic per workgroup: atomics on one address serialise in L2 (~10 ns each; 2048 of them were the kernel's 20 us)
   __shared__ float wmax[4];
-  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+  batch_max_stage(m, wmax, threadIdx.x);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-    if (m > 0.f && m < INFINITY) atomicMax(absmax + l, __float_as_uint(m));
-  }
+  batch_max_publish<4>(wmax, threadIdx.x, absmax + l);
 }
 
 __device__ __forceinline__ int scale_exponent(unsigned absmax_bits) {

@@ -15,13 +15,15 @@
 // SUNERF_GSCALE_LOG2); the hidden data gradients saturate at +-65504 instead of overflowing.
 #include "sunerf_common.h"
 #include "weight_ring.h"
+#include "emission_sweep.h"
 #include "../../include/sunerf_hip.h"
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------
 // integral backward: 32 lanes per ray, one sample per lane and 32-sample chunk (coalesced reads of raw / z and writes of
-// g_raw; the two sweeps along the ray are chunk-wise scans with a scalar carry, like the forward kernel's integral)
+// g_raw; the two sweeps along the ray are chunk-wise scans with a scalar carry; sweep 1 repeats the arithmetic of the forward
+// integral's step, emission_sweep.h, in its own text)
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int IB_THREADS = 256;                // 8 rays per workgroup
 constexpr int IB_RAYS = IB_THREADS / 32;
@@ -54,6 +56,9 @@ __global__ __launch_bounds__(IB_THREADS) void integral_bwd_kernel(
   const float* r = raw + ray * S * 2;
   const float gi = g_image[ray];
   // ---- sweep 1 (along the ray): emerging_i = I_i * T_i, T the exclusive product of (a + 1e-10) ----
+  // The arithmetic of emission_step() (emission_sweep.h), written out: this kernel keeps its own text, product scan included,
+  // because through the helpers it costs a register and 3 % of its time.  The tests hold both texts to
+  // one oracle (tests/test_gpu_emission_integral.py).
   float carry_T = 1.f, carry_z = 0.f;
   float sum_em = 0.f, dot_gw = 0.f;      // per-lane partial sums (only used with g_weights)
   const float z0 = z[0], z1 = z[1];
@@ -103,12 +108,7 @@ __global__ __launch_bounds__(IB_THREADS) void integral_bwd_kernel(
     // gradient arriving at em_i: the image's (gi) and, when the caller differentiates the weights output too, theirs
     const float ge = g_weights ? gi + (valid ? g_weights[ray * S + i] : 0.f) * inv_den - dot_over_den2 : gi;
     const float wv = g_weights ? ge * em : em;         // (without g_weights: the sums of em itself, scaled by gi afterwards)
-    float incl = wv;                                   // inclusive suffix sum within the chunk
-#pragma unroll
-    for (int d = 1; d < 32; d <<= 1) {
-      const float o = __shfl_down(incl, d, 32);
-      if (n + d < 32) incl += o;
-    }
+    const float incl = scan_down32(wv, n);             // inclusive suffix sum within the chunk
     const float suffix = carry_suffix + (incl - wv);
     carry_suffix += __shfl(incl, 0, 32);
     if (valid && ray_ok) {
@@ -121,10 +121,7 @@ __global__ __launch_bounds__(IB_THREADS) void integral_bwd_kernel(
       // regularization_i = relu(|p_i| - R) (1 - a_i)   (base_tracing.py:43-44, D2 resolved)
       const float gr = g_reg ? g_reg[ray * S + i] : g_reg_const;
       if (gr != 0.f) {
-        const float zi = z[i];
-        const float px = ox + dx * zi, py = oy + dy * zi, pz = oz + dz * zi;
-        const float pd = sqrtf((px * px + py * py) + pz * pz);
-        ga -= gr * fmaxf(pd - reg_radius, 0.f);
+        ga -= gr * fmaxf(sample_radius(ox, oy, oz, dx, dy, dz, z[i]) - reg_radius, 0.f);
       }
       // a = exp(-relu(r1) dist)
       const float g1 = (r1 > 0.f) ? ga * (-dist * a) : 0.f;
@@ -134,23 +131,16 @@ __global__ __launch_bounds__(IB_THREADS) void integral_bwd_kernel(
     }
   }
   }
-  // max |g_raw| of the batch (bit pattern of a non-negative float orders like an unsigned integer)
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) local_max = fmaxf(local_max, __shfl_xor(local_max, d));
+  // max |g_raw| of the batch
   __shared__ float wave_max[IB_THREADS / 64];
-  if ((tid & 63) == 0) wave_max[tid >> 6] = local_max;
+  batch_max_stage(local_max, wave_max, tid);
   __syncthreads();
-  if (tid == 0) {
-    float m = wave_max[0];
-#pragma unroll
-    for (int w = 1; w < IB_THREADS / 64; ++w) m = fmaxf(m, wave_max[w]);
-    if (m > 0.f && m < INFINITY) atomicMax(g_absmax_bits, __float_as_uint(m));
-  }
+  batch_max_publish<IB_THREADS / 64>(wave_max, tid, g_absmax_bits);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // integral forward on a GIVEN raw tensor: EmissionRadiativeTransfer.raw2outputs (emission.py:14-54) as a stand-alone entry
-// point (the render kernel has the same arithmetic fused behind its MLP).  32 lanes per ray, chunk-wise product scan.
+// point (the render kernel calls the same step, emission_sweep.h, behind its MLP).  32 lanes per ray, chunk-wise product scan.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(IB_THREADS) void integral_fwd_kernel(
     const float* __restrict__ raw, const float* __restrict__ z_vals, const float* __restrict__ rays_d, int64_t n_rays, int S,
@@ -163,42 +153,22 @@ __global__ __launch_bounds__(IB_THREADS) void integral_fwd_kernel(
   const float dnorm = sqrtf((dx * dx + dy * dy) + dz * dz);
   const float* z = z_vals + ray * S;
   const float* r = raw + ray * S * 2;
-  float carry_T = 1.f, carry_z = 0.f, sum_em = 0.f;
-  const float z0 = z[0], z1 = z[1];
+  EmissionCarry carry;
+  float sum_em = 0.f;
+  const float first = z[1] - z[0];               // emission.py:19-24: the first distance is duplicated
   for (int c = 0; c < n_chunks; ++c) {
     const int i = 32 * c + n;
     const bool valid = i < S;
     const float zi = z[valid ? i : S - 1];
-    float zprev = __shfl_up(zi, 1, 32);
-    if (n == 0) zprev = carry_z;
-    const float dist = ((i == 0) ? (z1 - z0) : (zi - zprev)) * dnorm;      // emission.py:19-24: first distance duplicated
     const f32x2 rr = *(const f32x2*)(r + 2 * (valid ? i : S - 1));
-    const float a = expf(-fmaxf(rr[1], 0.f) * dist);
-    float pr = valid ? (a + 1e-10f) : 1.f;
-#pragma unroll
-    for (int d = 1; d < 32; d <<= 1) {
-      const float o = __shfl_up(pr, d, 32);
-      if (n >= d) pr *= o;
-    }
-    float excl = __shfl_up(pr, 1, 32);
-    if (n == 0) excl = 1.f;
-    const float em = valid ? expf(rr[0]) * dist * (carry_T * excl) : 0.f;
-    float s = em;
-#pragma unroll
-    for (int d = 16; d >= 1; d >>= 1) s += __shfl_xor(s, d, 32);
-    sum_em += s;
+    const EmissionStep e = emission_step(carry, zi, first, rr[0], rr[1], dnorm, i, n, valid);
+    sum_em += sum32(e.em);
     if (valid) {
-      weights[ray * S + i] = em;                   // un-normalised; finalised below by the same lane
-      absorption[ray * S + i] = a;
+      weights[ray * S + i] = e.em;                 // un-normalised; finalised below by the same lane
+      absorption[ray * S + i] = e.a;
     }
-    carry_T *= __shfl(pr, 31, 32);
-    carry_z = __shfl(zi, 31, 32);
   }
-  const float denom = sum_em + 1e-10f;
-  for (int c = 0; c < n_chunks; ++c) {
-    const int i = 32 * c + n;
-    if (i < S) weights[ray * S + i] = weights[ray * S + i] / denom;
-  }
+  emission_normalise(weights + ray * S, S, n, sum_em + 1e-10f);
   if (n == 0) image[ray] = sum_em;
 }
 
@@ -225,8 +195,6 @@ struct DgradArgs {
   int S;
   int n_linear;
 };
-
-__device__ __forceinline__ float gscale_from_bits(unsigned bits) { return sunerf_gscale(bits); }
 
 __device__ __forceinline__ void pin_agpr(half8& f) { asm volatile("" : "+a"(f)); }
 
@@ -275,7 +243,7 @@ __global__ __launch_bounds__(DG_THREADS, 1) void dgrad_pair_kernel(DgradArgs a) 
   const int n_chunks = (a.S + 31) >> 5;
   const int n_pairs = (n_chunks + 1) >> 1;
   const int64_t n_groups = (a.n_rays + DG_WAVES - 1) / DG_WAVES;
-  const float gscale = gscale_from_bits(*a.g_absmax_bits);
+  const float gscale = sunerf_gscale(*a.g_absmax_bits);
   const char* wT_out = a.packedT;
   const char* wT_hidden = a.packedT + (size_t)NT * 1024;
   const unsigned dz_chunk_bytes = (unsigned)n_act * KS * 1024;
@@ -565,8 +533,7 @@ __global__ __launch_bounds__(1024) void layer_sumsq_kernel(PackTArgs a) {
   } else {
     for (size_t i = threadIdx.x; i < n; i += 1024) acc += a.W[l][i] * a.W[l][i];
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+  acc = sum64(acc);
   __shared__ float part[16];
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
@@ -695,10 +662,7 @@ extern "C" int sunerf_emission_integral_bwd(const float* raw, const float* z_val
 template <int D>
 static int launch_dgrad(const DgradArgs& a, hipStream_t stream) {
   const int64_t n_groups = (a.n_rays + DG_WAVES - 1) / DG_WAVES;
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  cus = sunerf_grid_cap("SUNERF_GRID_CAP_DGRAD", cus);
+  const int cus = sunerf_grid_cap("SUNERF_GRID_CAP_DGRAD", sunerf_cu_count());
   const unsigned grid = (unsigned)(n_groups < cus ? n_groups : cus);
   const size_t lds = (size_t)sunerf_ring::Ring<D>::RING;
   hipError_t e = hipFuncSetAttribute((const void*)dgrad_pair_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

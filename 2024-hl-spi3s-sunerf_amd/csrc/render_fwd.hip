@@ -14,6 +14,7 @@
 //   carry between chunks.
 #include "sunerf_common.h"
 #include "weight_ring.h"
+#include "emission_sweep.h"
 #include "../../include/sunerf_hip.h"
 #include <cstdlib>
 #include <type_traits>
@@ -95,11 +96,6 @@ __device__ __forceinline__ void encode_point(const float v[4], int h, F&& emit /
   for (int c = 0; c < 4; ++c) emit(40 + c, h ? 0.f : v[c]);
 #pragma unroll
   for (int c = 0; c < 4; ++c) emit(44 + c, 0.f);
-}
-
-__device__ __forceinline__ float shfl_up32(float v, int d, int n) {  // within the 32-lane half; n = lane & 31
-  const float o = __shfl_up(v, d, 32);
-  return o;
 }
 
 // Register plan (512 unified registers per lane, one wave per SIMD): the two activation fragment sets (layer input
@@ -971,8 +967,7 @@ __global__ __launch_bounds__(THREADS, 1) void render_fwd_kernel(RenderArgs a) {
     const float dnorm = sqrtf((dx * dx + dy * dy) + dz * dz);   // torch.norm(rays_d), emission.py:26
     const float* zrow = free_points ? nullptr : a.z_vals + ray * S;
 
-    float carry_T = 1.f;      // product of (absorption + 1e-10) over all previous samples of the ray
-    float carry_z = 0.f;      // z of the previous chunk's last sample
+    EmissionCarry ecarry;      // the integral's carry from chunk to chunk (not the MLP layers' `carry`)
     float sum_em = 0.f, sum_abs = 0.f, sum_h = 0.f;
 
     for (int c = 0; c < n_chunks; ++c) {
@@ -1208,25 +1203,9 @@ __global__ __launch_bounds__(THREADS, 1) void render_fwd_kernel(RenderArgs a) {
 
       // ---- emission / absorption integral for this chunk (emission.py:14-54); lanes 0..31 hold rows 0,1 ----
       const float r0 = out[0], r1 = out[1];   // meaningful on h == 0 lanes
-      // dists: z_i - z_{i-1}, first one duplicated (emission.py:21-22)
-      float zprev = __shfl_up(z, 1, 32);
       const float znext = __shfl_down(z, 1, 32);
-      if (n == 0) zprev = carry_z;
-      float dzv = (i == 0) ? (znext - z) : (z - zprev);
-      const float dist = dzv * dnorm;
-      const float inten = expf(r0) * dist;
-      const float absn = expf(-fmaxf(r1, 0.f) * dist);
-      float pr = valid ? (absn + 1e-10f) : 1.f;
-      // inclusive product scan over the 32 lanes of the half
-#pragma unroll
-      for (int d = 1; d < 32; d <<= 1) {
-        const float o = __shfl_up(pr, d, 32);
-        if (n >= d) pr *= o;
-      }
-      float excl = __shfl_up(pr, 1, 32);
-      if (n == 0) excl = 1.f;
-      const float T = carry_T * excl;
-      const float em = valid ? inten * T : 0.f;
+      const EmissionStep e = emission_step(ecarry, z, znext - z, r0, r1, dnorm, i, n, valid);
+      const float em = e.em, absn = e.a;
       const float pdist = sqrtf((px * px + py * py) + pz * pz);   // base_tracing.py:102
       float s_em = em, s_abs = valid ? (1.f - absn) : 0.f, s_h = em * pdist;
 #pragma unroll
@@ -1236,8 +1215,6 @@ __global__ __launch_bounds__(THREADS, 1) void render_fwd_kernel(RenderArgs a) {
         s_h += __shfl_xor(s_h, d, 32);
       }
       sum_em += s_em; sum_abs += s_abs; sum_h += s_h;
-      carry_T *= __shfl(pr, 31, 32);
-      carry_z = __shfl(z, 31, 32);
       if (ray_ok && valid && h == 0) {
         const int64_t o = ray * S + i;
         if (a.weights) {
@@ -1251,10 +1228,7 @@ __global__ __launch_bounds__(THREADS, 1) void render_fwd_kernel(RenderArgs a) {
     // ---- per-ray finalisation: normalise weights (emission.py:49-50), per-ray outputs ----
     if (ray_ok && h == 0 && a.weights) {
       const float denom = sum_em + 1e-10f;
-      for (int c = 0; c < n_chunks; ++c) {
-        const int i = 32 * c + n;
-        if (i < S) { const int64_t o = ray * S + i; a.weights[o] = a.weights[o] / denom; }
-      }
+      emission_normalise(a.weights + ray * S, S, n, denom);
       if (n == 0) {
         a.image[ray] = sum_em;
         if (a.height_map) a.height_map[ray] = sum_h / denom;
@@ -1286,9 +1260,7 @@ int launch_render_t(const RenderArgs& a, hipStream_t stream) {
   hipError_t e = hipFuncSetAttribute((const void*)render_fwd_kernel<D, STASH, FP8C, HALF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
   const int64_t n_groups = (a.n_rays + WAVES - 1) / WAVES;
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  int cus = sunerf_cu_count();
   if (cus > 1024) cus = 1024;   // sunerf_render_workspace_bytes is sized for at most 1024 workgroups
   cus = sunerf_grid_cap("SUNERF_GRID_CAP_FWD", cus);
   const unsigned grid = (unsigned)(n_groups < cus ? n_groups : cus);
@@ -1312,6 +1284,16 @@ int launch_render(const RenderArgs& a, int precision, hipStream_t stream) {
   if (precision == SUNERF_PRECISION_HALF)
     return a.stash ? launch_render_t<D, 1, false, true>(a, stream) : launch_render_t<D, 0, false, true>(a, stream);
   return a.stash ? launch_render_t<D, 1, false>(a, stream) : launch_render_t<D, 0, false>(a, stream);
+}
+// the widths that are built, for both entry points
+int launch_render_width(const RenderArgs& a, int d_filter, int precision, hipStream_t stream) {
+  switch (d_filter) {
+    case 64: return launch_render<64>(a, precision, stream);
+    case 128: return launch_render<128>(a, precision, stream);
+    case 256: return launch_render<256>(a, precision, stream);
+    case 512: return launch_render<512>(a, precision, stream);
+    default: return SUNERF_E_UNSUPPORTED;
+  }
 }
 
 }  // namespace
@@ -1350,13 +1332,7 @@ extern "C" int sunerf_emission_render_fwd(const void* packed, int d_filter, int 
   a.stash_phase = stash_format == SUNERF_STASH_PHASE;
   a.scratch = (char*)workspace;
   if (workspace_bytes < sunerf_render_workspace_bytes(d_filter)) return SUNERF_E_WORKSPACE;
-  switch (d_filter) {
-    case 64: return launch_render<64>(a, precision, (hipStream_t)stream);
-    case 128: return launch_render<128>(a, precision, (hipStream_t)stream);
-    case 256: return launch_render<256>(a, precision, (hipStream_t)stream);
-    case 512: return launch_render<512>(a, precision, (hipStream_t)stream);
-    default: return SUNERF_E_UNSUPPORTED;
-  }
+  return launch_render_width(a, d_filter, precision, (hipStream_t)stream);
 }
 
 extern "C" int sunerf_mlp_points_fwd(const void* packed, int d_filter, int n_linear, int precision, const float* points,
@@ -1376,11 +1352,5 @@ extern "C" int sunerf_mlp_points_fwd(const void* packed, int d_filter, int n_lin
   if (stash_format != SUNERF_STASH_FP16 && stash_format != SUNERF_STASH_PHASE) return SUNERF_E_BADARG;
   a.stash_phase = stash_format == SUNERF_STASH_PHASE;
   if (workspace_bytes < sunerf_render_workspace_bytes(d_filter)) return SUNERF_E_WORKSPACE;
-  switch (d_filter) {
-    case 64: return launch_render<64>(a, precision, (hipStream_t)stream);
-    case 128: return launch_render<128>(a, precision, (hipStream_t)stream);
-    case 256: return launch_render<256>(a, precision, (hipStream_t)stream);
-    case 512: return launch_render<512>(a, precision, (hipStream_t)stream);
-    default: return SUNERF_E_UNSUPPORTED;
-  }
+  return launch_render_width(a, d_filter, precision, (hipStream_t)stream);
 }

@@ -139,6 +139,13 @@ static inline int sunerf_grid_cap(const char* name, int cus) {
   const int v = s ? atoi(s) : 0;
   return (v > 0 && v < cus) ? v : cus;
 }
+// compute units of the current device: what the persistent kernels size their grids by (256 if the query fails)
+static inline int sunerf_cu_count() {
+  int dev = 0, cus = 256;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  return cus;
+}
 #define SUNERF_CLEAR_ERROR() (void)hipGetLastError()
 #define SUNERF_CHECK_LAUNCH()                         \
   do {                                                \

@@ -250,16 +250,9 @@ __global__ __launch_bounds__(TH_THREADS) void thomson_integral_bwd_kernel(Thomso
       local_max = fmaxf(local_max, fabsf(g0));
     }
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) local_max = fmaxf(local_max, __shfl_xor(local_max, d));
-  if ((tid & 63) == 0) wave_max[tid >> 6] = local_max;
+  batch_max_stage(local_max, wave_max, tid);
   __syncthreads();
-  if (tid == 0 && a.g_absmax_bits) {
-    float m = wave_max[0];
-#pragma unroll
-    for (int w = 1; w < TH_THREADS / 64; ++w) m = fmaxf(m, wave_max[w]);
-    if (m > 0.f && m < INFINITY) atomicMax(a.g_absmax_bits, __float_as_uint(m));
-  }
+  if (a.g_absmax_bits) batch_max_publish<TH_THREADS / 64>(wave_max, tid, a.g_absmax_bits);   // (null: the caller wants no maximum)
 }
 
 int check_inputs(const ThomsonArgs& a) {

@@ -10,6 +10,7 @@
 // results do not depend on scheduling.  ~4 bytes of HBM traffic per element and pass; the kernels are launched with a
 // fixed grid of at most TS_BLOCKS workgroups and stride over their input.
 #include "sunerf_common.h"
+#include "ray_scan.h"
 #include "../../include/sunerf_hip.h"
 
 namespace {
@@ -26,8 +27,7 @@ struct Workspace {
 };
 
 __device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  v = sum64(v);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   __syncthreads();   // sh may still be read by a previous call
   if (lane == 0) sh[wave] = v;

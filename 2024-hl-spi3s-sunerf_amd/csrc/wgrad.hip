@@ -31,8 +31,6 @@ struct WgradArgs {
   int lds_bytes;
 };
 
-__device__ __forceinline__ float gscale_from_bits(unsigned bits) { return sunerf_gscale(bits); }
-
 constexpr int NBUF = 4;   // LDS ring of chunk buffers (3 chunks of HBM latency cover)
 
 // KIND: 0 = in layer (X = encoding, 6 fragments), 1 = hidden layer, 2 = out layer (dZ built from g_raw)
@@ -60,7 +58,7 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, char* smem, int l
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n_act = a.n_linear - 1;
   const size_t dz_chunk_bytes = (size_t)n_act * KSF * 1024;
-  const float gscale = gscale_from_bits(*a.g_absmax_bits);
+  const float gscale = sunerf_gscale(*a.g_absmax_bits);
   const unsigned lds0 = (unsigned)(uintptr_t)smem;
   const unsigned dummy = lds0 + NBUF * BUF;
 

@@ -1,6 +1,8 @@
 """Emission / absorption integral kernels against ``sunerf_oracle.emission_outputs`` evaluated in float64 on the same fp32 inputs:
-the stand-alone forward and backward (csrc/render_bwd.hip: sunerf_emission_integral_fwd / _bwd) and the copy fused behind the
+the stand-alone forward and backward (csrc/render_bwd.hip: sunerf_emission_integral_fwd / _bwd) and the epilogue fused behind the
 MLP in the render kernel (csrc/render_fwd.hip), at the shapes where the kernels branch and in the regimes where fp32 runs out.
+The two forwards take the integral's per-chunk step from one text, csrc/emission_sweep.h (``test_fused_integral_is_the_stand_alone_integral``);
+sweep 1 of the backward keeps the same arithmetic in its own text.
 
 The kernels give a ray 32 lanes that walk its samples in chunks of 32; the transmittance, the previous z and the backward's
 suffix sum cross a chunk seam through a scalar carry, and the g_weights path reduces sum(em) and sum(g_weights em) over all
@@ -512,7 +514,7 @@ def test_emission_integral_nan_row(ops):
     assert bool(torch.isnan(f[0][4]).all())
 
 
-# ---- the fused copy behind the MLP ----------------------------------------------------------------------------------------
+# ---- the integral fused behind the MLP ----------------------------------------------------------------------------------------
 # out-layer (weight scale, bias r0, bias r1): raw ~ bias + small, driving the integral into the regimes above
 OUT_LAYERS = ((0.5, 0.0, -1.0), (0.3, 1.0, 0.0), (0.5, 0.5, 3.0), (1.0, -35.0, 30.0), (1.0, 2.0, 300.0), (0.3, 40.0, 3.0))
 
@@ -581,6 +583,21 @@ def test_fused_integral_width_512(ops, precision):
     for seed in (60, 63, 64):
         c, packed, t = fused_case(ops, 512, 2, 9, 40, p, seed)
         check_fused(ops, c, packed, t)
+
+
+def test_fused_integral_is_the_stand_alone_integral(ops):
+    """One text (csrc/emission_sweep.h): the render kernel's image, weights and absorption are, bit for bit, the stand-alone
+    forward applied to the raw the same call returned.  Width 64, EXACT, N = 9, one chunk, a partial one and both sides of a
+    seam, every out-layer regime at each S."""
+    for s in (2, 31, 33, 65):
+        for seed in range(FUSED_S.index(s) * 6, FUSED_S.index(s) * 6 + 6):
+            c, packed, t = fused_case(ops, 64, 2, 9, s, ops.PRECISION_EXACT, seed)
+            out = ops.emission_render_fwd(packed, c['o'].cuda(), c['d'].cuda(), t.cuda(), c['z'].cuda(), REG_RADIUS, want_raw=True)
+            alone = ops.emission_integral_fwd(out['raw'], c['z'].cuda(), c['d'].cuda())
+            torch.cuda.synchronize()
+            assert bool(torch.isfinite(out['raw']).all())
+            for k, want in zip(('image', 'weights', 'absorption'), alone):
+                assert torch.equal(out[k], want), (k, s, seed, (out[k] - want).abs().max().item())
 
 
 @pytest.mark.parametrize('cap', [1, 3])
