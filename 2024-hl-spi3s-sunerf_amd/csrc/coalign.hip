@@ -11,7 +11,7 @@
 //    broadcast).  When the chunk needs fewer than 256 threads, the 256 / G groups each take a SLICE of the tile's template pixels,
 //    as in psf_grad.hip.  A workgroup keeps its sums over a RUN of tiles of one plane -- the run is fixed by the arguments -- then
 //    adds the slices of each sum through LDS, slice 0 first, and writes one fp64 partial per sum, shift and run to the workspace.
-// 2. the FINAL kernel: one thread per sum adds its partials, run 0 first.
+// 2. the FINAL kernel (corr_bin.h's run_sum_final_kernel, shared with psf_grad.hip): one thread per sum adds its partials, run 0 first.
 //
 // The tile geometry (CorrBinArgs with kh = 2 max_dy + 1, kw = 2 max_dx + 1, bin 1, the anchor in the middle), the thread count and
 // the LDS opt-in are corr_bin.h's.  No floating-point atomics; -ffp-contract=off and no explicit fma: every operation is rounded on
@@ -181,20 +181,6 @@ __global__ __launch_bounds__(CB_THREADS) void coalign_partial_kernel(const float
   }
 }
 
-constexpr int CA_FINAL_THREADS = 256;
-
-__global__ __launch_bounds__(CA_FINAL_THREADS) void coalign_final_kernel(const double* __restrict__ partials, double* __restrict__ out,
-                                                                         int n_runs, int64_t per_plane, int64_t total) {
-  for (int64_t idx = (int64_t)blockIdx.x * CA_FINAL_THREADS + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * CA_FINAL_THREADS) {
-    const int64_t plane = idx / per_plane;
-    const double* src = partials + plane * n_runs * per_plane + (idx - plane * per_plane);
-    double s = src[0];
-#pragma unroll 16
-    for (int r = 1; r < n_runs; ++r) s = s + src[(int64_t)r * per_plane];      // unrolled: sixteen loads in flight, the adds in order
-    out[idx] = s;
-  }
-}
-
 int launch(const float* image, const float* templ, const uint8_t* bad_image, const uint8_t* bad_templ, double* out, double* partials,
            const CorrBinArgs& a, const CoalignPlan& p, hipStream_t st) {
   const size_t lds = coalign_lds_bytes(a, p);
@@ -216,8 +202,7 @@ int launch(const float* image, const float* templ, const uint8_t* bad_image, con
   }
 #undef CA_PARTIAL
   const int64_t per_plane = (int64_t)p.shifts * CA_SUMS, total = a.n_planes * per_plane;
-  hipLaunchKernelGGL(coalign_final_kernel, dim3(grid_of((total + CA_FINAL_THREADS - 1) / CA_FINAL_THREADS)), dim3(CA_FINAL_THREADS), 0, st,
-                     (const double*)partials, out, p.n_runs, per_plane, total);
+  launch_run_sum_final<false>(partials, out, p.n_runs, per_plane, total, 1.0, st);
   SUNERF_CHECK_LAUNCH();
   return 0;
 }

@@ -343,3 +343,28 @@ __device__ __forceinline__ void adjoint_sum_tile(const AdjointLds& L, const Adjo
     }
   }
 }
+
+// ---- the finish of a sum kept over runs (coalign.hip, psf_grad.hip) -------------------------------------------------------------
+// partials [group][run][per_group] -> out [group][per_group] = run 0 + run 1 + ..., one thread per output, the runs in run order;
+// SCALED: times scale.  (A template, so that the files that include this header and launch no finish get no kernel from it.)
+constexpr int CB_FINAL_THREADS = 256;
+
+template <bool SCALED>
+__global__ __launch_bounds__(CB_FINAL_THREADS) void run_sum_final_kernel(const double* __restrict__ partials, double* __restrict__ out,
+                                                                         int n_runs, int64_t per_group, int64_t total, double scale) {
+  for (int64_t idx = (int64_t)blockIdx.x * CB_FINAL_THREADS + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * CB_FINAL_THREADS) {
+    const int64_t group = idx / per_group;
+    const double* src = partials + group * n_runs * per_group + (idx - group * per_group);
+    double s = src[0];
+#pragma unroll 16
+    for (int r = 1; r < n_runs; ++r) s = s + src[(int64_t)r * per_group];      // unrolled: sixteen loads in flight, the adds in order
+    out[idx] = SCALED ? scale * s : s;
+  }
+}
+
+template <bool SCALED>
+static inline void launch_run_sum_final(const double* partials, double* out, int n_runs, int64_t per_group, int64_t total, double scale,
+                                        hipStream_t st) {
+  hipLaunchKernelGGL(run_sum_final_kernel<SCALED>, dim3(grid_of((total + CB_FINAL_THREADS - 1) / CB_FINAL_THREADS)), dim3(CB_FINAL_THREADS), 0, st,
+                     partials, out, n_runs, per_group, total, scale);
+}

@@ -3,8 +3,9 @@
 //
 // 1. the RATIO kernel: the strided correlation of instrument.hip (same tile rule, LDS staging, boundary handling, taps by scalar
 //    load, up to four outputs per thread) whose epilogue keeps the fp64 sum, forms ratio = (d + off) / (A u + off) and the
-//    pixel's term of the Poisson deviance, and reduces the terms of the tile in a fixed order (a butterfly inside each wave, the
-//    four waves in index order) into ONE partial per tile, indexed by the tile's number: the sum does not depend on the grid;
+//    pixel's term of the Poisson deviance, and reduces the terms of the tile in a fixed order (sum64's order inside each
+//    wave, then ordered_sum.h's wave-order stage) into ONE partial per tile, indexed by the tile's number: the sum does not depend on
+//    the grid;
 // 2. the CONTROL kernel: one workgroup per plane adds the plane's partials in a fixed order, writes the plane's state and decides
 //    whether the plane stops -- on the device, so that the host never waits between iterations;
 // 3. the UPDATE kernel: the gather-form adjoint of patch.hip (same tiles of 32 x 32 input pixels, LDS layout and order of
@@ -14,6 +15,7 @@
 // instrument.hip and patch.hip: the kernels here are their loops over tiles, the stopped-plane test and the epilogues.
 // No floating-point atomics; -ffp-contract=off and no explicit fma: every operation is rounded on its own, as the header says.
 #include "corr_bin.h"
+#include "ordered_sum.h"
 #include "../../include/sunerf_hip_deconvolve.h"
 
 namespace {
@@ -67,25 +69,19 @@ __global__ __launch_bounds__(CB_THREADS) void deconvolve_ratio_kernel(const floa
         if (valid) count = count + 1.0;
       }
     }
+    // sum64's order for both values, in ONE loop: two sum64 calls compile to two shuffle chains one after the other, which cost
+    // 1 % of an iteration; here a level's shuffles of both values are in flight together
 #pragma unroll
-    for (int step = 32; step >= 1; step >>= 1) {          // every lane ends with the wave's sum, formed in one order
+    for (int step = 32; step >= 1; step >>= 1) {
       dev = dev + __shfl_xor(dev, step);
       count = count + __shfl_xor(count, step);
     }
-    if ((t & 63) == 0) {
-      wave_sum[2 * (t >> 6)] = dev;
-      wave_sum[2 * (t >> 6) + 1] = count;
-    }
+    const double totals[2] = {dev, count};
+    park_wave_totals(totals, wave_sum);
     __syncthreads();
     if (t == 0) {
-      double s = wave_sum[0], n = wave_sum[1];
-#pragma unroll
-      for (int w = 1; w < RL_WAVES; ++w) {
-        s = s + wave_sum[2 * w];
-        n = n + wave_sum[2 * w + 1];
-      }
-      partials[2 * tile_id] = s;
-      partials[2 * tile_id + 1] = n;
+      partials[2 * tile_id] = sum_in_wave_order<RL_WAVES, 2>(wave_sum, 0);
+      partials[2 * tile_id + 1] = sum_in_wave_order<RL_WAVES, 2>(wave_sum, 1);
     }
     __syncthreads();                             // the tile and the waves' sums are overwritten by the next tile
   }
@@ -104,18 +100,11 @@ __global__ __launch_bounds__(CB_THREADS) void deconvolve_control_kernel(const do
     s = s + p[2 * i];
     n = n + p[2 * i + 1];
   }
-  sum[2 * t] = s;
-  sum[2 * t + 1] = n;
-  for (int half = CB_THREADS / 2; half >= 1; half >>= 1) {
-    __syncthreads();
-    if (t < half) {
-      sum[2 * t] = sum[2 * t] + sum[2 * (t + half)];
-      sum[2 * t + 1] = sum[2 * t + 1] + sum[2 * (t + half) + 1];
-    }
-  }
+  const double v[2] = {s, n};
+  lds_tree<CB_THREADS>(sum, v, add_values());          // (run once, on an array of its own: no barrier of the caller's)
   if (t == 0) {
     double* st = state + plane * SUNERF_DECONVOLVE_STATE;
-    const double deviance = sum[0], n_valid = sum[1];
+    const double deviance = sum[0], n_valid = sum[CB_THREADS];
     double applied = pass > 0 ? st[2] : 0.0;
     const bool stopped = stop > 0.0 && deviance <= stop * n_valid;
     if (!stopped && !last) applied = applied + 1.0;          // the update that follows this pass

@@ -16,7 +16,8 @@
 // The integral itself (layout, sweeps, kernel bodies, backward launcher) is dt_sweep.h, shared with dt_response_set.hip; this
 // file holds the AIA set policy -- the seven rows of dt_response.h -- the forward kernel and the entry points.
 #include "dt_sweep.h"
-#include "dt_response.h"      // NCH, NTAB, channel_of(), response(): shared with volume.hip
+#include "ordered_sum.h"
+#include "dt_response.h"     // NCH, NTAB, channel_of(), response(): shared with volume.hip
 
 namespace {
 
@@ -159,6 +160,15 @@ __global__ __launch_bounds__(256) void simple_star_kernel(StarArgs a) {
 // result does not depend on scheduling, and the grid depends on N*S only.
 constexpr int STAR_BWD_THREADS = 256;
 constexpr int STAR_BWD_MAX_GRID = 1024;
+constexpr int STAR_BWD_WAVES = STAR_BWD_THREADS / 64;
+
+// the four sums of every wave by sum64, parked for ordered_sum.h's wave-order stage (one barrier for all four: the caller's)
+__device__ __forceinline__ void star_park_totals(const double (&acc)[4], double* red) {
+  double totals[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) totals[k] = sum64(acc[k]);
+  park_wave_totals(totals, red);
+}
 
 __global__ __launch_bounds__(STAR_BWD_THREADS) void simple_star_bwd_partial_kernel(StarArgs a, const float* g_raw,
                                                                                     double* partials) {
@@ -178,20 +188,10 @@ __global__ __launch_bounds__(STAR_BWD_THREADS) void simple_star_bwd_partial_kern
       else acc[3] += g[1];
     }
   }
-  __shared__ double red[STAR_BWD_THREADS / 64][4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double v = sum64(acc[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
+  __shared__ double red[STAR_BWD_WAVES * 4];
+  star_park_totals(acc, red);
   __syncthreads();
-  if (threadIdx.x < 4) {
-    double v = 0.;
-#pragma unroll
-    for (int w = 0; w < STAR_BWD_THREADS / 64; ++w) v += red[w][threadIdx.x];
-    partials[(size_t)blockIdx.x * 4 + threadIdx.x] = v;
-  }
+  if (threadIdx.x < 4) partials[(size_t)blockIdx.x * 4 + threadIdx.x] = sum_in_wave_order<STAR_BWD_WAVES, 4>(red, threadIdx.x);
 }
 
 __global__ __launch_bounds__(STAR_BWD_THREADS) void simple_star_bwd_finish_kernel(StarArgs a, const double* partials,
@@ -202,21 +202,13 @@ __global__ __launch_bounds__(STAR_BWD_THREADS) void simple_star_bwd_finish_kerne
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[k] += partials[(size_t)b * 4 + k];
   }
-  __shared__ double red[STAR_BWD_THREADS / 64][4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double v = sum64(acc[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
+  __shared__ double red[STAR_BWD_WAVES * 4];
+  star_park_totals(acc, red);
   __syncthreads();
   if (threadIdx.x != 0) return;
   double S[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    S[k] = 0.;
-    for (int w = 0; w < STAR_BWD_THREADS / 64; ++w) S[k] += red[w][k];
-  }
+  for (int k = 0; k < 4; ++k) S[k] = sum_in_wave_order<STAR_BWD_WAVES, 4>(red, k);
   const double Rs = a.params[0], h0 = a.params[1], T0 = a.params[2], rho_0 = a.params[3], tph = a.t_photosphere;
   const double ln10 = 2.302585092994045684;
   // the ramp sums vanish when no sample lies on it: no 0 / 0 for Rs == 1

@@ -17,6 +17,7 @@
 //   nrgf_apply_kernel    one lane per pixel, its ring by bisection on edges^2
 // No floating-point atomics; every sum has an order fixed by the shape.
 #include "sunerf_common.h"
+#include "ordered_sum.h"
 #include "../../include/sunerf_hip.h"
 #include "../../include/sunerf_hip_enhance.h"
 
@@ -254,16 +255,13 @@ __device__ __forceinline__ void ring_rows(const RadialArgs& a, double e1, int& y
   if (!(a.cy - e1 - 2. <= (double)(a.H - 1)) || !(a.cy + e1 + 2. >= 0.)) { y0 = 1; y1 = 0; }
 }
 
+// one value over the workgroup by ordered_sum.h's halving tree, the result in every thread
 template <typename T, typename F>
-__device__ __forceinline__ T block_reduce(T v, T* red, int t, F f) {
-  red[t] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) red[t] = f(red[t], red[t + s]);
-    __syncthreads();
-  }
+__device__ __forceinline__ T block_reduce(T v, T* red, F f) {
+  const T one[1] = {v};
+  lds_tree<256>(red, one, f);
   const T r = red[0];
-  __syncthreads();
+  __syncthreads();          // the next call overwrites red[0]: every thread has read it
   return r;
 }
 
@@ -299,14 +297,14 @@ __global__ __launch_bounds__(256) void ring_statistics_kernel(RadialArgs a) {
       }
     }
     if (pass == 0) {
-      cnt = block_reduce(cnt, reinterpret_cast<unsigned long long*>(red), t, [](unsigned long long x, unsigned long long y) { return x + y; });
-      sum = block_reduce(sum, red, t, [](double x, double y) { return x + y; });
-      mn = block_reduce(mn, red, t, [](double x, double y) { return fmin(x, y); });
-      mx = block_reduce(mx, red, t, [](double x, double y) { return fmax(x, y); });
+      cnt = block_reduce(cnt, reinterpret_cast<unsigned long long*>(red), add_values());
+      sum = block_reduce(sum, red, add_values());
+      mn = block_reduce(mn, red, [](int, double x, double y) { return fmin(x, y); });
+      mx = block_reduce(mx, red, [](int, double x, double y) { return fmax(x, y); });
       mean = sum / (double)cnt;
       if (cnt == 0ull) break;
     } else {
-      ss = block_reduce(ss, red, t, [](double x, double y) { return x + y; });
+      ss = block_reduce(ss, red, add_values());
     }
   }
   if (t == 0) {
@@ -445,7 +443,6 @@ __global__ __launch_bounds__(256) void nrgf_apply_kernel(NrgfArgs a) {
   if (t < SUNERF_ENHANCE_NRGF_STATE && tally[t]) atomicAdd(a.state + (int64_t)p * SUNERF_ENHANCE_NRGF_STATE + t, (unsigned long long)tally[t]);
 }
 
-inline bool is_finite(double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; }
 inline bool coordinate_ok(double v) { return v >= -1073741824. && v <= 1073741824.; }      // false for NaN
 inline size_t align_up(size_t n, size_t a) { return (n + a - 1) / a * a; }
 inline size_t params_bytes(int n_planes) { return align_up((size_t)n_planes * sizeof(PlaneParams), 256); }

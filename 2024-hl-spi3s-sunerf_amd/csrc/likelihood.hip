@@ -6,11 +6,12 @@
 //
 // Reductions.  A ray's codes row may differ from its neighbour's (an ObservationSet mixes instruments), so the lanes of a wave hold
 // different table rows.  Per sweep a wave walks the distinct rows its lanes hold (ballot on row == row of the first lane not yet
-// served), reduces the four sums of the matching lanes with one fixed tree (the others add +0.0), and lane 0 adds the result to
-// the wave's own fp64 [row][4] array in LDS.  A workgroup adds its waves' arrays in wave order and writes [row][5] partials to
-// the workspace; the workgroup that takes the last ticket adds the partials in block order (groups of 8, then the groups).  No
-// floating-point atomics: the order of every addition is fixed by (n, grid) and by the data, so reruns give the same bits.
+// served), reduces the four sums of the matching lanes with one fixed tree (ordered_sum.h's sum64_dpp; the others add +0.0), and
+// lane 0 adds the result to the wave's own fp64 [row][4] array in LDS.  A workgroup adds its waves' arrays in wave order and
+// writes [row][5] partials to the workspace; the workgroup that takes the last ticket (ordered_sum.h) adds the partials in block
+// order (groups of 8, then the groups).  The order of every addition is fixed by (n, grid) and by the data.
 #include "sunerf_common.h"
+#include "ordered_sum.h"
 #include "../../include/sunerf_hip_likelihood.h"
 
 namespace {
@@ -25,7 +26,7 @@ constexpr int LK_SCALARS = 3;       // non-finite count, unknown-code count, reg
 constexpr int LK_GROUP = 8;         // the last workgroup adds the partials of 8 workgroups per work item, then the 16 groups
 constexpr int LK_GROUPS = LK_BLOCKS / LK_GROUP;
 
-// workspace: [0] ticket (unsigned), then from byte 64: LK_BLOCKS x (5 n_rows + 3) doubles of block partials
+// workspace (ordered_sum.h's Ticket): LK_BLOCKS x (5 n_rows + 3) doubles of block partials
 __host__ __device__ inline size_t partial_stride(int n_rows) { return (size_t)LK_ROW_SUMS * n_rows + LK_SCALARS; }
 
 struct Args {
@@ -42,38 +43,10 @@ struct Args {
   void* workspace;
 };
 
-// One level of the wave tree as a data-parallel move (no trip through the LDS crossbar): every lane reads its partner of CTRL.
-template <int CTRL>
-__device__ __forceinline__ double dpp_partner(double v) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, false);
-  return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo);
-}
-
-// The sum of a value over the 64 lanes, in every lane, by one fixed tree: partners 1 and 2 lanes apart (quad permutes), the other
-// quad of the group of 8 (row_half_mirror), the other half of the row of 16 (row_mirror), then the rows 16 and 32 lanes apart.
-// Both partners of a level add the same two numbers, so all lanes of a group hold the same bits.  Needs every lane active.
-__device__ __forceinline__ double wave_sum(double v) {
-  v += dpp_partner<0xB1>(v);       // quad_perm [1, 0, 3, 2]
-  v += dpp_partner<0x4E>(v);       // quad_perm [2, 3, 0, 1]
-  v += dpp_partner<0x141>(v);      // row_half_mirror
-  v += dpp_partner<0x140>(v);      // row_mirror
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
-
 __device__ __forceinline__ double block_sum(double v, double* sh) {
-  v = wave_sum(v);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  v = sum64_dpp(v);
   __syncthreads();   // sh may still be read by a previous call
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < LK_WAVES; ++w) t += sh[w];
-  return t;
+  return wave_order_sum<LK_WAVES>(v, sh);
 }
 
 // the term of one prediction p against the target t and its derivative with respect to m = g p
@@ -165,8 +138,8 @@ __global__ __launch_bounds__(LK_THREADS) void likelihood_kernel(Args a) {
       const int r = __shfl(row, leader);
       const bool mine = row == r;
       const unsigned long long match = __ballot(mine);
-      const double s0 = wave_sum(mine ? tc : 0.0), s1 = wave_sum(mine ? tf : 0.0), s2 = wave_sum(mine ? sq : 0.0),
-                   s3 = wave_sum(mine ? gl : 0.0);
+      const double s0 = sum64_dpp(mine ? tc : 0.0), s1 = sum64_dpp(mine ? tf : 0.0), s2 = sum64_dpp(mine ? sq : 0.0),
+                   s3 = sum64_dpp(mine ? gl : 0.0);
       if (lane == 0) {
         double* p = acc[wave][r];
         p[0] += s0; p[1] += s1; p[2] += s2; p[3] += s3;
@@ -183,11 +156,10 @@ __global__ __launch_bounds__(LK_THREADS) void likelihood_kernel(Args a) {
   for (int k = 0; k < a.n_extra; ++k)
     for (int64_t i = tid; i < a.extra_n[k]; i += stride) bad += (double)!isfinite(a.extra[k][i]);
 
-  unsigned* ticket = (unsigned*)a.workspace;
-  double* partial = (double*)((char*)a.workspace + 64);
+  const Ticket ws(a.workspace);
   const size_t ps = partial_stride(M);
   const double b0 = block_sum(bad, sh), b1 = block_sum(unknown, sh), b2 = block_sum(sum_r, sh);      // (their barriers order acc too)
-  double* mine = partial + (size_t)blockIdx.x * ps;
+  double* mine = ws.partial + (size_t)blockIdx.x * ps;
   for (int j = threadIdx.x; j < M * LK_ROW_SUMS; j += LK_THREADS) {
     const int r = j / LK_ROW_SUMS, k = j - r * LK_ROW_SUMS;
     double s = 0.0;
@@ -204,20 +176,13 @@ __global__ __launch_bounds__(LK_THREADS) void likelihood_kernel(Args a) {
     mine[M * LK_ROW_SUMS + 0] = b0; mine[M * LK_ROW_SUMS + 1] = b1; mine[M * LK_ROW_SUMS + 2] = b2;
   }
 
-  // exactly one workgroup, the one that finishes last, sees every partial
-  __shared__ unsigned last;
-  __threadfence();
-  __syncthreads();
-  if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
+  if (!last_block(ws.ticket)) return;
   // every sum in block order, in two levels so that the loads of a level are in flight together: work item (k, j) adds value j
   // of the workgroups 8 k .. 8 k + 7, then value j's 16 group sums are added in group order
   const int n_total = M * LK_ROW_SUMS + LK_SCALARS;
   for (int item = threadIdx.x; item < n_total * LK_GROUPS; item += LK_THREADS) {
     const int k = item / n_total, j = item - k * n_total;
-    const volatile double* p = partial + j;
+    const volatile double* p = ws.seen() + j;
     double v[LK_GROUP];
 #pragma unroll
     for (int u = 0; u < LK_GROUP; ++u) {
@@ -262,7 +227,7 @@ __global__ __launch_bounds__(LK_THREADS) void likelihood_kernel(Args a) {
     a.stats[5] = (float)s[0];
     a.stats[6] = (float)n_valid;
     a.stats[7] = (float)s[1];
-    *ticket = 0;       // ready for the next launch on this workspace
+    ws.rearm();
   }
 }
 
@@ -277,7 +242,7 @@ extern "C" int sunerf_likelihood_abi_version(void) { return SUNERF_LIKELIHOOD_AB
 
 extern "C" size_t sunerf_likelihood_workspace_bytes(int n_rows) {
   if (n_rows < 1 || n_rows > LK_MAX_ROWS) return 0;
-  return 64 + (size_t)LK_BLOCKS * partial_stride(n_rows) * sizeof(double);
+  return Ticket::bytes((size_t)LK_BLOCKS * partial_stride(n_rows));
 }
 
 extern "C" int sunerf_likelihood_loss(const float* coarse_image, const float* fine_image, const float* target_image,

@@ -14,11 +14,12 @@
 // Layout: launch 1 gives every MT_TW x MT_TH tile of outputs of every image one 256-thread workgroup.  It stages the tile's
 // (MT_TW + 6) x (MT_TH + 6) input pairs in LDS (reflected indices; each input byte comes from HBM once, the halo of the
 // neighbouring tiles from L2), sums the five products over 7 columns into LDS (fp64), then over 7 rows per output, and
-// writes four fp64 sums per tile (crop S, d^2, |d|, d) after a fixed-order LDS tree.  Launch 2 gives each image one
+// writes four fp64 sums per tile (crop S, d^2, |d|, d) after ordered_sum.h's halving tree.  Launch 2 gives each image one
 // workgroup that adds its tiles' sums in a fixed order and divides.  No atomics: results are bit-identical from run to run
 // and do not depend on the batch an image is scored in, nor on its place there.  A NaN pixel lies in some crop window
 // and in the pixel means, so it makes all four outputs of its image NaN.
 #include "sunerf_common.h"
+#include "ordered_sum.h"
 #include "../../include/sunerf_hip.h"
 
 namespace {
@@ -47,20 +48,6 @@ __device__ __forceinline__ int reflect(int i, int n) {
   i = i < 0 ? -i - 1 : (i >= n ? 2 * n - i - 1 : i);
   // positions beyond one reflection only occur outside the image, for outputs that are never counted: keep them in bounds
   return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
-
-__device__ __forceinline__ void tree_sum4(double (*red)[MT_THREADS], double v[4]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) red[k][t] = v[k];
-  __syncthreads();
-  for (int s = MT_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) red[k][t] += red[k][t + s];
-    }
-    __syncthreads();
-  }
 }
 
 __global__ __launch_bounds__(MT_THREADS) void image_metrics_tiles_kernel(MetricsArgs a) {
@@ -134,16 +121,16 @@ __global__ __launch_bounds__(MT_THREADS) void image_metrics_tiles_kernel(Metrics
       acc[2] += fabs(d);
       acc[3] += d;
     }
-    __syncthreads();                             // hs is reused for the reduction
-    double (*red)[MT_THREADS] = reinterpret_cast<double (*)[MT_THREADS]>(&hs[0][0][0]);
-    tree_sum4(red, acc);
-    if (t < 4) a.partial[tile * 4 + t] = red[t][0];
+    __syncthreads();                             // hs is reused for the reduction: every thread has read its window sums
+    double* red = &hs[0][0][0];                  // [4][MT_THREADS]
+    lds_tree<MT_THREADS>(red, acc, add_values());
+    if (t < 4) a.partial[tile * 4 + t] = red[t * MT_THREADS];
     __syncthreads();                             // red / sx / sy are overwritten by the next tile
   }
 }
 
 __global__ __launch_bounds__(MT_THREADS) void image_metrics_finish_kernel(MetricsArgs a) {
-  __shared__ double red[4][MT_THREADS];
+  __shared__ double red[4 * MT_THREADS];
   const int t = threadIdx.x;
   const double n_crop = (double)(a.height - 2 * MT_R) * (double)(a.width - 2 * MT_R);
   const double n_pix = (double)a.height * (double)a.width;
@@ -154,9 +141,9 @@ __global__ __launch_bounds__(MT_THREADS) void image_metrics_finish_kernel(Metric
 #pragma unroll
       for (int k = 0; k < 4; ++k) acc[k] += p[j * 4 + k];
     }
-    tree_sum4(red, acc);
-    if (t < 4) a.out[img * 4 + t] = red[t][0] / (t == 0 ? n_crop : n_pix);
-    __syncthreads();
+    lds_tree<MT_THREADS>(red, acc, add_values());
+    if (t < 4) a.out[img * 4 + t] = red[t * MT_THREADS] / (t == 0 ? n_crop : n_pix);
+    __syncthreads();                             // the results are read before the next image's tree overwrites them
   }
 }
 
@@ -180,7 +167,7 @@ extern "C" int sunerf_image_metrics(const float* pred, const float* target, int6
   if (n_images == 0) return 0;
   if (!shape_ok(n_images, height, width)) return SUNERF_E_BADARG;
   if (!pred || !target || !out || !workspace) return SUNERF_E_BADARG;
-  if (!(data_range > 0.0) || !(data_range <= 1.7976931348623157e308)) return SUNERF_E_BADARG;   // finite, > 0
+  if (!finite_positive(data_range)) return SUNERF_E_BADARG;
   if ((uintptr_t)out % sizeof(double) || (uintptr_t)workspace % sizeof(double)) return SUNERF_E_BADARG;
   if (workspace_bytes < sunerf_image_metrics_workspace_bytes(n_images, height, width)) return SUNERF_E_WORKSPACE;
   MetricsArgs a;

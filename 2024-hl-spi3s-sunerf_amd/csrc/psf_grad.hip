@@ -13,7 +13,8 @@
 //    add: the forward's inner loop with the roles of the operands swapped.  A workgroup keeps its sums in registers over a RUN of
 //    (plane, tile) items of one kernel index -- the run is fixed by the arguments -- then adds the slices of each tap through LDS,
 //    slice 0 first, and writes one fp64 partial per tap and run to the workspace.
-// 2. the FINAL kernel: one thread per tap adds the tap's partials, run 0 first, and multiplies by scale.
+// 2. the FINAL kernel (corr_bin.h's run_sum_final_kernel, shared with coalign.hip): one thread per tap adds the tap's partials, run 0
+//    first, and multiplies by scale.
 //
 // No floating-point atomics; -ffp-contract=off and no explicit fma: every operation is rounded on its own, as the header says.
 #include "corr_bin.h"
@@ -141,20 +142,6 @@ __global__ __launch_bounds__(CB_THREADS) void psf_grad_partial_kernel(const floa
   }
 }
 
-constexpr int PG_FINAL_THREADS = 256;
-
-__global__ __launch_bounds__(PG_FINAL_THREADS) void psf_grad_final_kernel(const double* __restrict__ partials, double* __restrict__ g_K,
-                                                                          int n_runs, int taps, int64_t total, double scale) {
-  for (int64_t idx = (int64_t)blockIdx.x * PG_FINAL_THREADS + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * PG_FINAL_THREADS) {
-    const int64_t k = idx / taps;
-    const double* src = partials + k * n_runs * taps + (idx - k * taps);
-    double s = src[0];
-#pragma unroll 16
-    for (int r = 1; r < n_runs; ++r) s = s + src[(int64_t)r * taps];          // unrolled: sixteen loads in flight, the adds in order
-    g_K[idx] = scale * s;
-  }
-}
-
 template <bool NEAREST>
 int launch(const float* in, const float* g_out, double* g_K, double* partials, const CorrBinArgs& a, const PsfGradPlan& p, hipStream_t st) {
   const size_t lds = psf_grad_lds_bytes(a, p);
@@ -175,8 +162,7 @@ int launch(const float* in, const float* g_out, double* g_K, double* partials, c
   }
 #undef PG_PARTIAL
   const int64_t total = (int64_t)a.n_kernels * p.taps;
-  hipLaunchKernelGGL(psf_grad_final_kernel, dim3(grid_of((total + PG_FINAL_THREADS - 1) / PG_FINAL_THREADS)), dim3(PG_FINAL_THREADS), 0, st,
-                     (const double*)partials, g_K, p.n_runs, p.taps, total, a.scale);
+  launch_run_sum_final<true>(partials, g_K, p.n_runs, p.taps, total, a.scale, st);
   SUNERF_CHECK_LAUNCH();
   return 0;
 }

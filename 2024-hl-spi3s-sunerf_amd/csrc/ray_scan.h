@@ -35,6 +35,7 @@ __device__ __forceinline__ float sum32(float v) {
 }
 
 // ---- over the 64 lanes of a wave (float and double): the order 32..1 is part of the result's bits ----
+// (what a workgroup and a grid do with the wave totals -- the waves in wave order, the LDS tree, the ticket -- is ordered_sum.h's)
 template <class T>
 __device__ __forceinline__ T sum64(T v) {
 #pragma unroll

@@ -166,8 +166,6 @@ __global__ __launch_bounds__(kTile * kTile) void register_frames_kernel(Register
   if (t < SUNERF_REGISTER_STATE && tally[t]) atomicAdd(a.state + (int64_t)blockIdx.z * SUNERF_REGISTER_STATE + t, (unsigned long long)tally[t]);
 }
 
-inline bool is_finite(double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; }
-
 template <int order>
 void launch(const RegisterArgs& a, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL(register_frames_kernel<order>, grid, dim3(kTile * kTile), 0, st, a);
@@ -189,7 +187,7 @@ extern "C" int sunerf_register_frames(const SunerfRegisterFrameDesc* frames, int
   const bool negative = n_frames < 0 || n_planes < 0 || out_height < 0 || out_width < 0;
   if (!negative && (n_frames == 0 || out_height == 0 || out_width == 0)) return 0;
   if (negative || n_planes == 0 || n_frames > 65535 || out_height > kTile * 65535) return SUNERF_E_BADARG;      // grid y and z
-  if (!(radius > 0.) || !is_finite(radius) || !is_finite(A) || !is_finite(B) || !is_finite(C)) return SUNERF_E_BADARG;
+  if (!finite_positive(radius) || !is_finite(A) || !is_finite(B) || !is_finite(C)) return SUNERF_E_BADARG;
   if (!frames || !c2w_ref || !tx_ref || !ty_ref || !out || !status || !state) return SUNERF_E_BADARG;
   if ((uintptr_t)frames % 8 || (uintptr_t)tx_ref % 8 || (uintptr_t)ty_ref % 8 || (uintptr_t)coords % 8 || (uintptr_t)state % 8)
     return SUNERF_E_BADARG;

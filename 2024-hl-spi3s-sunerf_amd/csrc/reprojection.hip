@@ -15,6 +15,7 @@
 // No atomics anywhere: the same inputs give the same bytes.  The only data-dependent loops are the binary searches (bounded by
 // the axis length), the view loop and the walk over the observers of one block (bounded by its 256 pixels).
 #include "sunerf_common.h"
+#include "ordered_sum.h"
 #include "reproject_math.h"
 #include "../../include/sunerf_hip.h"
 
@@ -148,15 +149,11 @@ struct FillArgs {
   double* stats; double* partial;       // partial [C][kFillBlocks][2]
 };
 
-// sum over the workgroup of (s, n), fixed tree: the result in red[0] / red[kBlock] for every thread after the last barrier
+// sum over the workgroup of (s, n) by ordered_sum.h's halving tree: the result in red[0] / red[kBlock] for every thread.  Each
+// kernel runs it once on an array of its own: no barrier of the caller's.
 __device__ __forceinline__ void tree_sum2(double* red, double s, double n) {
-  const int t = threadIdx.x;
-  red[t] = s; red[kBlock + t] = n;
-  __syncthreads();
-  for (int w = kBlock / 2; w > 0; w >>= 1) {
-    if (t < w) { red[t] += red[t + w]; red[kBlock + t] += red[kBlock + t + w]; }
-    __syncthreads();
-  }
+  const double v[2] = {s, n};
+  lds_tree<kBlock>(red, v, add_values());
 }
 
 __global__ __launch_bounds__(kBlock) void map_fill_partial_kernel(FillArgs a) {
@@ -284,8 +281,6 @@ __global__ __launch_bounds__(kBlock) void reproject_views_kernel(ViewsArgs a) {
     }
   }
 }
-
-inline bool finite_positive(double v) { return v > 0. && v <= 1.7976931348623157e308; }
 
 }  // namespace
 

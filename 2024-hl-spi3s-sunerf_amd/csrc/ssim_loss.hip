@@ -19,10 +19,11 @@
 //           scheme, g_p = (box(alpha) + x_p box(beta) + y_p box(gamma)) / W^2, times s'(x_p) under the stretch.  A gather: no atomics
 // The strips and the order inside them are fixed by (P, w) alone, so a plane's SSIM and gradient do not depend on its batch.
 //
-// Reductions: the SSIM of a plane is the sum of its work items' partial sums by one fixed tree; a workgroup adds its planes in
-// channel order and writes 4 fp64 partials to the workspace; the workgroup that takes the last ticket adds the partials in index
-// order (256 contiguous runs, then the same tree).  No floating-point atomics: reruns give the same bits.
+// Reductions: the SSIM of a plane is the sum of its work items' partial sums by ordered_sum.h's halving tree; a workgroup adds its
+// planes in channel order and writes 4 fp64 partials to the workspace; the workgroup that takes the last ticket (ordered_sum.h)
+// adds the partials in index order (256 contiguous runs, then the same tree).
 #include "sunerf_common.h"
+#include "ordered_sum.h"
 #include "../../include/sunerf_hip_ssim_loss.h"
 
 #include <cmath>
@@ -53,16 +54,11 @@ __device__ __forceinline__ double stretch(const Args& a, float v) {
   return asinh((double)v / a.vmax / a.a) / a.norm;
 }
 
-// the sum of one value over the workgroup, in every thread, by one fixed tree
+// the sum of one value over the workgroup, in every thread, by ordered_sum.h's halving tree
 __device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  __syncthreads();          // red may still be read by a previous call
-  red[t] = v;
-  __syncthreads();
-  for (int s = SL_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
+  const double one[1] = {v};
+  __syncthreads();          // red[0] may still be read by a previous call
+  lds_tree<SL_THREADS>(red, one, add_values());
   return red[0];
 }
 
@@ -187,7 +183,6 @@ __device__ __forceinline__ double plane_ssim_and_gradient(const Args& a, const d
 __global__ __launch_bounds__(SL_THREADS) void ssim_loss_kernel(Args a) {
   extern __shared__ __attribute__((aligned(16))) double lds[];      // X | Y | M [3][W W] | fp32 planes [3][CC][plane_stride]
   __shared__ double red[SL_THREADS];
-  __shared__ unsigned last;
   const int P = a.P, C = a.C, pixels = P * P, t = threadIdx.x;
   double* X = lds;
   double* Y = X + pixels;
@@ -247,24 +242,17 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_kernel(Args a) {
     }
   }
 
-  unsigned* ticket = (unsigned*)a.workspace;
-  double* partial = (double*)((char*)a.workspace + 64);
+  const Ticket ws(a.workspace);
   if (t == 0) {
-    double* mine = partial + (size_t)blockIdx.x * SL_PARTIAL;
+    double* mine = ws.partial + (size_t)blockIdx.x * SL_PARTIAL;
     mine[0] = sum[0]; mine[1] = sum[1]; mine[2] = valid[0]; mine[3] = valid[1];
   }
-  // exactly one workgroup, the one that finishes last, sees every partial
-  __threadfence();
-  __syncthreads();
-  if (t == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
+  if (!last_block(ws.ticket)) return;
   // every sum in index order: thread t adds a contiguous run of workgroups, the 256 runs are added by the tree
   const unsigned run = (gridDim.x + SL_THREADS - 1) / SL_THREADS;
   const unsigned b0 = min((unsigned)t * run, gridDim.x), b1 = min(b0 + run, gridDim.x);
   double s[SL_PARTIAL] = {0.0, 0.0, 0.0, 0.0};
-  const volatile double* p = partial;
+  const volatile double* p = ws.seen();
   for (unsigned b = b0; b < b1; ++b)
     for (int k = 0; k < SL_PARTIAL; ++k) s[k] += p[(size_t)b * SL_PARTIAL + k];
   for (int k = 0; k < SL_PARTIAL; ++k) s[k] = block_sum(s[k], red);
@@ -274,13 +262,11 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_kernel(Args a) {
     a.stats[1] = s[3] > 0.0 ? 1.0 - s[1] / s[3] : 0.0;
     a.stats[2] = s[2] + s[3];
     a.stats[3] = 2.0 * planes_per_image - (s[2] + s[3]);
-    *ticket = 0;       // ready for the next launch on this workspace
+    ws.rearm();
   }
 }
 
 size_t working_bytes(int P, int W) { return (2 * (size_t)P * P + 3 * (size_t)W * W) * sizeof(double); }
-
-bool finite_positive(double v) { return v > 0.0 && v <= 1.7976931348623157e308; }
 
 }  // namespace
 
@@ -289,7 +275,7 @@ extern "C" int sunerf_ssim_loss_abi_version(void) { return SUNERF_SSIM_LOSS_ABI_
 extern "C" size_t sunerf_ssim_loss_workspace_bytes(int64_t n, int C) {
   if (n < 1 || C < 1 || C > SUNERF_SSIM_LOSS_MAX_CHANNELS) return 0;
   if (n > (int64_t)0x7fffffff / C) return 0;          // one workgroup per patch and channel at the most: the grid is 32 bits
-  return 64 + (size_t)n * C * SL_PARTIAL * sizeof(double);
+  return Ticket::bytes((size_t)n * C * SL_PARTIAL);
 }
 
 extern "C" int sunerf_ssim_loss(const float* coarse, const float* fine, const float* target, int64_t n, int P, int C, int window,

@@ -130,6 +130,11 @@ static inline unsigned grid_of(int64_t work) {
   return (unsigned)(work < 1 ? 1 : (work < cap ? work : cap));
 }
 
+// argument checks of the entry points (host), by comparison so that they hold under any floating-point flags: neither NaN nor
+// infinite; and that with v > 0
+static inline bool is_finite(double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; }
+static inline bool finite_positive(double v) { return v > 0. && v <= 1.7976931348623157e308; }
+
 // hipGetLastError() reports the last error of ANY earlier runtime call on this thread (e.g. a probe made by the
 // caller's framework): clear it before a launch so that the check after the launch sees only our own.
 // Experiment knob (tools/experiments/overlap_probe.py): SUNERF_GRID_CAP_FWD / _DGRAD limit a persistent kernel's grid

@@ -6,11 +6,11 @@
 //   grad_norm_kernel torch.nn.utils.clip_grad_norm_ (what Lightning's gradient_clip_val = 0.5 calls, run_emission.py:72)
 //   adam_kernel      torch.optim.Adam single-tensor update (sunerf.py:31), operation order of torch/optim/adam.py
 //
-// All reductions are two-stage and ordered (block partials in fp64 -> the last block sums them in index order), so the
-// results do not depend on scheduling.  ~4 bytes of HBM traffic per element and pass; the kernels are launched with a
-// fixed grid of at most TS_BLOCKS workgroups and stride over their input.
+// All reductions are two-stage and ordered (block partials in fp64 -> the last block, found by ordered_sum.h's ticket, sums
+// them in index order), so the results do not depend on scheduling.  ~4 bytes of HBM traffic per element and pass; the
+// kernels are launched with a fixed grid of at most TS_BLOCKS workgroups and stride over their input.
 #include "sunerf_common.h"
-#include "ray_scan.h"
+#include "ordered_sum.h"
 #include "../../include/sunerf_hip.h"
 
 namespace {
@@ -19,34 +19,11 @@ constexpr int TS_THREADS = 256;
 constexpr int TS_BLOCKS = 128;
 constexpr int TS_MAX_EXTRA = 8;
 
-// workspace: [0] ticket (unsigned), then from byte 64: TS_BLOCKS x 4 doubles of block partials
-struct Workspace {
-  unsigned* ticket;
-  double* partial;
-  __host__ __device__ explicit Workspace(void* p) : ticket((unsigned*)p), partial((double*)((char*)p + 64)) {}
-};
-
+// workspace (ordered_sum.h's Ticket): TS_BLOCKS x 4 doubles of block partials
 __device__ __forceinline__ double block_sum(double v, double* sh) {
   v = sum64(v);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   __syncthreads();   // sh may still be read by a previous call
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < TS_THREADS / 64; ++w) t += sh[w];
-  return t;
-}
-
-// true for exactly one workgroup of the grid: the one that finishes last (all partials are then visible to it)
-__device__ __forceinline__ bool last_block(unsigned* ticket) {
-  __shared__ unsigned last;
-  __threadfence();
-  __syncthreads();
-  if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
-  __syncthreads();
-  if (last) __threadfence();
-  return last != 0;
+  return wave_order_sum<TS_THREADS / 64>(v, sh);
 }
 
 // Strided sweep of a float array with two 16-byte loads in flight per thread (a scalar grid-stride loop leaves every
@@ -121,7 +98,7 @@ __global__ __launch_bounds__(TS_THREADS) void loss_kernel(LossArgs a) {
   for (int k = 0; k < a.n_extra; ++k)
     sweep(a.extra[k], a.extra_n[k], tid, stride, [&](float x) { bad += !isfinite(x); });
 
-  Workspace ws(a.workspace);
+  const Ticket ws(a.workspace);
   const double b0 = block_sum((double)sq_c, sh), b1 = block_sum((double)sq_f, sh), b2 = block_sum((double)sum_r, sh),
                b3 = block_sum((double)bad, sh);
   if (threadIdx.x == 0) {
@@ -133,7 +110,7 @@ __global__ __launch_bounds__(TS_THREADS) void loss_kernel(LossArgs a) {
   // a single thread walking 512 x 4 uncached partials costs ~0.3 ms
   double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
   for (unsigned b = threadIdx.x; b < gridDim.x; b += TS_THREADS) {
-    const volatile double* p = ws.partial + (size_t)b * 4;
+    const volatile double* p = ws.seen() + (size_t)b * 4;
     s0 += p[0]; s1 += p[1]; s2 += p[2]; s3 += p[3];
   }
   s0 = block_sum(s0, sh); s1 = block_sum(s1, sh); s2 = block_sum(s2, sh); s3 = block_sum(s3, sh);
@@ -147,7 +124,7 @@ __global__ __launch_bounds__(TS_THREADS) void loss_kernel(LossArgs a) {
     a.stats[4] = -10.f * log10f(mse_f);                                   // sunerf.py:122
     a.stats[5] = (float)s3;
     a.stats[6] = 0.f; a.stats[7] = 0.f;
-    *ws.ticket = 0;       // ready for the next launch on this workspace
+    ws.rearm();
   }
 }
 
@@ -169,12 +146,12 @@ __global__ __launch_bounds__(TS_THREADS) void grad_norm_kernel(NormArgs a) {
     const float g = x * a.grad_scale;
     sq += g * g;
   });
-  Workspace ws(a.workspace);
+  const Ticket ws(a.workspace);
   const double b = block_sum((double)sq, sh);
   if (threadIdx.x == 0) ws.partial[(size_t)blockIdx.x * 4] = b;
   if (!last_block(ws.ticket)) return;
   double s = 0;
-  for (unsigned k = threadIdx.x; k < gridDim.x; k += TS_THREADS) s += ((const volatile double*)ws.partial)[(size_t)k * 4];
+  for (unsigned k = threadIdx.x; k < gridDim.x; k += TS_THREADS) s += ws.seen()[(size_t)k * 4];
   s = block_sum(s, sh);
   if (threadIdx.x == 0) {
     const float total = (float)sqrt(s);
@@ -195,7 +172,7 @@ __global__ __launch_bounds__(TS_THREADS) void grad_norm_kernel(NormArgs a) {
     a.norm_out[2] = skip ? 1.f : 0.f;
     a.norm_out[3] = 0.f;
     *(long long*)((char*)a.workspace + 8) = step;
-    *ws.ticket = 0;
+    ws.rearm();
   }
 }
 
@@ -245,7 +222,7 @@ int blocks_for(int64_t n) {
 
 }  // namespace
 
-extern "C" size_t sunerf_train_workspace_bytes(void) { return 64 + (size_t)TS_BLOCKS * 4 * sizeof(double); }
+extern "C" size_t sunerf_train_workspace_bytes(void) { return Ticket::bytes((size_t)TS_BLOCKS * 4); }
 
 extern "C" int sunerf_training_loss(const float* coarse_image, const float* fine_image, const float* target_image, int64_t n,
                                     const float* regularization, int64_t n_reg, const float* const* finite_check_host,

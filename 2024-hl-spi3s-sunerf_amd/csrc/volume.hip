@@ -23,6 +23,7 @@
 //                           a fixed LDS tree per workgroup, partial[workgroup][11].  Launch 2: one workgroup adds the partials in
 //                           a fixed order.  No atomics; the grid is a function of the voxel count only.
 #include "sunerf_common.h"
+#include "ordered_sum.h"
 #include "dt_response.h"
 #include "../../include/sunerf_hip.h"
 
@@ -226,22 +227,14 @@ struct VolMetricArgs {
   int n_blocks;
 };
 
-__device__ __forceinline__ void vm_tree(double (*red)[VM_THREADS], const double v[VM_N]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < VM_N; ++k) red[k][t] = v[k];
-  __syncthreads();
-  for (int s = VM_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) {
-#pragma unroll
-      for (int k = 0; k < VM_N; ++k) red[k][t] = k == VM_MAX ? fmax(red[k][t], red[k][t + s]) : red[k][t] + red[k][t + s];
-    }
-    __syncthreads();
-  }
+// ordered_sum.h's halving tree over the VM_N values, value VM_MAX by fmax; result k in red[k * VM_THREADS].  Each kernel runs it
+// once on an array of its own: no barrier of the caller's.
+__device__ __forceinline__ void vm_tree(double* red, const double (&v)[VM_N]) {
+  lds_tree<VM_THREADS>(red, v, [](int k, double acc, double other) { return k == VM_MAX ? fmax(acc, other) : acc + other; });
 }
 
 __global__ __launch_bounds__(VM_THREADS) void volume_metrics_partial_kernel(VolMetricArgs a, bool small) {
-  __shared__ double red[VM_N][VM_THREADS];
+  __shared__ double red[VM_N * VM_THREADS];
   double acc[VM_N];
 #pragma unroll
   for (int k = 0; k < VM_N; ++k) acc[k] = 0.;
@@ -265,11 +258,11 @@ __global__ __launch_bounds__(VM_THREADS) void volume_metrics_partial_kernel(VolM
     acc[10] += 1.;
   }
   vm_tree(red, acc);
-  if (threadIdx.x < VM_N) a.partial[(size_t)blockIdx.x * VM_N + threadIdx.x] = red[threadIdx.x][0];
+  if (threadIdx.x < VM_N) a.partial[(size_t)blockIdx.x * VM_N + threadIdx.x] = red[threadIdx.x * VM_THREADS];
 }
 
 __global__ __launch_bounds__(VM_THREADS) void volume_metrics_finish_kernel(VolMetricArgs a) {
-  __shared__ double red[VM_N][VM_THREADS];
+  __shared__ double red[VM_N * VM_THREADS];
   double acc[VM_N];
 #pragma unroll
   for (int k = 0; k < VM_N; ++k) acc[k] = 0.;
@@ -281,7 +274,7 @@ __global__ __launch_bounds__(VM_THREADS) void volume_metrics_finish_kernel(VolMe
     }
   }
   vm_tree(red, acc);
-  if (threadIdx.x < VM_N) a.out[threadIdx.x] = red[threadIdx.x][0];
+  if (threadIdx.x < VM_N) a.out[threadIdx.x] = red[threadIdx.x * VM_THREADS];
 }
 
 int vm_blocks(int64_t total) {
