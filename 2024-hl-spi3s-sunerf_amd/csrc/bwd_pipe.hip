@@ -29,11 +29,11 @@
 // counters, each with ONE writer: prod[j] = chunks whose half producer j has stored AND drained (in-order vmcnt: known
 // DRAIN iterations later), cons[j] = chunks consumer j has landed in its LDS.  A consumer may fetch chunk c once
 // min(prod) > c; a producer may overwrite slot c % RING once min(cons) > c - RING.  The counters are polled AHEAD by LDS-DMA
-// (a 4-byte-per-lane DMA into a small LDS slot, issued PIPE_POLL_LAG iterations before its value is read), so that a wave
+// (a 4-byte-per-lane DMA into a small LDS slot, issued POLL_LAG iterations before its value is read), so that a wave
 // never waits for a flag round trip unless the partner really is late; only then it falls back to a bounded spin.  The ring's
-// 16 slots are shared by the age of the polled counters, the distance at which dZ is requested (PIPE_ZD) and the publication
-// delay of the outputs (DRAIN): each iteration saved there is an iteration of slack between two stages (round 4: 4 + 4 + 4 ->
-// 2 + 2 + 3; before, every stage spent 15 % of the launch on round trips for counters that were merely old).
+// 16 slots are shared by the age of the polled counters, the distance at which dZ is requested (ZD_HIDDEN) and the publication
+// delay of the outputs (DRAIN): each iteration saved there is an iteration of slack between two stages (2 + 2 + 2; with
+// 4 + 4 + 4 every stage spent 15 % of the launch on round trips for counters that were merely old).
 // Placement is CHECKED, not assumed: every workgroup publishes its XCC_ID,
 // and a class (blockIdx % 8) that does not sit on one XCD makes the whole launch give up (status word; the reduce kernel then
 // writes NaN gradients, which the optimiser's non-finite guard skips, raises the STICKY status word in front of the workspace,
@@ -50,35 +50,13 @@ constexpr int WG = 512;                 // pipelined kernel: eight waves, two pe
 constexpr int WG_PRE = 256;             // prologue kernel
 constexpr int NBUF = 4;                 // staging buffers of the in-layer stage and of the prologue (chunks in flight: NBUF - 1)
 constexpr int NBUF_H = 5;               // ... of a hidden stage: chunk it + 4 is being fetched, chunk it + 1's phases are decoded, chunk it is consumed
-#ifndef PIPE_DMA_ON_WEIGHT
-#define PIPE_DMA_ON_WEIGHT 2            // who issues the LDS-DMA pieces of a hidden stage: see "WHO ISSUES THE PIECES" below (0: 11.48, 1: 11.38, 2: 11.04 ms, r4_pipe_ab11;
-                                        // with the decoder under the matrix chain, where the pieces of modes 0 and 1 compete with it: 0: 11.10, 1: 10.85, 2: 10.75, profiles/r5_ab/).
-                                        // Three more variants (3 / 7 / 7 / 7 pieces, protocol split over two waves, the data waves' tile in VGPRs) were measured slower
-                                        // and removed again: commit cafd360 has them, tools/experiments/README.md the numbers (3 / 7 / 7 / 7 again in
-                                        // round 6, on the skewed image and the round-5 order: 11.71 against 10.23 ms)
-#endif
-#ifndef PIPE_ZD
-#define PIPE_ZD 2                       // hidden stages below the top: dZ_l is requested this many iterations before it is consumed
-#endif
-#ifndef PIPE_RING
-#define PIPE_RING 16
-#endif
-#ifndef PIPE_POLL_LAG
-#define PIPE_POLL_LAG 2                 // iterations between the issue of a counter poll and the gate that reads it (1 .. NBUF_H - 1); 4 -> 2: kernel 12.2 -> 11.8 ms (r4_pipe_ab7)
-#endif
-constexpr int RING = PIPE_RING;                // chunk slots per hand-off ring
+constexpr int RING = 16;                // chunk slots per hand-off ring: what the three distances below do not use is slack between two stages (HAND-OFF above)
+constexpr int ZD_HIDDEN = 2;            // hidden stages below the top: dZ_l is requested this many iterations before it is consumed (~6000 clocks, an L2 read takes ~1000)
+constexpr int POLL_LAG = 2;             // iterations between the issue of a counter poll and the gate that reads it (1 .. NBUF_H - 1): a younger counter saves round trips
+constexpr int PF_HIDDEN = 2;            // a hidden stage's data-gradient waves request their B fragments this many k-steps ahead (see hidden_stage)
 constexpr int SLOT = PKS * 1024;        // one chunk of dZ: 16 fragments
-#ifndef PIPE_LDS_IMAGE
-#define PIPE_LDS_IMAGE 1                // LDS image of a hidden stage's fragments: 0 = fragments 1 KiB apart, rows in lane order; 1 = PAIR SKEW, fragments 1088 B apart
-                                        // (the odd fragment of a pair 64 B further, pair stride 2176); 2 = pair skew + ROW SWIZZLE (16-byte row r of a
-                                        // fragment at position r ^ 8 (r >> 5)).  See "LDS IMAGE" in hidden_stage.  Kernel, same-call medians
-                                        // (profiles/r6_ab/): with PIPE_PF = 4 image 1 / 2 -0.16 / -0.19 ms against image 0, with PIPE_PF = 2
-                                        // -0.29 / -0.22 ms (image 0 itself +0.30 ms there).  -DPIPE_LDS_IMAGE=0 -DPIPE_PF=4 is the round-5 kernel,
-                                        // instruction for instruction
-#endif
-static_assert(PIPE_LDS_IMAGE >= 0 && PIPE_LDS_IMAGE <= 2, "PIPE_LDS_IMAGE: 0, 1 or 2");
-constexpr int FRAG_H = PIPE_LDS_IMAGE ? 1088 : 1024;      // distance of two fragments in a hidden stage's staging buffer
-constexpr int BUF_HID = 24 * FRAG_H;    // hidden stage staging: dZ_l 16 | P[J] 8 fragments (16-bit phases, decoded IN PLACE to fp16 sin = H[J]): 24 / 25.5 KiB
+constexpr int FRAG_H = 1088;            // distance of two fragments in a hidden stage's staging buffer: PAIR SKEW, see "LDS IMAGE" in hidden_stage
+constexpr int BUF_HID = 24 * FRAG_H;    // hidden stage staging: dZ_l 16 | P[J] 8 fragments (16-bit phases, decoded IN PLACE to fp16 sin = H[J]): 25.5 KiB
 constexpr int BUF_IN = 16 * 1024;       // in-layer stage staging: dZ_0[J] 8 | enc 6 (| 2 unused) KiB
 constexpr int BUF_PRE = 19 * 1024;      // prologue staging: P 16 (decoded in place to H) | dZ_out operand tile 2 KiB | g_raw of the chunk 256 B
 constexpr unsigned SPIN_LIMIT = 50000000u;   // s_memrealtime ticks (100 MHz): 0.5 s
@@ -132,10 +110,7 @@ __device__ __forceinline__ void dma_piece(const char* src_lane, unsigned lds_dst
 template <int POLICY>
 __device__ __forceinline__ void dma_piece_s(const char* src_uniform, unsigned voff, unsigned lds_dst) {
   const unsigned d = __builtin_amdgcn_readfirstlane(lds_dst);
-#ifndef PIPE_STREAM_BITS
-#define PIPE_STREAM_BITS "nt"      // cache policy of the read-once HBM streams (phases, top dZ); experiment: "sc0 sc1 nt", "sc1 nt", "sc0 nt"
-#endif
-  if (POLICY == 1) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2 " PIPE_STREAM_BITS :: "v"(voff), "s"(d), "s"(src_uniform) : "memory");
+  if (POLICY == 1) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2 nt" :: "v"(voff), "s"(d), "s"(src_uniform) : "memory");
   else if (POLICY == 2) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2 sc1" :: "v"(voff), "s"(d), "s"(src_uniform) : "memory");
   else asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2" :: "v"(voff), "s"(d), "s"(src_uniform) : "memory");
 }
@@ -176,29 +151,19 @@ __device__ __forceinline__ void drain_matrix_pipe() { asm volatile("s_nop 15\n\t
 // Transposed operand read straight into FOUR CONSECUTIVE, FIXED registers (the matrix instruction's operand tuple): the two
 // ds_read_b64_tr_b16 halves of tr_issue land in separate register pairs and cost 4 v_mov per operand to join -- 48 per chunk
 // in a wave whose instruction stream is the kernel's critical path.  R0..R3: VGPR numbers, OFF: immediate byte offset.
-#ifndef PIPE_KO_WREADS
-#define PIPE_KO_WREADS 0
-#endif
-#if PIPE_KO_WREADS      // knock-out (results garbage): the weight-gradient waves' transposed operand reads are not issued
-#define TR_FIXED(R0, R1, R2, R3, OFF, var, base) asm volatile("" : "={v[" #R0 ":" #R3 "]}"(var) : "v"(base) : "memory")
-#else
 #define TR_FIXED(R0, R1, R2, R3, OFF, var, base)                                                                        \
   asm volatile("ds_read_b64_tr_b16 v[" #R0 ":" #R1 "], %1 offset:%2\n\tds_read_b64_tr_b16 v[" #R2 ":" #R3 "], %1 offset:%3" \
                : "={v[" #R0 ":" #R3 "]}"(var) : "v"(base), "i"(OFF), "i"((OFF) + 64) : "memory")
-#endif
-// The lane part of that address in a hidden stage's image (PIPE_LDS_IMAGE; 0: tr_lane_offset of grad_common.h, which the
-// in-layer stage, the prologue and the two-kernel backward keep), and where the 16-byte row of lane `lane` of a fragment sits
-// for everybody who moves whole rows: LDS-DMA (as its SOURCE offset: the DMA writes lane-linearly, and the permutation is an
-// involution), the data-gradient waves' B-fragment reads, the decoder.  Neither the second read's `offset:64` (rows + 4) nor the
-// k-step's + 256 (rows + 16) carries into the bit the swizzle flips (bit 3 of the row: rows q, q + 4 with q < 4).
+// The lane part of that address in a hidden stage's pair-skewed image ("LDS IMAGE" in hidden_stage; the in-layer stage, the
+// prologue and the two-kernel backward keep tr_lane_offset of grad_common.h), and where the 16-byte row of lane `lane` of a
+// fragment sits for everybody who moves whole rows: LDS-DMA (as its SOURCE offset), the data-gradient waves' B-fragment reads,
+// the decoder.
 __device__ __forceinline__ unsigned tr_lane_offset_image(int lane) {
-  if (PIPE_LDS_IMAGE == 0) return tr_lane_offset(lane);
   const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  int row = (p >> 1) * 32 + 8 * (g >> 1) + q;
-  if (PIPE_LDS_IMAGE == 2) row ^= 8 * (row >> 5);
+  const int row = (p >> 1) * 32 + 8 * (g >> 1) + q;
   return (g & 1) * FRAG_H + row * 16 + (p & 1) * 8;
 }
-__device__ __forceinline__ unsigned frag_row_offset(int lane) { return (PIPE_LDS_IMAGE == 2 ? lane ^ (8 * (lane >> 5)) : lane) * 16; }
+__device__ __forceinline__ unsigned frag_row_offset(int lane) { return lane * 16; }
 
 // dZ = dH * cos of one 32 x 32 tile, rounded to (saturating) fp16 for the chain -- and, before that rounding, added to this
 // lane's running bias sums `bs` (db = sum over samples of dZ, in fp32: round 4; until then the weight-gradient waves summed
@@ -213,32 +178,18 @@ __device__ __forceinline__ void dz_tile(const f32x16& acc, const float* c0, cons
     d1[j] = (_Float16)sunerf_sat16(p1);
   }
 }
-#ifndef PIPE_TRIM
-#define PIPE_TRIM 1      // 1: the data-gradient waves' epilogue and decoder on explicit register PAIRS (g, g + 1): packed fp32 multiplies / adds without
-                         // the 13 v_mov per chunk that hipcc's own pairing (j, 8 + j) needed, the phase scaling as 8 packed multiplies
-#endif
-#ifndef PIPE_FP16_OVFL
-#define PIPE_FP16_OVFL 1  // 1: MODE.FP16_OVFL set in the data-gradient waves (an overflowing f16 conversion clamps to +-65504, true infinities stay: probed,
-                          // tools/probes/probe_fp16_ovfl.hip) instead of 16 v_med3 per chunk: kernel 10.90 -> 10.76 ms (r4_pipe_ab20)
-#endif
-#ifndef PIPE_DECODE_UNDER_CHAIN
-#define PIPE_DECODE_UNDER_CHAIN 1   // 1: the data-gradient waves decode the NEXT chunk's phases behind the matrix instructions of their k-steps (the chain is
-                                    // dependent: the wave's vector issue slot idles ~900 clocks per chunk there) instead of behind the epilogue; 0: the old placement
-#endif
-#if PIPE_DECODE_UNDER_CHAIN && !PIPE_TRIM
-#error "PIPE_DECODE_UNDER_CHAIN is written on the register pairs of PIPE_TRIM"
-#endif
 typedef float v2f __attribute__((ext_vector_type(2)));
-// dz_tile on register pairs: p = acc * cos pairwise, fp32 bias sums, (saturating) fp16
+// dz_tile on explicit register PAIRS (g, g + 1), for the hidden stages' data-gradient waves: packed fp32 multiplies / adds without
+// the 13 v_mov per chunk that hipcc's own pairing (j, 8 + j) needs.  The fp16 conversion saturates through MODE.FP16_OVFL, which
+// those waves set (hidden_stage), instead of sunerf_sat16.
 __device__ __forceinline__ void dz_tile_pairs(const f32x16& acc, const v2f* cs2, half8& d0, half8& d1, v2f* bs2) {
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const v2f a = {acc[2 * q], acc[2 * q + 1]};
     const v2f p = a * cs2[q];
     bs2[q] += p;
-    const float x = PIPE_FP16_OVFL ? p.x : sunerf_sat16(p.x), y = PIPE_FP16_OVFL ? p.y : sunerf_sat16(p.y);
-    if (q < 4) { d0[2 * q] = (_Float16)x; d0[2 * q + 1] = (_Float16)y; }
-    else { d1[2 * q - 8] = (_Float16)x; d1[2 * q - 7] = (_Float16)y; }
+    if (q < 4) { d0[2 * q] = (_Float16)p.x; d0[2 * q + 1] = (_Float16)p.y; }
+    else { d1[2 * q - 8] = (_Float16)p.x; d1[2 * q - 7] = (_Float16)p.y; }
   }
 }
 // 8 phases of one fragment -> fp16 sin (in `h`) and cos pairs
@@ -340,19 +291,19 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
   // EIGHT waves, two per SIMD, with different jobs (one register budget of 256 per wave, two simple loops instead of one that
   // needs 400 registers -- hipcc rotated whole accumulator tiles between the register-file halves in that one):
   //   waves 0..3 ("data"):   dH tile 4 j + w = W_l^T dZ_l (W^T fragments resident in AGPRs), dZ_{l-1} = dH * cos -> ring, db_{l-1};
-  //                          ALL of the workgroup's DMA; the decoding of the phase stash (below)
-  //   waves 4..7 ("weight"): the 4 x 2 accumulator tiles of dW_l[:, J_j]; the hand-off protocol (wave 4)
+  //                          the decoding of the phase stash (below)
+  //   waves 4..7 ("weight"): the 4 x 2 accumulator tiles of dW_l[:, J_j]; ALL of the workgroup's DMA; the hand-off protocol (wave 4)
   // The two waves of a SIMD share its matrix pipe; while one issues LDS reads, DMA pieces or the epilogue, the other's
   // matrix instructions run.
   //
   // PHASE STASH [r4].  The forward leaves ONE 16-bit phase per pre-activation (sunerf_common.h) instead of an fp16 sin and an fp16
-  // cos: per chunk this workgroup takes in dZ_l (16 KiB) and the phases of ITS 128 features of layer l-1 (8 KiB, was 16).  Data wave
-  // w fetches the two phase fragments of its own output tile itself, and one iteration before the chunk is consumed it decodes
-  // them: sin -> fp16, written back IN PLACE (the LDS image the weight-gradient waves read with ds_read_b64_tr_b16 is the same as
-  // before), cos -> 16 registers for its own epilogue of the next iteration.  That work (2 LDS reads, 48 vector instructions
-  // 16 of them transcendental, 2 LDS writes) sat behind the epilogue until round 5 (PIPE_DECODE_UNDER_CHAIN = 0), ~650 clocks on
-  // the waves that had become the workgroup's long ones.  It depends on nothing the matrix chain produces, and that chain is 16
-  // DEPENDENT matrix instructions with an LDS wait in front of each: the wave's vector issue slot idles there.
+  // cos: per chunk this workgroup takes in dZ_l (16 KiB) and the phases of ITS 128 features of layer l-1 (8 KiB, was 16).  One
+  // iteration before the chunk is consumed data wave w decodes the two phase fragments of its own output tile: sin -> fp16,
+  // written back IN PLACE (the LDS image the weight-gradient waves read with ds_read_b64_tr_b16 is the same as before),
+  // cos -> 16 registers for its own epilogue of the next iteration.  That work (2 LDS reads, 48 vector instructions
+  // 16 of them transcendental, 2 LDS writes) depends on nothing the matrix chain produces, and that chain is 16 DEPENDENT
+  // matrix instructions with an LDS wait in front of each: the wave's vector issue slot idles there (~900 clocks per chunk),
+  // so the decoder is dealt out behind those instructions.
   // Per iteration `it`: chunk it + NBUF_H - 1 is requested, chunk it + 1's phases (requested three iterations ago; the requesting
   // wave's counted wait in front of the barrier at the top of `it` covers them, whoever that wave is) are decoded, chunk it is
   // consumed.  ORDER OF A DATA-GRADIENT WAVE'S ITERATION [r5]:
@@ -367,8 +318,7 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
   //   epilogue on the OTHER cos set `cosc2` (copied from `cosn2` at the top of the iteration: two sets live, 16 VGPRs more --
   //     the branch stays within 128), products, fp16, two stores.
   // Arithmetic and rounding are those of decode_phases_pairs (the scaling comes out as two v_mul_f32 instead of one
-  // v_pk_mul_f32: the same IEEE product); the gradients are bit-identical to the old placement's.  Measured (profiles/r5_ab/):
-  // kernel 11.05 -> 10.60 ms, data-wave k-steps 1500 -> 1705 clocks, epilogue + decoder 1030 -> 375 (stamped run).
+  // v_pk_mul_f32: the same IEEE product).  Measured against the decoder behind the epilogue: DESIGN.md section 5.4, profiles/r5_ab/.
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n_act = a.n_linear - 1, n_links = n_act - 1;
@@ -378,14 +328,12 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
   const unsigned lds_poll = lds_dummy + 1024;
   const unsigned lds_abort = lds_poll + NBUF_H * 256;      // [2]
   unsigned* status = a.ctrl;
-  // LDS IMAGE [r6].  One ds_read_b64_tr_b16 is 64 lanes x 8 B = 128 dwords over 64 banks: 2 per bank at best.  With fragments 1 KiB
-  // apart and rows in lane order (image 0) the weight-gradient waves' lanes fall on 32 banks, 4 dwords each: fragment 2T + 1
-  // (lanes 16-31, 48-63) lies 1024 B = 0 mod 256 B behind 2T, and so do rows R + 32 (+ 512 B, the lanes with p >= 2).  Image 1
-  // puts every fragment 64 B further than the last (FRAG_H = 1088): the two fragments of a pair fall on different banks, 64 banks
-  // x 2 dwords.  Image 2 also swaps rows R + 32 + 8 and R + 32 of each 16-row group pair (row r at r ^ 8 (r >> 5)), so that each
-  // half-wave alone covers the 64 banks once.  The global layouts are untouched: the DMA's per-lane SOURCE offset carries the row
-  // permutation, `voff` below, which is also the LDS offset of lane `lane`'s own row for the lane-linear readers and writers.
-  // Operands, registers and summation order are those of image 0: bit-identical gradients.
+  // LDS IMAGE.  One ds_read_b64_tr_b16 is 64 lanes x 8 B = 128 dwords over 64 banks: 2 per bank at best.  With fragments 1 KiB
+  // apart the weight-gradient waves' lanes fall on 32 banks, 4 dwords each: fragment 2T + 1 (lanes 16-31, 48-63) lies
+  // 1024 B = 0 mod 256 B behind 2T.  PAIR SKEW puts every fragment 64 B further than the last (FRAG_H = 1088): the two fragments
+  // of a pair fall on different banks, 64 banks x 2 dwords.  The global layouts are untouched, and operands, registers and
+  // summation order are those of the unskewed image: bit-identical gradients (measured: DESIGN.md section 5.4, profiles/r6_ab/).
+  // `voff` is the LDS offset of lane `lane`'s own row for the lane-linear readers and writers, and the DMA's per-lane source offset.
   const unsigned voff = frag_row_offset(lane);
 
   char* ring_in = TOP ? nullptr : a.rings + ((size_t)P * n_links + l) * RING * SLOT;
@@ -399,7 +347,7 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
   // iteration of lead the stage above must have, and one more before this stage's own outputs count as published (in-order
   // vmcnt).  ZD = 2 iterations (~6000 clocks, an L2 read takes ~1000) leaves 9 of the ring's 16 slots as slack, 4 gave 6.
   // The top stage reads dZ_top from HBM, ungated: it keeps the long distance.
-  constexpr int ZD = TOP ? NBUF_H - 1 : PIPE_ZD;
+  constexpr int ZD = TOP ? NBUF_H - 1 : ZD_HIDDEN;
   // wave-uniform sources / LDS destinations of the pieces being fetched, set at the top of an iteration: dZ of chunk it + ZD,
   // phases of chunk it + NBUF_H - 1 (both into the staging buffer of their chunk, chunk % NBUF_H)
   const char *nz = nullptr, *np = nullptr;
@@ -438,49 +386,32 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
     else dma_piece_s<2>(nz + (size_t)f * 1024, voff, dst);
   };
   auto piece_p = [&](int f) __attribute__((always_inline)) { dma_piece_s<1>(np + (size_t)f * 1024, voff, preal ? pdst + f * FRAG_H : lds_dummy); };
-  // WHO ISSUES THE PIECES (PIPE_DMA_ON_WEIGHT): 0 = the data-gradient waves, between their matrix instructions (4 dZ fragments +
-  // the 2 phase fragments of the wave's own tile each); 1 = the phase fragments by the weight-gradient waves (2 each, between
-  // THEIR matrix instructions); 2 = everything by the weight-gradient waves (4 + 2 each).  A piece holds the issuing wave for
-  // 100 - 200 clocks; behind the barrier the weight-gradient waves have ~1000 clocks to spare per chunk, the data-gradient waves
-  // -- the workgroup's long ones since they decode the phases -- none.
-  // Counted waits (vmcnt counts in issue order).  Data-gradient waves, per iteration z z z z p p s s (mode 0), z z z z s s (1),
-  // s s (2): at the top of iteration `it` dZ of chunk `it` (issued in it - ZD) and the phases of chunk it + 1 (issued in it - 3)
-  // must have landed if the wave fetched them itself: at most WAIT_LEFT younger operations outstanding; the stores of iteration
-  // it - DRAIN come before all of those: chunk it - DRAIN of this stage's output is complete, which is what wave 4 publishes.
-  // Weight-gradient waves, per iteration [flag store, poll (wave 4)] then their pieces: W_WAIT younger operations (below).
-  constexpr int NO = 2;
-  constexpr int NP_D = PIPE_DMA_ON_WEIGHT == 0 ? 6 : PIPE_DMA_ON_WEIGHT == 1 ? 4 : 0;      // (mode 2: none)      // pieces per data-gradient wave and iteration
-  constexpr int NP_W = 6 - NP_D;                                                           // ... per weight-gradient wave
-  constexpr int PER_D = NP_D + NO;
-  auto min3 = [](int x, int y, int z) constexpr { return x < y ? (x < z ? x : z) : (y < z ? y : z); };
-  // z's are the oldest four operations of their iteration, p's the next two, the stores the youngest two
-  constexpr int WAIT_LEFT = NP_D == 0 ? NO : min3((ZD - 1) * PER_D + (NP_D - 4) + NO, NP_D == 6 ? 2 * PER_D + NO : 63, 2 * PER_D);
-  constexpr int DRAIN = (WAIT_LEFT + PER_D - 1) / PER_D + 1;      // smallest k with WAIT_LEFT <= (k - 1) PER_D
-  // weight-gradient wave v, per iteration [flag store, poll: wave 4 only] z z z z p p (mode 2) / p p (mode 1): dZ of chunk `it`
-  // was issued in it - ZD, the phases of chunk it + 1 in it - 3, the poll read now in it - PIPE_POLL_LAG
-  auto w_wait = [min3](int per_w, bool gate_wave) constexpr {
-    return min3(NP_W == 6 ? (ZD - 1) * per_w + 2 : 63, NP_W >= 2 ? 2 * per_w : 63, gate_wave ? PIPE_POLL_LAG * per_w - 2 : 63);
-  };
-  constexpr int W_WAIT_GATE = w_wait(NP_W + 2, true), W_WAIT_REST = w_wait(NP_W, false);
+  // WHO ISSUES THE PIECES.  The weight-gradient waves issue all of them, between THEIR matrix instructions: wave v the dZ
+  // fragments v, 4 + v, 8 + v, 12 + v and the phase fragments 2 v, 2 v + 1.  A piece holds the issuing wave for 100 - 200 clocks;
+  // behind the barrier the weight-gradient waves have ~1000 clocks to spare per chunk, the data-gradient waves -- the workgroup's
+  // long ones since they decode the phases -- none.  (The data-gradient waves issuing all or four of the six, and three more
+  // splits, were measured slower and removed: commit cafd360 has them, README.md and tools/experiments/README.md the numbers.)
+  // Counted waits (vmcnt counts in issue order; the operand is the number of YOUNGER operations that may still be in flight).
+  // Data-gradient waves: two output stores per iteration and nothing else.  WAIT_LEFT = 2 at the top of iteration `it` leaves the
+  // stores of it - 1 in flight: the output of chunk it - DRAIN, DRAIN = 2, is complete, which is what wave 4 publishes.
+  // Weight-gradient waves, per iteration [flag store, poll: wave 4 only] z z z z p p, 8 (wave 4) or 6 operations.  At the top of
+  // `it` must have landed: dZ of chunk `it`, issued in it - ZD (younger: that iteration's p p and ZD - 1 whole iterations); the
+  // phases of chunk it + 1, issued last in it - 3 (younger: two whole iterations); wave 4's poll read now, issued second in
+  // it - POLL_LAG (younger: its six pieces and POLL_LAG - 1 whole iterations).
+  //   wave 4: min(8 (ZD - 1) + 2, 16, 8 POLL_LAG - 2) = 10 (top stage, ZD = 4: 14);  the others: min(6 (ZD - 1) + 2, 12) = 8 (top: 12)
+  constexpr int WAIT_LEFT = 2, DRAIN = 2;
+  constexpr int W_WAIT_GATE = TOP ? 14 : 10, W_WAIT_REST = TOP ? 12 : 8;
+  static_assert(ZD == (TOP ? 4 : 2) && POLL_LAG == 2, "the counted waits are derived for these distances");
 
   static_assert(W_WAIT_GATE >= 0 && W_WAIT_GATE < 64 && WAIT_LEFT < 64, "vmcnt is a 6-bit counter");
   static_assert(ZD >= 1 && ZD <= NBUF_H - 1, "dZ fetch distance");
 
   if (wave < 4) {
     // =============================================== data-gradient waves ===============================================
-#if defined(PIPE_PRIO) && PIPE_PRIO == 1
-    __builtin_amdgcn_s_setprio(1);
-#endif
-    // output stores / DMA pieces (dZ fragments w, 4 + w, 8 + w, 12 + w; phase fragments 2 w, 2 w + 1 of this wave's own tile) per iteration
-#ifndef PIPE_PF
-#define PIPE_PF 2
-#endif
-    // B fragments requested PF k-steps ahead of their matrix instructions.  On image 0 four were best (round 5: PF = 2 +0.22 ms, 6 +0.09 ms;
-    // round 6: image 0 with PF = 2 +0.30 ms): the reads wait behind the weight-gradient waves' operand reads, which start at the same
-    // barrier and are replayed four-fold there.  On the skewed images those take half the LDS cycles or fewer, and two reads ahead are
-    // enough: kernel, same-call medians against the parent (profiles/r6_ab/r6_pipe_ab2.log, ab3.log): image 2 with PF = 1 / 2 / 3 / 4 / 6
-    // -0.05 / -0.22 .. -0.32 / -0.13 / -0.20 / -0.17 ms, image 1 with PF = 2 / 6 -0.29 / -0.25 ms
-    constexpr int PF = PIPE_PF;
+    // B fragments requested PF k-steps ahead of their matrix instructions.  The reads wait behind the weight-gradient waves'
+    // operand reads, which start at the same barrier; on the skewed image those take half the LDS cycles of the unskewed one, and
+    // two reads ahead are enough (4 and 6 measured slower: DESIGN.md section 5.4, profiles/r6_ab/).
+    constexpr int PF = PF_HIDDEN;
     const int U = 4 * j + wave;                      // output tile: features 32 U .. 32 U + 31 of layer l-1
     const int li = (a.n_linear - 2) - l;
     half8 wt_hi[PKS], wt_lo[HI_ONLY ? 1 : PKS];
@@ -498,19 +429,12 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
       }
     }
     char* scratch = a.rings + (size_t)a.NP * n_links * RING * SLOT + ((size_t)blockIdx.x * 4 + wave) * 2048;
-    // cos of this wave's tile for the chunk consumed NEXT (decoded one iteration ahead), and the decoder: the two phase fragments
-    // of the tile (this wave's OWN DMA pieces: its counted wait covers them) -> fp16 sin in place (the H image of the
-    // weight-gradient waves, who see it behind the next barrier) + cos here.  `decode` is the whole decoder in one block: the
-    // prologue iteration that decodes chunk 0, and every iteration of the old placement (behind the epilogue).  The main loop
-    // deals the same work out over its k-steps (PIPE_DECODE_UNDER_CHAIN, see the order of an iteration above).
-    // Measured alternatives (tools/experiments/README.md).  Round 4, when the data-gradient waves still issued DMA pieces between
-    // their matrix instructions (behind the epilogue: kernel 12.0 ms): dealt out over the k-steps 12.2 (k-steps 1050 -> 2120
-    // clocks), the sin half on the weight-gradient waves 12.9, all DMA on the weight-gradient waves 13.5.  Round 5, k-step loop free
-    // of vector-memory operations (behind the epilogue: 11.05): one phase per k-step 10.60; the 16 register moves cosn2 -> cosc2
-    // dealt out as well 10.57 against 10.58 in that call (noise: not kept); two phases per k-step on the last eight k-steps only
-    // 11.17 against 11.04 in that call (a slower box: parent 11.46).
-    float cosn[16];
-    v2f cosn2[8];      // (PIPE_TRIM) the same as pairs (g, g + 1)
+    // cos of this wave's tile for the chunk consumed NEXT (decoded one iteration ahead), as pairs (g, g + 1), and the decoder: the
+    // two phase fragments of the tile -> fp16 sin in place (the H image of the weight-gradient waves, who see it behind the next
+    // barrier) + cos here.  `decode` is the whole decoder in one block, for the prologue iteration that decodes chunk 0.  The
+    // main loop deals the same work out over its k-steps (see the order of an iteration above; measured alternatives:
+    // tools/experiments/README.md).
+    v2f cosn2[8];
     typedef __attribute__((address_space(3))) v4u lds_v4u;
     typedef __attribute__((address_space(3))) half8 lds_half8;
     v4u dp[2];
@@ -521,31 +445,19 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
     };
     auto decode = [&](int b) __attribute__((always_inline)) {
       const unsigned at = lds0 + b * BUF_HID + (16 + 2 * wave) * FRAG_H + voff;
-      if (PIPE_TRIM) {
-        const half8 h0 = decode_phases_pairs(dp[0], cosn2), h1 = decode_phases_pairs(dp[1], cosn2 + 4);
-        *(lds_half8*)(uintptr_t)at = h0;
-        *(lds_half8*)(uintptr_t)(at + FRAG_H) = h1;
-        return;
-      }
-      float sn[16];
-      decode_phases(dp[0], sn, cosn);
-      decode_phases(dp[1], sn + 8, cosn + 8);
-      *(lds_half8*)(uintptr_t)at = to_half8(sn);
-      *(lds_half8*)(uintptr_t)(at + FRAG_H) = to_half8(sn + 8);
+      const half8 h0 = decode_phases_pairs(dp[0], cosn2), h1 = decode_phases_pairs(dp[1], cosn2 + 4);
+      *(lds_half8*)(uintptr_t)at = h0;
+      *(lds_half8*)(uintptr_t)(at + FRAG_H) = h1;
     };
-    // prologue iterations -(NBUF_H-1) .. -1: DMA only (+ two dummy stores: the same vmcnt accounting as a full iteration); the
-    // last of them decodes chunk 0
+    // prologue iterations -(NBUF_H-1) .. -1: two dummy stores (the same vmcnt accounting as a full iteration); the last of them
+    // decodes chunk 0
     bool stop = false;
     for (int it = -(NBUF_H - 1); it < 0; ++it) {
       asm volatile("s_waitcnt vmcnt(%0)" :: "i"(WAIT_LEFT) : "memory");
       barrier_mem();
       const unsigned ab = lds_ld(lds_abort + (it & 1) * 4);
-      if (NP_D >= 4) next_z(it + ZD);
-      if (NP_D == 6) next_p(it + NBUF_H - 1);
       const Rsrc sc = make_rsrc(scratch, 2048);
       const half8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (NP_D >= 4) { piece_z(wave); piece_z(4 + wave); piece_z(8 + wave); piece_z(12 + wave); }
-      if (NP_D == 6) { piece_p(2 * wave); piece_p(2 * wave + 1); }
       buf_store(zero, sc, 0);
       buf_store(zero, sc, 1024);
       if (ab) { stop = true; break; }
@@ -556,13 +468,12 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
     const bool stamp = a.dbg != nullptr;
     char* out_z = ring_out;                        // ring slot of this iteration's output
     int out_slot = 0, buf = 0;                     // buf = it % NBUF_H
-    float bs[16];                                  // this lane's share of db_{l-1}[32 U ..]: fp32 sums of dH * cos
-    v2f bs2[8];
-#pragma unroll
-    for (int g = 0; g < 16; ++g) bs[g] = 0.f;
+    v2f bs2[8];                                    // this lane's share of db_{l-1}[32 U ..]: fp32 sums of dH * cos, pairs (g, g + 1)
 #pragma unroll
     for (int q = 0; q < 8; ++q) bs2[q] = (v2f){0.f, 0.f};
-    if (PIPE_FP16_OVFL) __builtin_amdgcn_s_setreg(1 | (23 << 6) | (0 << 11), 1);      // hwreg(HW_REG_MODE, 23, 1) = FP16_OVFL
+    // MODE.FP16_OVFL: an overflowing f16 conversion clamps to +-65504, true infinities stay (tools/probes/probe_fp16_ovfl.hip) --
+    // the saturation of dz_tile_pairs without 16 v_med3 per chunk
+    __builtin_amdgcn_s_setreg(1 | (23 << 6) | (0 << 11), 1);      // hwreg(HW_REG_MODE, 23, 1) = FP16_OVFL
     for (int it = 0; it < (stop ? 0 : n_my); ++it) {
       unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0;
       if (stamp) s0 = __builtin_amdgcn_s_memtime();
@@ -576,18 +487,12 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
       // abort word of this iteration: requested now, looked at when the iteration's work is done (every wave leaves in the same
       // iteration, so the barrier counts still agree; what a doomed iteration computes and stores is garbage either way)
       const unsigned ab = lds_ld(lds_abort + (it & 1) * 4);
-      if (NP_D >= 4) next_z(it + ZD);
-      if (NP_D == 6) next_p(it + NBUF_H - 1);
       const char* B = smem + (size_t)buf * BUF_HID;
       f32x16 dacc = {0};
       half8 bf[PF + 1];
-      float cosc[16];                              // cos of the chunk consumed now (decoded in the previous iteration)
-      v2f cosc2[8];
-#pragma unroll
-      for (int g = 0; g < 16; ++g) cosc[g] = cosn[g];
+      v2f cosc2[8];                                // cos of the chunk consumed now (decoded in the previous iteration)
 #pragma unroll
       for (int q = 0; q < 8; ++q) cosc2[q] = cosn2[q];
-#if PIPE_DECODE_UNDER_CHAIN
       // the next chunk's two phase fragments, in front of the first B fragment: the loop's lgkmcnt(PF - 1) waits count past them.
       // (Unconditional: in the last iteration the buffer holds stale bytes of this wave's own region, the results are not stored.)
       read_phases(nbuf);
@@ -595,7 +500,6 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
       half8 hn[2];         // fp16 sin of the two fragments, written back behind the last matrix instruction
       v2f dr = {0.f, 0.f};  // the scaled phase pair in flight between an even k-step and the odd one behind it
       float ds0 = 0.f;
-#endif
 #pragma unroll
       for (int s = 0; s < PF; ++s) bf[s] = *(const half8*)(B + s * FRAG_H + voff);
 #pragma unroll
@@ -603,39 +507,22 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
         if (ks + PF < PKS) bf[(ks + PF) % (PF + 1)] = *(const half8*)(B + (ks + PF) * FRAG_H + voff);
         if constexpr (!HI_ONLY) dacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wt_lo[ks], bf[ks % (PF + 1)], dacc, 0, 0, 0);
         dacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wt_hi[ks], bf[ks % (PF + 1)], dacc, 0, 0, 0);
-        if (NP_D >= 4) {
-          if (ks == 0) piece_z(wave);
-          if (ks == 2) piece_z(4 + wave);
-          if (ks == 4) piece_z(8 + wave);
-          if (ks == 6) piece_z(12 + wave);
-        }
-        if (NP_D == 6) {
-          if (ks == 8) piece_p(2 * wave);
-          if (ks == 10) piece_p(2 * wave + 1);
-        }
-#if PIPE_DECODE_UNDER_CHAIN
         // one phase per k-step behind its matrix instruction(s): k-steps 2 q, 2 q + 1 decode dword q & 3 of fragment q >> 2
         __builtin_amdgcn_sched_barrier(0);
         if ((ks & 1) == 0) decode_pair_first(dp[ks >> 3][(ks >> 1) & 3], dr, cosn2[ks >> 1], ds0);
         else decode_pair_second(dr, cosn2[ks >> 1], ds0, hn[ks >> 3], (ks >> 1) & 3);
-#else
-        if (ks == 12 && decode_next) read_phases(nbuf);      // the next chunk's phases, decoded behind the epilogue
-#endif
         __builtin_amdgcn_sched_barrier(0);
       }
-#if PIPE_DECODE_UNDER_CHAIN
       if (decode_next) {
         const unsigned at = lds0 + nbuf * BUF_HID + (16 + 2 * wave) * FRAG_H + voff;
         *(lds_half8*)(uintptr_t)at = hn[0];
         *(lds_half8*)(uintptr_t)(at + FRAG_H) = hn[1];
       }
-#endif
       if (stamp) { asm volatile("" :: "v"(dacc)); s3 = __builtin_amdgcn_s_memtime(); }
       // dZ_{l-1} = dH * cos (fp16, saturating) -> ring slot, fragments 2 U, 2 U + 1 of the chunk
       half8 d0, d1;
       const Rsrc ro = make_rsrc(out_z, SLOT);
-      if (PIPE_TRIM) dz_tile_pairs(dacc, cosc2, d0, d1, bs2);
-      else dz_tile(dacc, cosc, cosc + 8, d0, d1, bs);
+      dz_tile_pairs(dacc, cosc2, d0, d1, bs2);
       unsigned long long s3a = 0, s3b = 0;
       if (stamp) { asm volatile("" :: "v"(d0), "v"(d1)); s3a = __builtin_amdgcn_s_memtime(); }
       buf_store(d0, ro, (2 * U) * 1024);
@@ -644,9 +531,6 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
       out_slot = out_slot + 1 == RING ? 0 : out_slot + 1;
       out_z = out_slot == 0 ? ring_out : out_z + SLOT;
       buf = nbuf;
-#if !PIPE_DECODE_UNDER_CHAIN
-      if (decode_next) decode(buf);
-#endif
       if (stamp) {
         const unsigned long long s4 = __builtin_amdgcn_s_memtime();
         ph[0] += s1 - s0; ph[1] += s2 - s1; ph[2] += s3 - s2; ph[3] += s4 - s3; ph[4] += s3a - s3; ph[5] += s3b - s3;
@@ -658,10 +542,9 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
     barrier_mem();
     // db_{l-1}, row tile U, of this pipeline: the bias column of layer l-1's partial-sum slot (every slot is written exactly once:
     // a workgroup without chunks writes its zeros)
-    if (PIPE_TRIM) {
+    float bs[16] = {0};      // (store_bias_sums takes scalars; without the initialiser hipcc allocates the decoder's registers differently)
 #pragma unroll
-      for (int q = 0; q < 8; ++q) { bs[2 * q] = bs2[q].x; bs[2 * q + 1] = bs2[q].y; }
-    }
+    for (int q = 0; q < 8; ++q) { bs[2 * q] = bs2[q].x; bs[2 * q + 1] = bs2[q].y; }
     store_bias_sums(bs, a.partial + ((size_t)(l - 1) * a.NP + P) * (PT * (PT + 1)) * 1024 + ((size_t)U * (PT + 1) + PT) * 1024);
     if (stamp && P == 0 && lane == 0) {      // timeline of iteration n_my / 2: [workgroup of the pipeline][wave][8] 64-bit shader clocks
       unsigned long long* t = (unsigned long long*)(a.dbg + 256 * 8 * 4) + (((size_t)(blockIdx.x >> 3) * 8 + wave) * 8);
@@ -675,9 +558,6 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
   }
 
   // ================================================= weight-gradient waves =================================================
-#if defined(PIPE_PRIO) && PIPE_PRIO == 2
-  __builtin_amdgcn_s_setprio(1);
-#endif
   const int v = wave - 4;
   const bool gatew = v == 0;      // the protocol wave: publishes this workgroup's counters, polls the partners', gates the next iteration
   // block of this wave: row tiles 4 rq .. +3 (features of dZ_l), column tiles 2 cq, 2 cq + 1 of J_j (db_l is summed where dZ_l is
@@ -733,20 +613,20 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
   }
 
   bool aborted = false;
-  // These waves issue no DMA (round 4: every piece of the workgroup goes through the data-gradient waves); wave 4 has the two
-  // vector-memory operations of the protocol per iteration (flag store, poll).  The two waves of a SIMD share its matrix pipe:
+  // These waves issue every DMA piece of the workgroup; wave 4 also has the two vector-memory operations of the protocol per
+  // iteration (flag store, poll).  The two waves of a SIMD share its matrix pipe:
   // the data wave starts its matrix instructions right behind the barrier, this wave's 16 follow its operand reads.
   // top(): counted wait (wave 4), barrier, abort word, wave 4's publication and poll.
   unsigned long long tw = 0, tb = 0;       // SUNERF_PIPE_DEBUG: shader clocks in the counted wait / the barrier
   unsigned long long t_wait = 0, t_bar = 0, tl[6] = {0, 0, 0, 0, 0, 0};
   const bool stamp = a.dbg != nullptr;
-  int pslot = PIPE_POLL_LAG;               // the poll issued in iteration `it` lands in LDS slot (it + PIPE_POLL_LAG) % NBUF_H, read in iteration it + PIPE_POLL_LAG
+  int pslot = POLL_LAG;                    // the poll issued in iteration `it` lands in LDS slot (it + POLL_LAG) % NBUF_H, read in iteration it + POLL_LAG
   auto top = [&](int it) __attribute__((always_inline)) {
     unsigned long long sa = 0, sb = 0;
     if (stamp) sa = __builtin_amdgcn_s_memtime();
-    // (the poll issued PIPE_POLL_LAG iterations ago and this wave's pieces of chunk `it` / phases of chunk it + 1 have landed)
+    // (the poll issued POLL_LAG iterations ago and this wave's pieces of chunk `it` / phases of chunk it + 1 have landed)
     if (gatew) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(W_WAIT_GATE) : "memory");
-    else if (NP_W) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(W_WAIT_REST) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" :: "i"(W_WAIT_REST) : "memory");
     if (stamp) sb = __builtin_amdgcn_s_memtime();
     barrier_mem();
     if (stamp) { t_wait = sb; t_bar = __builtin_amdgcn_s_memtime(); tw += sb - sa; tb += t_bar - sb; }
@@ -758,22 +638,22 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
         const int pv = lane == 0 ? it + 1 : it - DRAIN + 1;
         st_agent(lane == 0 ? my_cons : my_prod, (unsigned)(pv > 0 ? pv : 0));
       }
-      // ... then the poll whose value is read PIPE_POLL_LAG iterations on
+      // ... then the poll whose value is read POLL_LAG iterations on
       pslot = pslot + 1 == NBUF_H ? 0 : pslot + 1;
       dma_poll(poll_src, lds_poll + pslot * 256);
     }
     return ab;
   };
-  // this wave's pieces of an iteration (modes 1, 2): dZ fragments v, 4 + v, 8 + v, 12 + v of chunk it + ZD, phase fragments 2 v, 2 v + 1
+  // this wave's pieces of an iteration: dZ fragments v, 4 + v, 8 + v, 12 + v of chunk it + ZD, phase fragments 2 v, 2 v + 1
   // of chunk it + NBUF_H - 1; `q` = 0 .. 5 in the order z z z z p p
   auto w_piece = [&](int q) __attribute__((always_inline)) {
-    if (q < 4) { if (NP_W == 6) piece_z(4 * q + v); }
-    else if (NP_W >= 2) piece_p(2 * v + q - 4);
+    if (q < 4) piece_z(4 * q + v);
+    else piece_p(2 * v + q - 4);
   };
   for (int it = -(NBUF_H - 1); it < 0; ++it) {      // prologue iterations: protocol (+ this wave's pieces of the first chunks)
     const unsigned ab = top(it);
-    if (NP_W == 6) next_z(it + ZD);
-    if (NP_W >= 2) next_p(it + NBUF_H - 1);
+    next_z(it + ZD);
+    next_p(it + NBUF_H - 1);
 #pragma unroll
     for (int q = 0; q < 6; ++q) w_piece(q);
     if (ab) { aborted = true; break; }
@@ -786,8 +666,8 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
     unsigned long long s0 = 0, s1 = 0, s2 = 0;
     if (stamp) s0 = __builtin_amdgcn_s_memtime();
     const unsigned ab = top(it);
-    if (NP_W == 6) next_z(it + ZD);
-    if (NP_W >= 2) next_p(it + NBUF_H - 1);
+    next_z(it + ZD);
+    next_p(it + NBUF_H - 1);
     if (stamp) s1 = __builtin_amdgcn_s_memtime();
     // operand bases of this wave's block: row tiles r0.. of the dZ fragments, column tiles c0.. of the H fragments (fp16 sin,
     // decoded in place by the data-gradient waves one iteration ago); the tile and k-step parts of the addresses are immediates
@@ -832,7 +712,7 @@ __device__ __forceinline__ void hidden_stage(const PipeArgs& a, char* smem, int 
         const half8 af = ks ? A1[i] : A0[i];
         mfma_agpr(acc[i][0], af, bf0);
         mfma_agpr(acc[i][1], af, bf1);
-        if (4 * ks + i < NP_W) w_piece(6 - NP_W + 4 * ks + i);      // one piece behind each of the first pairs of matrix instructions
+        if (4 * ks + i < 6) w_piece(4 * ks + i);      // one piece behind each of the first six pairs of matrix instructions
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -954,9 +834,6 @@ __device__ __forceinline__ void in_stage(const PipeArgs& a, char* smem, int P, i
     }
     issue_chunk(nxt, nxt & (NBUF - 1));
     if (it < 0) continue;
-#if defined(PIPE_ABL_IN_STAGE) && PIPE_ABL_IN_STAGE
-    continue;       // timing-only knock-out (round 4): the in-layer stage keeps its protocol and its DMA, computes nothing
-#endif
     const unsigned bufA = lds0 + buf * BUF_IN + laneoff, bufB = bufA + 8 * 1024;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {

@@ -116,22 +116,9 @@ struct PairTmp {
   float s0, s1, r0, r1, c0, c1;
   half2v hi, cpk;
 };
-#ifndef SUNERF_ABL_NO_TRANS
-#define SUNERF_ABL_NO_TRANS 0
-#endif
 constexpr int XL_SHIFT = 17;      // log2 of the factor on the fp8 remainder operand (folded into its conversion, undone by the block scale)
-#ifndef SUNERF_ABL_NO_L8
-#define SUNERF_ABL_NO_L8 0        // the remainder's scale + fp8 conversion (3 vector instructions per pair micro-op) not issued
-#endif
 template <int STASH>
 __device__ __forceinline__ void epi_stage_a(const f32x16& acc, int p, PairTmp& t) {
-#if SUNERF_ABL_NO_TRANS
-  t.s0 = __builtin_amdgcn_fractf(acc[2 * p]);
-  t.s1 = __builtin_amdgcn_fractf(acc[2 * p + 1]);
-  if (STASH) { t.c0 = t.s0; t.c1 = t.s1; }
-  asm volatile("" : "+v"(t.s0), "+v"(t.s1));
-  return;
-#endif
   t.s0 = __builtin_amdgcn_sinf(acc[2 * p]);
   t.s1 = __builtin_amdgcn_sinf(acc[2 * p + 1]);
   asm volatile("" : "+v"(t.s0), "+v"(t.s1));
@@ -279,12 +266,6 @@ struct Mlp {
   static __device__ __forceinline__ void start(Ring<D>& ring, Pipe& p) {
     ring.template issue_page<0>();
     ring.template issue_page<0>();
-#if SUNERF_ABL_NO_DMA
-    ring.template issue_page<0>();
-    ring.template issue_page<0>();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ring.priming = false;
-#endif
     ring.acquire();
     // the pass starts at page phase 0, i.e. in the middle of a trickle cycle that began at the acquire phase: deal out
     // the pieces of page 2 that the k-steps between the acquire phase and the page end would have issued
@@ -468,20 +449,6 @@ struct Mlp {
   }
 };
 
-#ifndef SUNERF_PIN_MFMA
-#define SUNERF_PIN_MFMA 1
-#endif
-// Energy ablations (tools/energy_ablation.sh; results in DESIGN.md section 10): each removes ONE kind of work from the hidden
-// tiles of the fp8c forward while every operand stays finite -- the outputs are wrong, the time tells what that work costs.
-#ifndef SUNERF_ABL_NO_AREAD
-#define SUNERF_ABL_NO_AREAD 0     // weight operands are not re-read from LDS (the first group's stay in registers)
-#endif
-#ifndef SUNERF_ABL_NO_TRANS
-#define SUNERF_ABL_NO_TRANS 0     // v_fract instead of v_sin (/ v_cos) in the epilogue
-#endif
-#ifndef SUNERF_BATCH_READS
-#define SUNERF_BATCH_READS 1
-#endif
 // ---- d <= 256: fp16 head product + two block-scaled fp8 correction products (format: sunerf_common.h, "fp8c") ----------
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -511,10 +478,6 @@ __device__ __forceinline__ void epi_stage_c8(const PairTmp& t, int p, int FP, ha
   // a neighbouring dword when the two halves of a dword are written by different micro-ops.  Round 2: the instruction through
   // inline asm with the dword tied in and out -- 16 vector instructions fewer per tile in a kernel bound by its one wave's issue
   // slots (a vector instruction costs that wave ~4.8 cycles, tools/probes/probe_valu_cost.hip).
-#if SUNERF_ABL_NO_L8   // issue-slot ablation: 3 of the ~17 vector instructions of a pair micro-op are not issued
-  if (dq & 1) w8h[d] = __builtin_amdgcn_cvt_pk_fp8_f32(t.s0, t.s1, w8h[d], true);
-  else w8h[d] = __builtin_amdgcn_cvt_pk_fp8_f32(t.s0, t.s1, w8h[d], false);
-#else
   // (the scaled conversion divides by its scale operand; 2^XL_SHIFT puts |remainder| <= 2^-12 at <= 32, i.e. every remainder
   // above 2^-23 into e4m3's normal range; the matrix instruction's block scale of this operand is 127 - XL_SHIFT.  The head's
   // conversion merges into the dword's stale content: the other word is rewritten by the neighbouring micro-op anyway)
@@ -526,7 +489,6 @@ __device__ __forceinline__ void epi_stage_c8(const PairTmp& t, int p, int FP, ha
     w8h[d] = __builtin_amdgcn_cvt_pk_fp8_f32(t.s0, t.s1, w8h[d], false);
     asm volatile("v_cvt_scalef32_pk_fp8_f32 %0, %1, %2, %3" : "+v"(w8l[d]) : "v"(t.r0), "v"(t.r1), "s"(cvt_scale));
   }
-#endif
   if (STASH) {
     if (p < 4) { ch0[2 * p] = t.cpk[0]; ch0[2 * p + 1] = t.cpk[1]; }
     else { ch1[2 * p - 8] = t.cpk[0]; ch1[2 * p - 7] = t.cpk[1]; }
@@ -676,11 +638,9 @@ struct Mlp8 : Mlp<D> {
         } else {
           accc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(q.ah8[slot8], xl8[g], accc, 0, 0, 0, sc.a_hi, 0, 127 - XL_SHIFT);
         }
-#if SUNERF_PIN_MFMA
         // the matrix instruction opens its segment: what follows runs in ITS shadow (without this the scheduler is free to
         // move it to the end of the segment, i.e. behind work that was sized for the previous instruction)
         __builtin_amdgcn_sched_barrier(0);
-#endif
         if (HAS_PREV) {
           if (PER == 0) {
             // The previous tile's two accumulators are summed in segment 2, behind two of this tile's matrix instructions
@@ -724,15 +684,7 @@ struct Mlp8 : Mlp<D> {
           }
         }
         // in-place prefetch of the next group's operand
-        if (SUNERF_ABL_NO_AREAD) {
-          // (opaque to the optimiser, or it folds the matrix instructions that now see the same operand again)
-          if (sg == 5) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(q.a16[slot8][i]));
-            asm volatile("" : "+v"(q.al8[slot8]), "+v"(q.ah8[slot8]));
-          }
-        } else if (RS0 >= 0) {
-#if SUNERF_BATCH_READS
+        if (RS0 >= 0) {
           // all reads of the next group behind the two long (84-cycle) fp8 instructions: the four fp16 operands after the
           // first, the two fp8 operands after the second.  One s_waitcnt per batch instead of one per matrix instruction,
           // and the 32-cycle fp16 segments keep their few issue slots for the epilogue.
@@ -743,11 +695,6 @@ struct Mlp8 : Mlp<D> {
             q.al8[slot8] = lds_v8i(lb.at(nbo + 4096), lb.at(nbo + 5120));
             q.ah8[slot8] = lds_v8i(lb.at(nbo + 6144), lb.at(nbo + 7168));
           }
-#else
-          if (sg < 4) q.a16[slot8][sg] = lds_half8(lb.at(nbo + sg * 1024));
-          else if (sg == 4) q.al8[slot8] = lds_v8i(lb.at(nbo + 4096), lb.at(nbo + 5120));
-          else q.ah8[slot8] = lds_v8i(lb.at(nbo + 6144), lb.at(nbo + 7168));
-#endif
         } else {
           if (sg < 4) q.a16[slot8][sg] = *(const half8*)(nb + sg * 1024);
           else if (sg == 4) q.al8[slot8] = load8(nb + 4096);
@@ -900,12 +847,10 @@ struct Mlp8 : Mlp<D> {
 #define SUNERF_TILE8(UU)                                                                                             \
       if (U == UU) {                                                                                                   \
         constexpr int RS = RS_HIDDEN < 0 ? -1 : (RS_HIDDEN + UU * KS) % RING_STEPS;                                    \
-        ring.mark_begin(UU == 0 ? 1 : (UU % 2 ? 2 : 3));   /* debug builds: 1 carry tile, 2 / 3 odd / even tile */      \
         if (UU == 0) acc = tile8<true, RS, STASH>(ring, p, q, acc, xhi, xh8, xl8, sc, prev, pc, XL, xhi, xh8, xl8, w8h, w8l, st, \
                                                   st_prev + XL * 1024, CD);                                           \
         else acc = tile8<true, RS, STASH>(ring, p, q, acc, xhi, xh8, xl8, sc, prev, pc, 2 * UU - 2, yhi, yh8, yl8, w8h, w8l, st, \
                                           st_own + (2 * UU - 2) * 1024, CD);                                          \
-        ring.mark_end(UU == 0 ? 1 : (UU % 2 ? 2 : 3));                                                                  \
       }
       SUNERF_TILE8(0) SUNERF_TILE8(1) SUNERF_TILE8(2) SUNERF_TILE8(3) SUNERF_TILE8(4) SUNERF_TILE8(5) SUNERF_TILE8(6) SUNERF_TILE8(7)
 #undef SUNERF_TILE8
@@ -948,7 +893,6 @@ __global__ __launch_bounds__(THREADS, 1) void render_fwd_kernel(RenderArgs a) {
   typename M::Pipe pipe;
   pipe.frag = slot + lane * 16;
   M::start(ring, pipe);
-  ring.mark_begin(6);   // debug builds: 6 = the whole kernel after start-up
   const int S = a.S;
   const int n_chunks = (S + 31) >> 5;
   const int64_t n_groups = (a.n_rays + WAVES - 1) / WAVES;
@@ -1084,16 +1028,7 @@ __global__ __launch_bounds__(THREADS, 1) void render_fwd_kernel(RenderArgs a) {
           }
         }
         v8i w8h = {0}, w8l = {0};                              // fp8 operands of the group under construction
-#if SUNERF_DBG_BARRIER
-        ring.dbg_kind = 0;
-#endif
-        ring.mark_end(5);
-        ring.mark_begin(0);
         f32x16 carry = M8::template in_layer<STASH>(ring, pipe, bias, h, e_hi, e_lo, xa_hi, xa_h8, xa_l8, w8h, w8l, st, (int)SL.h_off(0));
-        ring.mark_end(0);
-#if SUNERF_DBG_BARRIER
-        ring.dbg_kind = 1;
-#endif
         typename M8::Pipe8 q8;
         f32x16 pc = {0};                                       // correction accumulator of the pending tile (in layer: none)
         M8::preload(pipe, q8, M::RS_HIDDEN >= 0 ? M::RS_HIDDEN : pipe.rstep);
@@ -1110,19 +1045,10 @@ __global__ __launch_bounds__(THREADS, 1) void render_fwd_kernel(RenderArgs a) {
                                                    xb_l8, xa_hi, xa_h8, xa_l8, w8h, w8l, carry, pc, st, (int)SL.h_off(l), (int)SL.h_off(l + 1));
         }
         if (l < a.n_linear - 1) {
-#if SUNERF_DBG_BARRIER
-          ring.dbg_kind = 2;
-#endif
           carry = M8::template hidden_layer<STASH>(ring, pipe, q8, bias + (size_t)l * D, h, scales(l), xa_hi, xa_h8, xa_l8, xb_hi,
                                                    xb_h8, xb_l8, w8h, w8l, carry, pc, st, (int)SL.h_off(l - 1), (int)SL.h_off(l));
-#if SUNERF_DBG_BARRIER
-          ring.dbg_kind = 3;
-#endif
-          ring.mark_begin(4);
           out = M8::template out_layer<STASH>(ring, pipe, q8, obias, h, scales(a.n_linear - 1), xb_hi, xb_h8, xb_l8, w8h, w8l, carry, pc, st,
                                               (int)SL.h_off(l));
-          ring.mark_end(4);
-          ring.mark_begin(5);
         } else {
           out = M8::template out_layer<STASH>(ring, pipe, q8, obias, h, scales(a.n_linear - 1), xa_hi, xa_h8, xa_l8, w8h, w8l, carry, pc, st,
                                               (int)SL.h_off(l - 1));
@@ -1237,19 +1163,6 @@ __global__ __launch_bounds__(THREADS, 1) void render_fwd_kernel(RenderArgs a) {
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the two prefetches still in flight target our LDS: drain
-#if SUNERF_DBG_BARRIER
-  if (lane == 0 && blockIdx.x < 64) {
-    float* o = a.weights + ((size_t)blockIdx.x * 4 + wave) * 16;
-    o[0] = (float)ring.dbg_vm; o[1] = (float)ring.dbg_bar; o[2] = (float)ring.dbg_n;
-  }
-#endif
-  ring.mark_end(6);
-#if SUNERF_DBG_TILES
-  if (lane == 0 && blockIdx.x < 64) {
-    float* o = a.weights + ((size_t)blockIdx.x * 4 + wave) * 16;
-    o[0] = (float)ring.dbg_cyc; o[1] = 0.f; o[2] = (float)ring.dbg_cnt;
-  }
-#endif
 }
 
 template <int D, int STASH, bool FP8C, bool HALF = false>

@@ -23,8 +23,6 @@
 // error grows as 2^-24 / s^2 (8 % at 215 solar radii).  The sample point, its radius and A..D are evaluated in fp64 from the
 // fp32 inputs (C in the cancellation-free form (1 - c)(4 + c + c^2) / 3 with 1 - c = s^2 / (1 + c), L as log1p, c^2 as
 // (r^2 - R^2) / r^2): the residual relative error is ~1e-16 / s^2.  The sums stay fp32 (positive terms).
-// -DSUNERF_THOMSON_GEOMETRY_FP32 builds the same arithmetic in fp32: a measurement variant (tools/thomson_render_time.py), not
-// a product configuration.
 //
 // Layout as dt.hip: 32 lanes per ray, one sample per lane and 32-sample chunk (coalesced reads of raw / z, coalesced writes),
 // per-ray sums over the ray's own lanes (butterfly), no float atomics: reruns are bit-identical.  The backward also writes
@@ -38,12 +36,6 @@ namespace {
 constexpr int TH_THREADS = 256;
 constexpr int TH_RAYS = TH_THREADS / 32;      // rays per workgroup (and per step of its walk over the batch)
 constexpr int TH_MAX_GRID = 1024;             // backward: workgroups of the grid (one atomic max each)
-
-#ifdef SUNERF_THOMSON_GEOMETRY_FP32
-typedef float geo_t;
-#else
-typedef double geo_t;
-#endif
 
 struct ThomsonArgs {
   const float* raw;          // (N,S,C) channel 0 = log density (log10 rho for a NeRF, ln rho for a field)
@@ -74,8 +66,8 @@ struct ThomsonArgs {
 
 // lane-uniform quantities of one ray
 struct Ray {
-  geo_t ox, oy, oz, dx, dy, dz;
-  geo_t p2;                  // |o x d|^2 / l^2: squared impact parameter, sin^2(chi) = p2 / r^2
+  double ox, oy, oz, dx, dy, dz;
+  double p2;                 // |o x d|^2 / l^2: squared impact parameter, sin^2(chi) = p2 / r^2
   float len;                 // l = |d| (fp32, as the reference's torch.norm)
   __device__ __forceinline__ void init(const ThomsonArgs& a, int64_t ray) {
     const float* o = a.rays_o + ray * 3;
@@ -83,7 +75,7 @@ struct Ray {
     ox = o[0]; oy = o[1]; oz = o[2];
     dx = d[0]; dy = d[1]; dz = d[2];
     len = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-    const geo_t cx = oy * dz - oz * dy, cy = oz * dx - ox * dz, cz = ox * dy - oy * dx;
+    const double cx = oy * dz - oz * dy, cy = oz * dx - ox * dz, cz = ox * dy - oy * dx;
     p2 = (cx * cx + cy * cy + cz * cz) / (dx * dx + dy * dy + dz * dz);
   }
 };
@@ -95,31 +87,31 @@ struct Sample {
 
 // radius of the sample at z and, when WANT_I, the two scattering intensities per electron
 template <bool WANT_I>
-__device__ __forceinline__ Sample sample_geometry(const Ray& ry, float z, geo_t R, geo_t u) {
-  const geo_t zz = z;
-  const geo_t px = ry.ox + ry.dx * zz, py = ry.oy + ry.dy * zz, pz = ry.oz + ry.dz * zz;
-  const geo_t r2 = px * px + py * py + pz * pz;
-  const geo_t r = sqrt(r2);
+__device__ __forceinline__ Sample sample_geometry(const Ray& ry, float z, double R, double u) {
+  const double zz = z;
+  const double px = ry.ox + ry.dx * zz, py = ry.oy + ry.dy * zz, pz = ry.oz + ry.dz * zz;
+  const double r2 = px * px + py * py + pz * pz;
+  const double r = sqrt(r2);
   Sample o;
   o.r = (float)r;
   o.i_tot = o.i_p = 0.f;
   // inside / on the Sun, or a NaN point.  (On the limb itself c = 0 and (c^2 / s) L below is 0 * inf: the finite check at the
   // end would zero r == R as well, so `>` and `>=` compute the same here; the comparison states the contract.)
   if (!WANT_I || !(r > R)) return o;
-  const geo_t s = R / r, s2 = s * s;
+  const double s = R / r, s2 = s * s;
   // cos^2 from the squares: r^2 - R^2 is exact next to the limb, where 1 - s^2 keeps only the rounding of r (1e-3 of c one
   // fp32 step of z outside a limb at R = 1 / 0.7, and with it of I_P = c s^2 sin^2(chi) at u = 0).  r > R gives r^2 > R^2.
-  const geo_t c2 = (r2 - R * R) / r2, c = sqrt(c2);
-  const geo_t L = geo_t(0.5) * log1p(geo_t(2) * s / (geo_t(1) - s));       // ln((1 + s) / c)
-  const geo_t k = c2 * r / R * L;                                          // (c^2 / s) L
-  const geo_t A = c * s2;
-  const geo_t B = geo_t(-0.125) * ((geo_t(1) - geo_t(3) * s2) - k * (geo_t(1) + geo_t(3) * s2));
-  const geo_t Cc = s2 / (geo_t(1) + c) * (geo_t(4) + c + c2) / geo_t(3);  // 4/3 - c - c^3/3
-  const geo_t D = geo_t(0.125) * ((geo_t(5) + s2) - k * (geo_t(5) - s2));
-  const geo_t sin2chi = ry.p2 / r2;
-  const geo_t it = (geo_t(1) - u) * Cc + u * D;
-  const geo_t ip = sin2chi * ((geo_t(1) - u) * A + u * B);
-  const geo_t itot = geo_t(2) * it - ip;
+  const double c2 = (r2 - R * R) / r2, c = sqrt(c2);
+  const double L = 0.5 * log1p(2.0 * s / (1.0 - s));   // ln((1 + s) / c)
+  const double k = c2 * r / R * L;                      // (c^2 / s) L
+  const double A = c * s2;
+  const double B = -0.125 * ((1.0 - 3.0 * s2) - k * (1.0 + 3.0 * s2));
+  const double Cc = s2 / (1.0 + c) * (4.0 + c + c2) / 3.0;   // 4/3 - c - c^3/3
+  const double D = 0.125 * ((5.0 + s2) - k * (5.0 - s2));
+  const double sin2chi = ry.p2 / r2;
+  const double it = (1.0 - u) * Cc + u * D;
+  const double ip = sin2chi * ((1.0 - u) * A + u * B);
+  const double itot = 2.0 * it - ip;
   const float ft = (float)fabs(itot), fp = (float)fabs(ip);
   if (isfinite(ft) && isfinite(fp)) { o.i_tot = ft; o.i_p = fp; }
   return o;
@@ -136,7 +128,7 @@ __global__ __launch_bounds__(TH_THREADS) void thomson_integral_fwd_kernel(Thomso
   const int64_t ray = (int64_t)blockIdx.x * TH_RAYS + sub;
   if (ray >= a.n_rays) return;                     // (a whole 32-lane group leaves: the shuffles are 32 wide)
   const int S = a.S, n_chunks = (S + 31) >> 5;
-  const geo_t R = a.solar_radius[0], u = a.limb[0];
+  const double R = a.solar_radius[0], u = a.limb[0];
   const float c0 = a.c0[0];
   Ray ry;
   ry.init(a, ray);
@@ -183,7 +175,7 @@ __global__ __launch_bounds__(TH_THREADS) void thomson_integral_bwd_kernel(Thomso
   __shared__ float wave_max[TH_THREADS / 64];
   const int tid = threadIdx.x, n = tid & 31, sub = tid >> 5;
   const int S = a.S, n_chunks = (S + 31) >> 5;
-  const geo_t R = a.solar_radius[0], u = a.limb[0];
+  const double R = a.solar_radius[0], u = a.limb[0];
   const float c0 = a.c0[0];
   const bool ratios = a.g_dist_sun || a.g_dist_obs || a.g_weights;
   const bool want_i = a.g_pixel_b != nullptr;

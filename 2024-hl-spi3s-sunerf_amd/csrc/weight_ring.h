@@ -3,24 +3,6 @@
 #pragma once
 #include "sunerf_common.h"
 
-#ifndef SUNERF_DBG_BARRIER
-#define SUNERF_DBG_BARRIER 0
-#endif
-#ifndef SUNERF_DBG_TILES
-#define SUNERF_DBG_TILES 0
-#endif
-#ifndef SUNERF_DBG_SHIFT
-#define SUNERF_DBG_SHIFT 0
-#endif
-#ifndef SUNERF_DBG_KIND
-#define SUNERF_DBG_KIND 1
-#endif
-// SUNERF_ABL_NO_DMA (round 4, tools/experiments/r4_fwd_dma.sh): timing-only ablation -- the ring is filled once with real
-// pages and never refilled: what the weight stream (its LDS-DMA instructions, its L2 -> LDS traffic) costs the forward.
-// Outputs are wrong, operands stay finite.
-#ifndef SUNERF_ABL_NO_DMA
-#define SUNERF_ABL_NO_DMA 0
-#endif
 namespace sunerf_ring {
 
 constexpr int WAVES = 4;
@@ -53,9 +35,6 @@ struct Ring {
   unsigned dst;          // LDS byte address of this wave's quarter of the ring slot to fill next
   unsigned dst_first;    // ... of slot 0
   unsigned voff;         // lane * 16
-#if SUNERF_ABL_NO_DMA
-  bool priming = true;
-#endif
 
   __device__ __forceinline__ void init(const char* packed, size_t stream_bytes, unsigned lds_base, int wave, int lane) {
     const unsigned quarter = __builtin_amdgcn_readfirstlane(wave) * (PAGE / WAVES);
@@ -73,15 +52,10 @@ struct Ring {
   template <int J>
   __device__ __forceinline__ void issue_piece() {
     static_assert(J >= 0 && J < PIECES, "piece index");
-#if SUNERF_ABL_NO_DMA
-    if (priming)
-#endif
-    {
-      const char* sg = src + (J / 4) * 4096;
-      const unsigned dg = dst + (J / 4) * 4096;
-      asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2 offset:%3"
-                   :: "v"(voff), "s"(dg), "s"(sg), "i"((J % 4) * 1024) : "memory");
-    }
+    const char* sg = src + (J / 4) * 4096;
+    const unsigned dg = dst + (J / 4) * 4096;
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2 offset:%3"
+                 :: "v"(voff), "s"(dg), "s"(sg), "i"((J % 4) * 1024) : "memory");
     if (J == PIECES - 1) {   // page complete: advance to the next page / ring slot
       src += PAGE;
       if (src == src_end) src = src_first;
@@ -100,35 +74,9 @@ struct Ring {
   // the page being acquired, besides the PIECES of the following page
   template <int EXTRA = 0>
   __device__ __forceinline__ void acquire() {
-#if SUNERF_DBG_BARRIER
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(%0)" :: "i"(PIECES + EXTRA) : "memory");
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-    __builtin_amdgcn_s_barrier();
-    const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-    if (dbg_kind == SUNERF_DBG_KIND) { dbg_vm += (unsigned)(t1 - t0); dbg_bar += (unsigned)(t2 - t1); dbg_n += 1; }
-#else
     asm volatile("s_waitcnt vmcnt(%0)" :: "i"(PIECES + EXTRA) : "memory");
     __builtin_amdgcn_s_barrier();
-#endif
   }
-#if SUNERF_DBG_BARRIER
-  unsigned dbg_vm = 0, dbg_bar = 0, dbg_n = 0;
-  int dbg_kind = 0;
-#endif
-#if SUNERF_DBG_TILES
-  // cycles between mark_begin() and mark_end() of the regions tagged SUNERF_DBG_KIND (one kind per build: the counters
-  // live in SGPRs, of which the DMA addressing leaves few)
-  unsigned long long dbg_t0 = 0;
-  unsigned dbg_cyc = 0, dbg_cnt = 0;
-  __device__ __forceinline__ void mark_begin(int kind) { if (kind == SUNERF_DBG_KIND) dbg_t0 = __builtin_amdgcn_s_memtime(); }
-  __device__ __forceinline__ void mark_end(int kind) {
-    if (kind == SUNERF_DBG_KIND && dbg_t0 != 0) { dbg_cyc += (unsigned)((__builtin_amdgcn_s_memtime() - dbg_t0) >> SUNERF_DBG_SHIFT); dbg_cnt += 1; }
-  }
-#else
-  __device__ __forceinline__ void mark_begin(int) {}
-  __device__ __forceinline__ void mark_end(int) {}
-#endif
 };
 
 }  // namespace sunerf_ring

@@ -1234,7 +1234,7 @@ def _dz_guard(d, s):
 
 
 def _pipe_guard():
-    """One workgroup's share of the pipelined backward's workspace: a hand-off ring of PIPE_RING chunk slots."""
+    """One workgroup's share of the pipelined backward's workspace: a hand-off ring of RING (bwd_pipe.hip:53) chunk slots."""
     import mlp_seams as ms
     return ms.PIPE_RING * ms.PIPE_SLOT
 
@@ -1429,7 +1429,7 @@ def mlp_wgrad(shape, device):
 
 @case('sunerf_mlp_backward_pipe', [(256, n, s, acc) for d, n, s in MLP_SHAPES if d == 256 for acc in (0, 1)],
       'bwd_pipe.hip: persistent launch of 256 workgroups, pairs own a layer; fewer chunks than pipelines at these sizes; workspace: '
-      'sticky block (zeroed by the caller), control block, hand-off rings of PIPE_RING 16 slots (guard: _pipe_guard)')
+      'sticky block (zeroed by the caller), control block, hand-off rings of RING 16 slots (guard: _pipe_guard)')
 def mlp_backward_pipe(shape, device):
     d, n, s, acc = shape
     c = Ctx(device)

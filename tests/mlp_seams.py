@@ -7,12 +7,12 @@ tests/test_gpu_mlp_seams.py puts a float64-checked backward probe on the chunks 
 
 CHUNK = 32
 ENC_FRAGS = 6                         # sunerf_common.h:44  SUNERF_KS0: encoding fragments of a stash chunk
-FWD_RAYS_PER_WG = 4                   # weight_ring.h:26  WAVES: render_fwd.hip and render_bwd.hip:215 take one ray per wave
-PIPE_RING = 16                        # bwd_pipe.hip:61-67  chunk slots of a hand-off ring
+FWD_RAYS_PER_WG = 4                   # weight_ring.h:8  WAVES: render_fwd.hip and render_bwd.hip:215 take one ray per wave
+PIPE_RING = 16                        # bwd_pipe.hip:53  RING: chunk slots of a hand-off ring
 PIPE_D, PIPE_PT = 256, 8              # bwd_pipe.hip:48  the pipelined backward's width and workspace tiles
-PIPE_SLOT = (PIPE_D // 16) * 1024     # bwd_pipe.hip:68  one chunk of dZ
+PIPE_SLOT = (PIPE_D // 16) * 1024     # bwd_pipe.hip:57  SLOT: one chunk of dZ
 STASH_FP16, STASH_PHASE = 0, 1        # include/sunerf_hip.h:111-112
-MAX_FWD_GRID = 1024                   # render_fwd.hip:1292
+MAX_FWD_GRID = 1024                   # render_fwd.hip:1177
 
 
 def chunks_per_ray(S):
@@ -38,13 +38,13 @@ def ranges(total, parts):
 # ---- sizes: what the C ABI exposes ------------------------------------------------------------------------------------
 
 def act_chunk_bytes(D, n_linear, fmt):
-    """StashLayout::chunk_bytes (sunerf_common.h:102-111): 6 encoding fragments, then per activation layer D/16 fragments of
+    """StashLayout::chunk_bytes (sunerf_common.h:107): 6 encoding fragments, then per activation layer D/16 fragments of
     16-bit phases or 2 x D/16 of fp16 sin + cos, 1 KiB each."""
     return ENC_FRAGS * 1024 + (n_linear - 1) * (1 if fmt == STASH_PHASE else 2) * (D // 16) * 1024
 
 
 def act_stash_bytes(n_rays, S, D, n_linear, fmt):
-    """sunerf_act_stash_bytes (render_fwd.hip:1325-1330): every chunk plus one spare; phases at D = 256 only."""
+    """sunerf_act_stash_bytes (render_fwd.hip:1220-1225): every chunk plus one spare; phases at D = 256 only."""
     if fmt == STASH_PHASE and D != PIPE_D:
         return 0
     return (total_chunks(n_rays, S) + 1) * act_chunk_bytes(D, n_linear, fmt)
@@ -56,7 +56,7 @@ def dz_chunk_bytes(D, n_linear):
 
 
 def dz_stash_bytes(n_rays, S, D, n_linear):
-    """sunerf_dz_stash_bytes (render_bwd.hip:645-649): every chunk plus the spare."""
+    """sunerf_dz_stash_bytes (render_bwd.hip:611-615): every chunk plus the spare."""
     return (total_chunks(n_rays, S) + 1) * dz_chunk_bytes(D, n_linear)
 
 
@@ -66,12 +66,12 @@ def wgrad_split(n_linear, cus, D):
 
 
 def pipe_pipelines(n_linear, cus=256):
-    """PipeLayout (bwd_pipe.hip:1096-1098): 8 XCD classes x the whole pipelines of 2 (n_linear - 1) workgroups a class holds."""
+    """PipeLayout (bwd_pipe.hip:1083-1084): 8 XCD classes x the whole pipelines of 2 (n_linear - 1) workgroups a class holds."""
     return 8 * ((cus // 8) // (2 * (n_linear - 1)))
 
 
 def pipe_workspace_bytes(n_rays, S, n_linear, cus=256):
-    """sunerf_bwd_pipe_workspace_bytes = PipeLayout::total (bwd_pipe.hip:1093-1109, :1133-1138)."""
+    """sunerf_bwd_pipe_workspace_bytes = PipeLayout::total (bwd_pipe.hip:1076-1096, :1119-1124)."""
     def up(v):
         return (v + 255) // 256 * 256
     n_act, NP = n_linear - 1, pipe_pipelines(n_linear, cus)
@@ -90,7 +90,7 @@ def exact_chunk_samples(D):
 
 def chunk_seams(n_rays, S):
     """The first and the last chunk of the batch; the last chunk of the first and of the last ray -- partial when S % 32 != 0,
-    and with an odd chunk count per ray the one whose dgrad partner is the spare chunk (render_fwd.hip:1328)."""
+    and with an odd chunk count per ray the one whose dgrad partner is the spare chunk (render_fwd.hip:1223)."""
     cpr, total = chunks_per_ray(S), total_chunks(n_rays, S)
     tail = ('partial ' if S % CHUNK else '') + 'last chunk of a ray' + (' (partner: the spare)' if cpr % 2 else '')
     seams = {cpr - 1: tail + ', first ray', total - 1: tail + ', last ray'}
@@ -99,9 +99,9 @@ def chunk_seams(n_rays, S):
 
 
 def forward_seam_rays(n_rays, grid):
-    """render_fwd.hip:957-963 and :1288-1294: workgroup g takes groups of 4 rays g, g + grid, ... with grid = min(groups, CUs or
+    """render_fwd.hip:898-907 and :1175-1179: workgroup g takes groups of 4 rays g, g + grid, ... with grid = min(groups, CUs or
     SUNERF_GRID_CAP_FWD, 1024): the last ray of a sweep, the first ray of every further sweep, the first ray of the last (partial)
-    group.  The stash slices those rays write are what the backward reads (render_fwd.hip:994)."""
+    group.  The stash slices those rays write are what the backward reads (render_fwd.hip:934)."""
     groups = -(-n_rays // FWD_RAYS_PER_WG)
     grid = min(groups, grid, MAX_FWD_GRID)
     rays = {}
@@ -124,7 +124,7 @@ def forward_seams(n_rays, S, grid):
 
 def dgrad_seams(n_rays, S, grid):
     """render_bwd.hip:275-316: one ray per wave, its chunks in pairs (2 pr, 2 pr + 1); with an odd chunk count the last chunk's
-    partner is the spare (:284, :306-316).  Workgroups of 4 rays over min(groups, CUs or SUNERF_GRID_CAP_DGRAD) (:693-698, :301)."""
+    partner is the spare (:284, :306-316).  Workgroups of 4 rays over min(groups, CUs or SUNERF_GRID_CAP_DGRAD) (:658-661, :245)."""
     cpr = chunks_per_ray(S)
     seams = {}
     for ray in (0, n_rays - 1):
@@ -147,9 +147,9 @@ def wgrad_seams(n_rays, S, split):
 
 
 def pipe_seams(n_rays, S, n_linear, cus=256, prologue_every=False):
-    """bwd_pipe.hip:927-932: pipeline P takes chunks [P per, min(total, (P + 1) per)), per = ceil(total / NP): its first and last
-    chunk, where its hand-off rings wrap (cbeg + 16 k, PIPE_RING slots, :61-67, :809: the first two wraps and the last), the
-    short last range.  The prologue (:956-960) splits the chunks over its `cus` workgroups the same way: the first and last chunk
+    """bwd_pipe.hip:913-918: pipeline P takes chunks [P per, min(total, (P + 1) per)), per = ceil(total / NP): its first and last
+    chunk, where its hand-off rings wrap (cbeg + 16 k, RING slots, :53, :531-532: the first two wraps and the last), the
+    short last range.  The prologue (:942-946) splits the chunks over its `cus` workgroups the same way: the first and last chunk
     of the first two, a middle and the last non-empty workgroup's range (``prologue_every``: of all of them)."""
     seams = {}
     for P, (b, e) in enumerate(ranges(total_chunks(n_rays, S), pipe_pipelines(n_linear, cus))):

@@ -1,5 +1,5 @@
 """The pipelined backward's data-gradient waves decode the NEXT chunk's phases behind the matrix instructions of their k-steps
-(csrc/bwd_pipe.hip, PIPE_DECODE_UNDER_CHAIN): the cases in which that order can go wrong -- no main-loop iteration at all, a single
+(csrc/bwd_pipe.hip, the order of an iteration in hidden_stage): the cases in which that order can go wrong -- no main-loop iteration at all, a single
 one (chunk 0 is decoded in the prologue iterations and nothing behind it), the wrap of the five staging buffers, ragged last
 chunks, every layer count -- on BOTH builds of the kernel: W^T as fp16 head + remainder (SUNERF_PIPE_HI_ONLY=0, what
 test_gpu_pipe.py forces) and the single fp16 W^T that the benchmark runs (=1).  Bounds: those of test_gpu_pipe.py for the same

@@ -1,5 +1,5 @@
-"""The LDS image of the pipelined backward's hidden stages (csrc/bwd_pipe.hip, PIPE_LDS_IMAGE: fragments 1088 bytes apart, rows
-possibly permuted) at the smallest shapes where a wrong row, a wrong fragment base or a wrapped staging buffer shows: the
+"""The LDS image of the pipelined backward's hidden stages (csrc/bwd_pipe.hip, "LDS IMAGE": fragments 1088 bytes apart, the
+pair skew) at the smallest shapes where a wrong row, a wrong fragment base or a wrapped staging buffer shows: the
 pipelined backward against the fp64 oracle and against the two-kernel backward, helpers and the 1e-3 per-tensor bound of
 test_gpu_pipe.py.  A row or a fragment taken from the wrong place pairs a dZ with another sample's or another feature's
 activation: the sums then differ from the oracle's by their own size, not by 1e-3."""

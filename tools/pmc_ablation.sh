@@ -1,6 +1,6 @@
 #!/bin/bash
-# Cycles, clock and wait split of the inference forward for the shipped build and energy-ablation builds
-# (tools/energy_ablation.sh): tools/pmc_ablation.sh "" abl_NO_AREAD ...      ("" = shipped)
+# Cycles, clock and wait split of the inference forward for the shipped build and variant builds (tools/build_variant.sh, e.g.
+# of another commit's csrc; outputs are not checked for finiteness): tools/pmc_ablation.sh "" <name> ...      ("" = shipped)
 R=/root/repo
 cd /tmp && export TMPDIR=/tmp
 export SUNERF_FORWARD_PRECISION=fast

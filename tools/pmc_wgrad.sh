@@ -1,5 +1,5 @@
 #!/bin/bash
-# Duration, cycles and clock of wgrad for the shipped build and variants: tools/pmc_wgrad.sh "" nomfma ...
+# Duration, cycles and clock of wgrad for the shipped build and variants (tools/build_variant.sh): tools/pmc_wgrad.sh "" <name> ...
 R=/root/repo
 cd /tmp && export TMPDIR=/tmp
 for v in "$@"; do

@@ -1,4 +1,4 @@
-// Hardware probe: ds_read_b64_tr_b16 under the three LDS images of bwd_pipe.hip (PIPE_LDS_IMAGE 0 / 1 / 2).
+// Hardware probe: ds_read_b64_tr_b16 under the three LDS images measured for bwd_pipe.hip (unskewed, pair skew -- the shipped one --, pair skew + row swizzle).
 //   1. semantics: does each lane's address feed only its own 8 bytes?  A fragment pair is filled with 16-bit values that name
 //      their own byte address; from the shipped (affine) pattern the map (lane, element) -> (lane whose address was used, element
 //      of its 8 bytes) is derived, and every other pattern -- the pair skew, skew + row swizzle, and a scrambled one with no

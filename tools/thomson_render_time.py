@@ -5,9 +5,7 @@
   * a 32768-ray training step of the NeRF (coarse + fine pass, tB/pB MSE, backward): the step's time and the Thomson
     forward + backward kernels' time on its shapes.
 
-Kernel times are CUDA-event medians of the kernel alone on the same shapes.  Run once with the product library and once with
-the fp32-geometry variant (tools/build_variant.sh geo32 -DSUNERF_THOMSON_GEOMETRY_FP32, then SUNERF_HIP_LIB=...) to see
-what the fp64 geometry costs.  One JSON line.
+Kernel times are CUDA-event medians of the kernel alone on the same shapes.  One JSON line.
 
     python tools/thomson_render_time.py [--resolution 1024] [--repeats 5] [--no-mhd]
 """
