@@ -11,7 +11,7 @@ COMMON="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused
 # -amdgpu-mfma-vgpr-form: MFMA accumulators in architectural VGPRs.  The render / dgrad kernels keep their activation
 # fragments in the AGPR half of the register file (see render_fwd.hip), so this removes a v_accvgpr_read per accumulator
 # element from every tile epilogue.  wgrad.hip holds 256 accumulator registers per lane and wants them in AGPRs.
-VGPR_FORM="pack sampler rays columns render_fwd render_bwd dt dt_response_set dem dem_inversion mhd thomson train_step bwd_exact metrics observations reprojection volume grid_field dynamic_grid prep instrument patch likelihood ssim_loss deconvolve psf_grad despike coalign stack noise_gate register enhance"
+VGPR_FORM="pack sampler rays columns render_fwd render_bwd dt dt_response_set dem dem_inversion mhd thomson polarimetry train_step bwd_exact metrics observations reprojection volume grid_field dynamic_grid prep instrument patch likelihood ssim_loss deconvolve psf_grad despike coalign stack noise_gate register enhance"
 AGPR="wgrad bwd_pipe"     # accumulators in AGPRs (bwd_pipe.hip: 128 per weight-gradient wave, W^T fragments per data-gradient wave)
 pids=()
 objs=()

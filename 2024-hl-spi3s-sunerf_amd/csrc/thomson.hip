@@ -29,6 +29,7 @@
 // the bit pattern of max |g_raw| (one integer atomic max per workgroup) that the MLP backward takes as its gradient scale.
 #include "sunerf_common.h"
 #include "ray_scan.h"
+#include "thomson_math.h"
 #include "../../include/sunerf_hip.h"
 
 namespace {
@@ -98,21 +99,8 @@ __device__ __forceinline__ Sample sample_geometry(const Ray& ry, float z, double
   // inside / on the Sun, or a NaN point.  (On the limb itself c = 0 and (c^2 / s) L below is 0 * inf: the finite check at the
   // end would zero r == R as well, so `>` and `>=` compute the same here; the comparison states the contract.)
   if (!WANT_I || !(r > R)) return o;
-  const double s = R / r, s2 = s * s;
-  // cos^2 from the squares: r^2 - R^2 is exact next to the limb, where 1 - s^2 keeps only the rounding of r (1e-3 of c one
-  // fp32 step of z outside a limb at R = 1 / 0.7, and with it of I_P = c s^2 sin^2(chi) at u = 0).  r > R gives r^2 > R^2.
-  const double c2 = (r2 - R * R) / r2, c = sqrt(c2);
-  const double L = 0.5 * log1p(2.0 * s / (1.0 - s));   // ln((1 + s) / c)
-  const double k = c2 * r / R * L;                      // (c^2 / s) L
-  const double A = c * s2;
-  const double B = -0.125 * ((1.0 - 3.0 * s2) - k * (1.0 + 3.0 * s2));
-  const double Cc = s2 / (1.0 + c) * (4.0 + c + c2) / 3.0;   // 4/3 - c - c^3/3
-  const double D = 0.125 * ((5.0 + s2) - k * (5.0 - s2));
-  const double sin2chi = ry.p2 / r2;
-  const double it = (1.0 - u) * Cc + u * D;
-  const double ip = sin2chi * ((1.0 - u) * A + u * B);
-  const double itot = 2.0 * it - ip;
-  const float ft = (float)fabs(itot), fp = (float)fabs(ip);
+  const ThomsonIntensity e = thomson_intensity(r2, r, R, u, ry.p2);   // thomson_math.h: A..D, I_T, I_P, I_tot in fp64
+  const float ft = (float)fabs(e.i_tot), fp = (float)fabs(e.i_p);
   if (isfinite(ft) && isfinite(fp)) { o.i_tot = ft; o.i_p = fp; }
   return o;
 }

@@ -339,6 +339,19 @@ class Instrument:
             kw.setdefault(name, p[:, k])
         return combine(frames, **kw)
 
+    def stokes(self, frames: torch.Tensor, angles, **kw) -> dict:
+        """Polariser exposures ``frames`` [N, C, h, w] observed at ``angles`` turned into Stokes planes, tB and pB with this
+        instrument's noise model as the weights: :func:`sunerf_hip.polarimetry.stokes` with ``a`` and ``b`` of
+        :func:`sunerf_hip.despike.despike_params` (``center``, ``throughput``, ``efficiency``, ``bad``)."""
+        from .despike import despike_params
+        from .polarimetry import stokes
+        if not isinstance(frames, torch.Tensor) or frames.dim() not in (3, 4):
+            raise ValueError('Instrument.stokes: frames must be a tensor [N, C, h, w] or [N, h, w]')
+        p = despike_params(self, 1 if frames.dim() == 3 else frames.shape[1])
+        for k, name in enumerate(('a', 'b')):
+            kw.setdefault(name, p[:, k])
+        return stokes(frames, angles, **kw)
+
     def noise_gate(self, frames: torch.Tensor, **kw) -> dict:
         """A sequence of observed ``frames`` [T, C, h, w] noise-gated with this instrument's noise model as the expected noise
         power: :func:`sunerf_hip.noise_gate.noise_gate` with ``a`` and ``b`` of :func:`sunerf_hip.despike.despike_params`

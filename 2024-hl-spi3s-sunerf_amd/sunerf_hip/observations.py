@@ -28,6 +28,7 @@ from .feed import RayPool
 
 MAX_CHANNELS = 16           # SUNERF_OBS_MAX_CHANNELS
 AU_IN_SOLAR_RADII = 215.03215567054764
+POLARISED_PLANES = (1.0, 2.0)          # the wavelength labels of the two planes of a white-light view: total and polarised brightness
 
 # struct SunerfViewDesc (include/sunerf_hip.h); the library's sizeof is compared when a table is first built
 VIEW_DESC = np.dtype({
@@ -290,6 +291,27 @@ class ObservationSet:
         prepared, grid = prepare_image(image, wcs, device=self.device, **prep)
         return self.add_view(prepared, lat, lon, distance, time, grid=grid, wavelengths=wavelengths, downscale=downscale,
                              center=center, name=name)
+
+    def add_polarised_view(self, frames, angles, lat, lon, distance=AU_IN_SOLAR_RADII, time=0.0, grid: Optional[dict] = None,
+                           tx=None, ty=None, center=None, name: Optional[str] = None, **stokes_kw) -> dict:
+        """Adds the white-light view that ``N`` exposures through a linear polariser make: ``frames`` [N, H, W] at the polariser
+        ``angles`` go through :func:`sunerf_hip.polarimetry.stokes` (``throughput``, ``efficiency``, ``a``, ``b``, ``bad``), and the
+        ``(tB, pB)`` pair becomes a two-plane view -- the planes ``ThompsonScattering`` renders -- with the wavelength labels
+        ``POLARISED_PLANES``.  ``center = (cy, cx)``: the Sun's centre in pixels; default: where the view's pixel axes cross zero
+        angle (``enhance.sun_geometry``).  UNDETERMINED pixels (and pB on the centre pixel) are NaN, so
+        ``pool(drop_nonfinite=True)`` leaves their rays out.  Returns the Stokes dict, with the view's ``index``."""
+        from .enhance import sun_geometry
+        from .polarimetry import stokes
+        from .reprojection import Observer
+        frames = torch.as_tensor(frames)
+        if frames.dim() != 3:
+            raise ValueError(f'add_polarised_view: frames must be (N, H, W) exposures of one detector, got {tuple(frames.shape)}')
+        if center is None:
+            center, _ = sun_geometry(Observer(lat, lon, distance, grid=None if grid is None else dict(grid), tx=tx, ty=ty), self.Rs_per_ds)
+        out = stokes(frames.to(device=self.device, dtype=torch.float32), angles, center=center, **stokes_kw)
+        out['index'] = self.add_view(torch.stack([out['tb'], out['pb']]), lat, lon, distance, time, grid=grid, tx=tx, ty=ty,
+                                     wavelengths=POLARISED_PLANES, name=name)
+        return out
 
     def add_rendered_view(self, loader, lat, lon, time, distance=AU_IN_SOLAR_RADII, wl=None, resolution=None, center=None,
                           key: str = 'image', scale: float = 1.0, **kwargs) -> int:
